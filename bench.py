@@ -21,9 +21,15 @@ Workloads (``BASELINE.json`` / SURVEY 8d), per GPU:
 One "step" = one pass of the hot path over the whole batch: the step kernel (dynamics, goal, reward, done)
 + the render kernel (observation).
 
-Timing: ``--windows`` windows of EXACTLY K steps each, every window bracketed by barrier + synchronize on both
-sides, per window the MAX over ranks; ``ms_per_step`` / ``value`` are the MEDIAN window (min / max reported too:
-one 14 ms window is inside the +-3 % spread between observation-buffer allocations).
+Timing: ``--windows`` windows of EXACTLY K steps each (default one: ``--steps K`` timed steps in all), every window
+bracketed by barrier + synchronize on both sides, per window the MAX over ranks; ``ms_per_step`` / ``value`` are the
+MEDIAN window (min / max reported too: one 14 ms window is inside the +-3 % spread between observation-buffer
+allocations).
+
+``--dump-outputs DIR``: after the timed windows rank 0 writes what the last timed step left in the buffers it writes
+(``pos``, ``steps``, ``reward``, ``dgoals``, ``terminated``, ``truncated`` and the observation) as ``DIR/<name>.npy`` in
+float32 / float64 (see ``dump_outputs``).  The actions come from a seeded generator, so the same arguments give the same
+inputs on every run and two builds can be compared output for output.
 
 One JSON line of at most 4 KB is printed by rank 0 (contract in the task statement; tools/bench_line.py: top-level contract
 fields + ``config`` + ``roofline`` + ``cpu_baseline`` + one short object per other configuration); the FULL record (every
@@ -56,6 +62,47 @@ import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 C4_SEED = 100
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: half of it for the per-environment state, half for the observation sample
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, vec):
+    """Writes the buffers the step path writes, as they are after the last step, to ``out_dir/<name>.npy``.
+
+    Integers of 32 bits and float64 go out as float64, everything else as float32 (both exact).  The state arrays hold
+    every environment while they fit in half of ``DUMP_MAX_BYTES``; beyond that, and always for the observation, they
+    hold the environments of a fixed sample (``np.random.default_rng(DUMP_SEED)``, sorted), listed in ``state_envs.npy`` /
+    ``obs_envs.npy``.
+    """
+    B = vec.num_envs
+    state = {k: getattr(vec, k) for k in ("pos", "steps", "reward", "dgoals", "terminated", "truncated")}
+    arrays = dict(state, obs=vec.obs) if vec.obs is not None else state
+
+    def out_dtype(t):
+        return np.float64 if t.dtype in (torch.float64, torch.int32, torch.int64) else np.float32
+
+    def env_bytes(names):
+        return sum(np.dtype(out_dtype(arrays[k])).itemsize * arrays[k][0].numel() for k in names)
+
+    def sample(per_env):  # None: every environment; else the sample, each of its entries 8 more bytes (the index list)
+        if B * per_env <= DUMP_MAX_BYTES // 2:
+            return None
+        n = max(1, (DUMP_MAX_BYTES // 2) // (per_env + 8))
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+
+    picks = {"state": sample(env_bytes(state))}
+    if vec.obs is not None:
+        picks["obs"] = sample(env_bytes(["obs"]))
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        envs = picks["obs" if name == "obs" else "state"]
+        if envs is not None:
+            t = t[torch.as_tensor(envs, device=t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(out_dtype(t)))
+    for group, envs in picks.items():
+        if envs is not None:
+            np.save(os.path.join(out_dir, group + "_envs.npy"), envs.astype(np.float64))
 
 
 def level1_paths():
@@ -193,7 +240,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=0,
+    ap.add_argument("--windows", type=int, default=1,
                     help="timed windows of --steps steps each (median reported); 0 = as many as fill --min-seconds, at least 7")
     ap.add_argument("--min-seconds", type=float, default=3.0,
                     help="with --windows 0: total timed GPU work (long enough for a device-utilisation sampler to see it)")
@@ -223,6 +270,8 @@ def main():
                          "keeps the first one of the fast class); default: the product default of VecPushWorld")
     ap.add_argument("--full-record", default=None,
                     help="where the full record goes (default gpurun_out/bench_full.json, bench_full_n<N>.json for N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
     if args.obs is None:
         args.obs = "uint8" if args.config == "c3" else "none"
@@ -356,6 +405,8 @@ def main():
         barrier()
         torch.cuda.synchronize()
         t_next += K
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, vec)
 
     # the collectives of the whole job: SUM of the step counters, MAX of every window (a few bytes), and the
     # per-rank medians gathered for the report
