@@ -340,6 +340,13 @@ int64_t pw_engine_obs_stride(const PwEngine* e);       /* recommended env stride
 #define PW_OPT_MAILBOX_FORM 48       /* read-only: 0 no mailbox open, 1 its kernel steps one lane per environment (whole-grid boards / tables in memory), 2 the segments
                                       of the bound batch */
 #define PW_OPT_STEP_ONE_APPLIES 49    /* read-only: 1 when pw_step_render_delta on a batch of one with a completion word takes the one-launch form on this engine */
+#define PW_OPT_EXPAND_FORM 50        /* read-only: the form of this engine's most recent pw_expand4 launch (0 = none yet; it records, it chooses nothing):
+                                      bits 0-3 the kernel family -- 1 lane groups (pw_expand4_kernel), 2 one lane per state with the tables
+                                      in memory (pw_expand4_lane_kernel), 3 pw_expand4_v2_kernel, 4 pw_expand4_v2w_kernel, 5
+                                      pw_expand4_v2q_kernel --, bits 8-15 the movables N, bit 16 kPipe, bit 17 kNT (non-temporal stores),
+                                      bit 18 kPD (pair tables sized per pair), bits 20-23 wavefronts per workgroup, bit 24 the tile order
+                                      (PW_OPT_EXPAND_TILE_ORDER & 1), bit 25 persistent workgroups, bits 32-62 the workgroups of the
+                                      grid.  Bits 16-18 and 24-25 are 0 outside families 3-5. */
 #define PW_OPT_OBS_TUNE_MS 40        /* pw_obs_alloc_tuned: wall-clock budget of the candidate screen in milliseconds (0 = default 10 000): no
                                       further candidate is allocated once it is spent (the best so far is kept and tuned) -- bounds the
                                       constructor when several ranks of a node screen at the same time */

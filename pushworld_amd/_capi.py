@@ -218,6 +218,7 @@ OPTIONS = {
     "obs_screen_ms": 41,       # read-only: what the last screen took
     "step_one_applies": 49,    # read-only: step_render_delta on a batch of one with a completion word is ONE launch on this engine
     "mailbox_form": 48,        # read-only: 0 no mailbox open, 1 lanes / boards, 2 the segments of the bound batch
+    "expand_form": 50,         # read-only: kernel instance and grid of the last pw_expand4 launch (decode_expand_form)
     "mailbox_seg": 47,         # the resident kernel of a fully bound batch runs its segments (tables in LDS): 0 automatic, 2 never
     "step_one_fused": 46,      # step_render_delta on a batch of one with a completion word: 1 (default) one launch, 2 ... writing whole rows, 0 two launches
     "bind_min_envs": 36,       # pw_batch_bind: environments of a batch that must play a puzzle for it to be bound (0 = default 48)
@@ -242,6 +243,19 @@ _OPTION_VALUES_BY_KEY = {"step_boards": {"auto": 0, "never": 2},
                          "expand_lds_tables": {"auto": 0, "never": 2},
                          "step_mixed_groups": {"auto": 0, "never": 2},
                          "step_lds_tables": {"auto": 0, "always": 1, "never": 2}}
+
+EXPAND_FAMILIES = {1: "group", 2: "lane", 3: "v2", 4: "v2w", 5: "v2q"}
+
+
+def decode_expand_form(word: int) -> dict:
+    """The fields of ``get_option("expand_form")`` (PW_OPT_EXPAND_FORM, include/pushworld_amd.h): which pw_expand4 kernel
+    instance the engine's last expansion launched, and on how many workgroups.  ``None`` before the first launch."""
+    word = int(word)
+    if word == 0:
+        return None
+    return {"family": EXPAND_FAMILIES[word & 15], "n": (word >> 8) & 255, "pipe": (word >> 16) & 1, "nt": (word >> 17) & 1,
+            "pd": (word >> 18) & 1, "waves": (word >> 20) & 15, "tile_order": (word >> 24) & 1,
+            "persistent": (word >> 25) & 1, "groups": word >> 32}
 
 
 def _load():

@@ -678,6 +678,7 @@ int pw_engine_create(const PwPuzzleSet* s, const PwEngineConfig* cfg, PwEngine**
   e->expand_groups_per_cu = 0;
   e->search_batch_groups_per_cu = 0;
   e->expand_wg_waves = 0;
+  e->expand_form = 0;
   e->step_mixed = 0;
   e->num_cus = 256;
   e->d_search_slab = nullptr;
@@ -1837,6 +1838,14 @@ int pw_step_render_delta(PwEngine* e, const int32_t* puzzle_id, const uint8_t* a
 
 static constexpr int64_t kExpandLaneStates = 131072;  // pw_expand4: frontiers from this size on run one lane per state
 
+// PW_OPT_EXPAND_FORM: which kernel instance and grid a pw_expand4 launch used, packed as include/pushworld_amd.h lays it out
+static int64_t expand_form_word(int family, int n, bool pipe, bool nt, bool pair_dims, int waves, int tile_order, bool persistent,
+                                int64_t groups) {
+  return static_cast<int64_t>(family) | (static_cast<int64_t>(n) << 8) | (pipe ? 1ll << 16 : 0) | (nt ? 1ll << 17 : 0) |
+         (pair_dims ? 1ll << 18 : 0) | (static_cast<int64_t>(waves) << 20) | (static_cast<int64_t>(tile_order) << 24) |
+         (persistent ? 1ll << 25 : 0) | (groups << 32);
+}
+
 int pw_expand4(PwEngine* e, int32_t puzzle, const int32_t* states, int32_t* succ, uint32_t* moved, uint8_t* goal,
                int32_t num_states, void* stream) try {
   if (!e) return pw_fail(PW_EINVAL, "null engine");
@@ -1934,7 +1943,13 @@ int pw_expand4(PwEngine* e, int32_t puzzle, const int32_t* states, int32_t* succ
       else if (tiles_per_wave > 0)  // (a small frontier still fills the chip: at least 8 workgroups per CU while there are tiles)
         groups = std::max<int64_t>((blocks + tiles_per_wave - 1) / tiles_per_wave, std::min<int64_t>(blocks, static_cast<int64_t>(e->num_cus) * 8));
       else groups = std::min<int64_t>(blocks, static_cast<int64_t>(e->num_cus) * (table_bytes <= 32u * 1024u ? 8 : std::min<int64_t>(2, resident)));
+      // tile order 1: workgroup b sweeps the eighth b mod 8 of the tiles -- with fewer than 8 workgroups (frontiers of fewer
+      // than 8 blocks) the other eighths would have none; the extra workgroups of a small frontier find no tiles of their own
+      if (x.tile_order == 1 && groups < 8) groups = 8;
       const dim3 grid(static_cast<unsigned>(groups)), block(static_cast<unsigned>(64 * waves));
+      // (kPipe 0 instances store non-temporally, and so do all per-pair ones: 17 .. 20 movables among them)
+      e->expand_form = expand_form_word(n > 16 ? 5 : (waves == 8 ? 4 : 3), n, pipe, nt || !pipe || pair_dims, pair_dims, waves,
+                                        x.tile_order, tiles_per_wave == 0, groups);
 #define PW_X2P(K) /* per-pair table dimensions (7 .. 16 movables): the same grids; no plain-store A/B instance */          \
   case K: {                                                                                                               \
     const void* fn = waves == 8 ? reinterpret_cast<const void*>(pw_expand4_v2w_kernel<K, true>)                           \
@@ -2013,6 +2028,7 @@ int pw_expand4(PwEngine* e, int32_t puzzle, const int32_t* states, int32_t* succ
     const size_t lds = static_cast<size_t>(64) * (per_pass * n + 2 + np_lane / 2 + 1) * sizeof(int);
     const bool flags_vec = reinterpret_cast<uintptr_t>(moved) % 16 == 0 && reinterpret_cast<uintptr_t>(goal) % 4 == 0;
     const int vec_out = flags_vec ? width : -width;
+    e->expand_form = expand_form_word(2, n, false, false, false, 1, 0, false, grid.x);
 #define PW_X1(NP)                                                                                         \
   do {                                                                                                    \
     if (per_pass == 4) hipLaunchKernelGGL((pw_expand4_lane_kernel<NP, true>), grid, wave, lds, st, a, vec_out, per_pass);  \
@@ -2026,6 +2042,7 @@ int pw_expand4(PwEngine* e, int32_t puzzle, const int32_t* states, int32_t* succ
     prof.close();
     return check_launch("pw_expand4");
   }
+  e->expand_form = expand_form_word(1, n, false, false, false, 4, 0, false, (n <= 8 || (n <= 16 && !e->step_wide_groups)) ? g8.x : (n <= 16 ? g16.x : g32.x));
   if (n <= 8) {
     if (tab) hipLaunchKernelGGL((pw_expand4_kernel<8, true>), g8, block, 0, st, a);
     else hipLaunchKernelGGL((pw_expand4_kernel<8, false>), g8, block, 0, st, a);
@@ -2190,6 +2207,7 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
     case PW_OPT_TUNED_NS:
     case PW_OPT_STEP_TABLE_BYTES:
     case PW_OPT_STEP_TABLE_PUZZLES:
+    case PW_OPT_EXPAND_FORM:
       return pw_fail(PW_EINVAL, "read-only option");
     case PW_OPT_STEP_TABLES: {
       if (value < 0 || value > 3)
@@ -2249,6 +2267,7 @@ int64_t pw_engine_get_option(const PwEngine* e, int32_t option) try {
     case PW_OPT_EXPAND_GROUPS_PER_CU: return e->expand_groups_per_cu;
     case PW_OPT_SEARCH_BATCH_GROUPS_PER_CU: return e->search_batch_groups_per_cu;
     case PW_OPT_EXPAND_WG_WAVES: return e->expand_wg_waves;
+    case PW_OPT_EXPAND_FORM: return e->expand_form;
     case PW_OPT_STEP_BLOCK_ORDER: return e->step_reverse;
     case PW_OPT_STEP_BOARDS: return e->step_boards;
     case PW_OPT_STEP_BOARD_SET: return e->d_boards ? 1 : 0;

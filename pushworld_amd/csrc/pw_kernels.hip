@@ -177,6 +177,7 @@ struct PwEngine {
   int expand_wg_waves;  // PW_OPT_EXPAND_WG_WAVES: cap on the wavefronts of a lone workgroup per CU (0 = automatic)
   int search_batch_groups_per_cu;  // PW_OPT_SEARCH_BATCH_GROUPS_PER_CU (0 = automatic)
   int expand_groups_per_cu;  // PW_OPT_EXPAND_GROUPS_PER_CU: persistent workgroups per CU (0 = as many as fit LDS, at most 8)
+  int64_t expand_form;     // PW_OPT_EXPAND_FORM (read-only): what the most recent pw_expand4 launched (0 = nothing yet)
   int64_t ovl_bytes;
   int ovl_puzzles;         // puzzles with tables
   std::vector<uint8_t> ovl_has;  // [set size] host copy: puzzle p has tables

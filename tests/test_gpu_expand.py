@@ -2,6 +2,7 @@
 order and Position2D encoding, checked against the oracle (order="cpp") and the C++
 reference's own known answers (cpp/test/test_pushworld_puzzle.cc, cpp/test/search/*)."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -412,39 +413,6 @@ def test_pair_tables_sized_per_pair_against_the_oracle():
     assert checked >= 40
 
 
-def _many_movables_text(rng, n_mov, cols=20, rows=14):
-    """a puzzle with n_mov movables (agent included) of 1-3 cells, goals for a third of them, some walls"""
-    grid = [[[] for _ in range(cols)] for _ in range(rows)]
-
-    def blob(n):
-        cells = [(int(rng.integers(0, cols)), int(rng.integers(0, rows)))]
-        for _ in range(n - 1):
-            bx, by = cells[int(rng.integers(0, len(cells)))]
-            dx, dy = [(1, 0), (-1, 0), (0, 1), (0, -1)][int(rng.integers(0, 4))]
-            if 0 <= bx + dx < cols and 0 <= by + dy < rows and (bx + dx, by + dy) not in cells:
-                cells.append((bx + dx, by + dy))
-        return cells
-
-    for _ in range(int(rng.integers(4, 14))):
-        grid[int(rng.integers(0, rows))][int(rng.integers(0, cols))].append("W")
-    names = ["A"] + [f"M{k}" for k in range(1, n_mov)]
-    for name in names:
-        while True:
-            cells = blob(int(rng.integers(1, 4)))
-            if all(not grid[y][x] for x, y in cells):
-                for x, y in cells:
-                    grid[y][x].append(name)
-                break
-    for k in range(1, n_mov):
-        if rng.random() < 0.35:
-            x, y = int(rng.integers(0, cols)), int(rng.integers(0, rows))
-            if not any(t.startswith("G") or t == "W" for t in grid[y][x]):
-                grid[y][x].append(f"G{k}")
-    if not any(t.startswith("G") for row in grid for c in row for t in c):
-        grid[0][0] = [t for t in grid[0][0] if t != "W"] + ["G1"]
-    return "\n".join(" ".join("+".join(c) if c else "." for c in row) for row in grid) + "\n"
-
-
 def test_wide_work_word_17_to_20_movables_against_the_oracle():
     """pw_expand4_v2_kernel with a 128-bit work word (4 bits per movable and action): 17 .. 20 movables, per-pair byte tables
     (round 5; `Clean Sweep`, 19 movables, was the one benchmark puzzle left to the lane kernel).  `Clean Sweep` and seeded random
@@ -456,6 +424,9 @@ def test_wide_work_word_17_to_20_movables_against_the_oracle():
     from pushworld_amd.puzzle import PushWorldPuzzle
     from pushworld_amd.search import BreadthFirstSearch
 
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from puzzle_gen import many_movables_text
+
     texts = []
     for lv in (1, 2, 3, 4):
         for path in bd.level_paths(lv):
@@ -466,7 +437,7 @@ def test_wide_work_word_17_to_20_movables_against_the_oracle():
     assert any(name.startswith("Clean Sweep") for name, _ in texts)
     rng = np.random.default_rng(1719)
     for n in (17, 18, 19, 20, 20):
-        texts.append((f"random{n}", _many_movables_text(rng, n)))
+        texts.append((f"random{n}", many_movables_text(rng, n)))
     high_moves = 0
     for name, text in texts:
         oz = c_oracle.COraclePuzzle(text, order="cpp")

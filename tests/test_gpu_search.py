@@ -384,8 +384,9 @@ def test_search_batch_equals_a_host_breadth_first_search(golden):
     eng = _capi.Engine(pset, None, 3, 1, _capi.OBS_U8)
     oracles = [c_oracle.COraclePuzzle(t) for t in texts]
     seen_verdicts = set()
+    results = {}
     for cap in (300, 5000, 200000):
-        verdict, plan_len, n_states = search_batch(eng, None, max_states=cap)
+        verdict, plan_len, n_states = results[cap] = search_batch(eng, None, max_states=cap)
         for i, k in enumerate(keys):
             m = golden.meta[k]
             if m["num_movables"] > 8 or m["width"] > 16 or m["height"] > 16:
@@ -400,7 +401,29 @@ def test_search_batch_equals_a_host_breadth_first_search(golden):
             seen_verdicts.add(want_v)
     assert seen_verdicts == {0, 1, 2}
     # plans: A shortest plan of every solved puzzle, valid under the oracle (replayed from the initial state)
-    v_p, l_p, _, plans = search_batch(eng, None, max_states=5000, plan_cap=64)
+    v_p, l_p, n_p, plans = search_batch(eng, None, max_states=5000, plan_cap=64)
+    # the persistent workgroups pull puzzles from a counter: how many there are (PW_OPT_SEARCH_BATCH_GROUPS_PER_CU: at most that
+    # many per CU, one per puzzle beyond) changes no result.  The set repeated past 3 workgroups per CU: at 1 and 3 per CU (and the
+    # default 2) every workgroup searches several puzzles one after the other, at 8 each searches one -- verdicts, plan lengths,
+    # state counts and plans equal those of the set searched once
+    import torch
+
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    rep = np.tile(np.arange(len(keys), dtype=np.int32), -(-(3 * ncu + 1) // len(keys)))
+    assert len(rep) > 3 * ncu
+    try:
+        for per_cu in (0, 1, 3, 8):
+            eng.set_option("search_batch_groups_per_cu", per_cu)
+            for cap in (300, 5000):
+                got = search_batch(eng, rep, max_states=cap)
+                for g, w in zip(got, results[cap]):
+                    assert (np.asarray(g) == np.asarray(w)[rep]).all(), (per_cu, cap)
+            got = search_batch(eng, rep, max_states=5000, plan_cap=64)
+            for g, w in zip(got[:3], (v_p, l_p, n_p)):
+                assert (np.asarray(g) == np.asarray(w)[rep]).all(), per_cu
+            assert got[3] == [plans[i] for i in rep], per_cu
+    finally:
+        eng.set_option("search_batch_groups_per_cu", 0)
     v_all, p_all, _ = search_batch(eng, None, max_states=5000)
     # (with plans a goal state that found no room in the full store has no links to walk: such a search is `unknown`)
     lost = (v_all == 1) & (v_p == 2)
