@@ -688,6 +688,44 @@ int pw_search_plan(PwSearch* s, int64_t index, uint8_t* actions, int32_t cap, vo
 int pw_search_batch(PwEngine* e, const int32_t* puzzles, int32_t n, int64_t max_states_each, int32_t novelty_width,
                     uint8_t* verdict, int32_t* plan_len, int32_t* num_states, uint8_t* plans, int32_t plan_cap, void* stream);
 
+/* ---------------------------------------------------------- recursive graph distance (RGD) heuristic
+ * RecursiveGraphDistanceHeuristic::estimate_cost_to_goal (cpp/src/heuristics/recursive_graph_distance.cc:43-252) for a
+ * whole array of states of ONE puzzle of an engine's set.
+ *
+ * pw_puzzle_movement_graph: the feasible-movement graph of movable `obj` (domain_transition_graph.cc:113-216), host only.
+ *   masks  host uint8 [height][width]: bit a (0..3 = L, R, U, D) = an edge from (x, y) in action a's direction,
+ *          bit 4 = (x, y) is a node (every start position is one, edgeless or not).
+ *
+ * pw_rgd_create builds the graphs of every movable, uploads them and computes on the device the shortest-path length
+ * between every pair of nodes of every graph (PathDistances::getDistance, domain_transition_graph.cc:218-300): one
+ * wavefront per (movable, target) runs a breadth-first search over the reversed graph, one grid row per lane.  One device
+ * allocation of sum over movables of nodes^2 * 2 bytes plus small tables; PW_ELIMIT above PW_RGD_MAX_BYTES.  Synchronous.
+ *   fewest_tools  1: the reference default (recursive_graph_distance.h:179, what run_planner uses); 0: every goal's cost is
+ *                 searched at pushing depth N - 2 (recursive_graph_distance.cc:53-58)
+ *   budget        recursion frames (calls of get_recursive_pushing_cost) one state may take; 0 = PW_RGD_DEFAULT_BUDGET.
+ *                 A state that needs more gets NaN and counts in pw_rgd_exceeded.  Each frame costs a few dozen dependent
+ *                 table reads of one lane, so the budget is what bounds a launch: at 65 536 frames one launch of 2^20
+ *                 full-depth states of a Level-1 puzzle with 11 movables ran 144 s (profiles/rgd_eval.txt); fewest-tools
+ *                 states on Level 1 stay below 4 096.
+ *
+ * pw_rgd_eval: cost[k] = estimate_cost_to_goal of states[k] (+inf: provably no way to the goal), bit-identical to the
+ *   reference.  states device int32 [count][N] Position2D (x * 10000 + y), pw_expand4's format; cost device float [count].
+ *   One deviation: a state with a movable off its own graph gets NaN, where the reference throws from .at() (states
+ *   reachable from the initial state never are).  Asynchronous on `stream`: no allocation, no synchronisation (capturable).
+ * pw_rgd_distances: d[k] = the graph distance of movable `obj` from src[k] to dst[k] (device int32 Position2D in, device
+ *   float out): 0 when src == dst is a node, +inf when dst is not a node or cannot be reached.  Asynchronous.
+ * pw_rgd_exceeded: states that ran out of budget since pw_rgd_create (synchronises `stream`). */
+#define PW_RGD_MAX_BYTES (1ll << 30)
+#define PW_RGD_DEFAULT_BUDGET (1ll << 12)
+typedef struct PwRgd PwRgd;
+int pw_puzzle_movement_graph(const PwPuzzle* p, int32_t obj, uint8_t* masks);
+int pw_rgd_create(PwEngine* e, int32_t puzzle, int32_t fewest_tools, int64_t budget, PwRgd** out);
+void pw_rgd_destroy(PwRgd* r);
+int pw_rgd_eval(PwRgd* r, const int32_t* states, float* cost, int32_t count, void* stream);
+int pw_rgd_distances(PwRgd* r, int32_t obj, const int32_t* src, const int32_t* dst, float* d, int32_t count,
+                     void* stream);
+int64_t pw_rgd_exceeded(PwRgd* r, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

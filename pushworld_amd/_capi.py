@@ -175,6 +175,12 @@ SIGNATURES = {
     "pw_counters_reset": (c_int, [c_void_p, c_void_p]),
     "pw_next_state": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "pw_plan_states": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pw_puzzle_movement_graph": (c_int, [c_void_p, c_int32, c_void_p]),
+    "pw_rgd_create": (c_int, [c_void_p, c_int32, c_int32, c_int64, POINTER(c_void_p)]),
+    "pw_rgd_destroy": (None, [c_void_p]),
+    "pw_rgd_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_rgd_distances": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_rgd_exceeded": (c_int64, [c_void_p, c_void_p]),
 }
 
 # pw_engine_set_option keys (include/pushworld_amd.h)
@@ -357,6 +363,12 @@ class ParsedPuzzle:
     @property
     def agent_wall_cells(self):
         return self._lazy("aw", lambda: _cells(lib.pw_puzzle_agent_wall_cells, self.handle))
+
+    def movement_graph_masks(self, obj: int) -> "np.ndarray":
+        """``pw_puzzle_movement_graph``: uint8 [height, width], bit a = edge in action a's direction, bit 4 = node."""
+        out = np.zeros((self.height, self.width), np.uint8)
+        check(lib.pw_puzzle_movement_graph(self.handle, int(obj), c_void_p(out.ctypes.data)))
+        return out
 
     @property
     def names(self):

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <cstdio>
 #include <cstring>
@@ -659,3 +660,156 @@ int pw_puzzleset_load(const char* path, int device, PwPuzzleSet** out) try {
 }
 
 }  // extern "C"
+
+// ---- feasible-movement graphs of the RGD heuristic (domain_transition_graph.cc:113-216) ----------------------------
+// The reference grows the graphs from the initial positions with a frontier and a map from "pusher transition" to the
+// object transitions waiting for it.  The graphs are the least fixed point of a monotone rule, so the order of discovery
+// does not matter: here a node event tries the four moves of a new node, and an edge event re-tries the moves of every
+// object that the new pusher edge could push (the waiting transitions, recomputed from the push offsets instead of stored).
+namespace {
+
+struct GraphBuilder {
+  const PwPuzzleHeader& h;
+  int W, H, N;
+  std::vector<std::vector<PwCell>> cells;          // shape cells of every movable
+  const uint64_t *wall, *awall;
+  std::vector<std::vector<PwCell>> offs;           // [(a * N + i) * N + j]: push offsets of pusher i against pushee j
+  std::vector<uint8_t>& m;
+  std::vector<std::array<int, 4>> work;            // (kind, j, x, y) -- kind 0: node, 1..4: edge in action kind - 1
+
+  static constexpr int kDx[4] = {-1, 1, 0, 0};
+  static constexpr int kDy[4] = {0, 0, -1, 1};
+
+  GraphBuilder(const PwPuzzleHeader& hh, const uint8_t* blob, std::vector<uint8_t>& masks)
+      : h(hh), W(hh.W), H(hh.H), N(hh.N), m(masks) {
+    const uint8_t* b = blob + h.base;
+    wall = reinterpret_cast<const uint64_t*>(b + h.off_wall);
+    awall = reinterpret_cast<const uint64_t*>(b + h.off_awall);
+    const uint64_t* rows = reinterpret_cast<const uint64_t*>(b + h.off_shapes);
+    cells.resize(N);
+    for (int j = 0; j < N; j++)
+      for (int r = 0; r < h.objtab[j].h; r++)
+        for (int c = 0; c < h.objtab[j].w; c++)
+          if ((rows[h.objtab[j].row_off + r] >> c) & 1ull) cells[j].push_back({c, r});
+    offs.resize(4 * N * N);
+    for (int a = 0; a < 4; a++)
+      for (int i = 0; i < N; i++)
+        for (int j = 1; j < N; j++) offsets(a, i, j, offs[(a * N + i) * N + j]);
+    m.assign(static_cast<size_t>(N) * H * W, 0);
+  }
+
+  // pushworld_puzzle.cc:123-138: pushee cell - (pusher cell + displacement), unless the pusher already overlaps there
+  void offsets(int a, int i, int j, std::vector<PwCell>& out) const {
+    std::set<PwCell> cand, cj(cells[j].begin(), cells[j].end());
+    for (const auto& p : cells[i])
+      for (const auto& q : cells[j]) cand.insert({q.first - p.first - kDx[a], q.second - p.second - kDy[a]});
+    out.clear();
+    for (const auto& r : cand) {
+      bool overlap = false;
+      for (const auto& p : cells[i]) overlap = overlap || cj.count({p.first + r.first, p.second + r.second});
+      if (!overlap) out.push_back(r);
+    }
+  }
+
+  // movable j placed at (x, y) lies inside the grid: [0, W - w] x [0, H - h] (pushworld_puzzle.cc:162-170)
+  bool inside(int j, int x, int y) const {
+    return x >= 0 && y >= 0 && x <= W - h.objtab[j].w && y <= H - h.objtab[j].h;
+  }
+  bool hits_wall(int j, int x, int y) const {
+    const uint64_t* rows = j == 0 ? awall : wall;  // the agent also collides with agent walls (cc:327-337)
+    for (const auto& c : cells[j]) {
+      const int cx = x + c.first, cy = y + c.second;
+      if (cx >= 0 && cy >= 0 && cx < W && cy < H && ((rows[cy] >> cx) & 1ull)) return true;
+    }
+    return false;
+  }
+  // static collision (cc:147-172): inside the grid, free of walls now, on a wall after the move
+  bool blocked(int j, int x, int y, int a) const {
+    return inside(j, x, y) && !hits_wall(j, x, y) && hits_wall(j, x + kDx[a], y + kDy[a]);
+  }
+  uint8_t& at(int j, int x, int y) { return m[(static_cast<size_t>(j) * H + y) * W + x]; }
+  uint8_t get(int j, int x, int y) const {
+    return (x >= 0 && y >= 0 && x < W && y < H) ? m[(static_cast<size_t>(j) * H + y) * W + x] : 0;
+  }
+
+  void add_node(int j, int x, int y) {
+    if (at(j, x, y) & PW_RGD_NODE) return;
+    at(j, x, y) |= PW_RGD_NODE;
+    work.push_back({0, j, x, y});
+  }
+
+  // the move of movable j from its node (x, y) in action a, if it is feasible now
+  void try_edge(int j, int x, int y, int a) {
+    if (at(j, x, y) & (1u << a)) return;
+    if (blocked(j, x, y, a)) return;
+    const int ex = x + kDx[a], ey = y + kDy[a];
+    // Only reachable from a start position that overlaps a wall, where the reference's graph would run off the grid.
+    if (!inside(j, ex, ey)) return;
+    if (j != 0) {  // some other movable must be able to make the pushing move already (domain_transition_graph.cc:169-206)
+      bool pushed = false;
+      for (int i = 0; i < N && !pushed; i++) {
+        if (i == j) continue;
+        for (const auto& r : offs[(a * N + i) * N + j])
+          if (get(i, x + r.first, y + r.second) & (1u << a)) {
+            pushed = true;
+            break;
+          }
+      }
+      if (!pushed) return;
+    }
+    at(j, x, y) |= static_cast<uint8_t>(1u << a);
+    work.push_back({1 + a, j, x, y});
+    add_node(j, ex, ey);
+  }
+
+  void run() {
+    for (int j = 0; j < N; j++) add_node(j, h.init[j][0], h.init[j][1]);
+    while (!work.empty()) {
+      const std::array<int, 4> w = work.back();
+      work.pop_back();
+      const int kind = w[0], i = w[1], x = w[2], y = w[3];
+      if (kind == 0) {
+        for (int a = 0; a < 4; a++) try_edge(i, x, y, a);
+        continue;
+      }
+      const int a = kind - 1;  // pusher i gained the edge (x, y) -> (x, y) + d_a: retry the movables it can push
+      for (int j = 1; j < N; j++) {
+        if (j == i) continue;
+        for (const auto& r : offs[(a * N + i) * N + j]) {
+          const int px = x - r.first, py = y - r.second;
+          if (get(j, px, py) & PW_RGD_NODE) try_edge(j, px, py, a);
+        }
+      }
+    }
+  }
+};
+
+constexpr int GraphBuilder::kDx[4];
+constexpr int GraphBuilder::kDy[4];
+
+}  // namespace
+
+void pw_movement_graphs(const PwPuzzleHeader& h, const uint8_t* blob, std::vector<uint8_t>& masks) {
+  GraphBuilder g(h, blob, masks);
+  g.run();
+}
+
+void pw_push_offsets(const PwPuzzleHeader& h, const uint8_t* blob, std::vector<std::vector<PwCell>>& out) {
+  std::vector<uint8_t> unused;
+  GraphBuilder g(h, blob, unused);
+  out = g.offs;
+}
+
+extern "C" int pw_puzzle_movement_graph(const PwPuzzle* p, int32_t obj, uint8_t* masks) try {
+  if (!p || !masks) return pw_fail(PW_EINVAL, "null argument");
+  if (obj < 0 || obj >= static_cast<int>(p->names.size())) return pw_fail(PW_EINVAL, "bad object index");
+  PwPuzzleHeader hdr;
+  std::vector<uint8_t> blob, m;
+  pack_puzzle(*p, &hdr, blob);
+  pw_movement_graphs(hdr, blob.data(), m);
+  const size_t plane = static_cast<size_t>(p->width) * p->height;
+  std::memcpy(masks, m.data() + plane * obj, plane);
+  return PW_OK;
+} catch (...) {
+  return pw_current_exception();  // nothing C++ leaves the C ABI
+}

@@ -43,6 +43,16 @@ int pw_fail(int code, const std::string& msg);
 // no C++ exception crosses the C ABI (host vectors and strings are the only things that can throw).
 int pw_current_exception() noexcept;
 
+// Feasible-movement graphs (domain_transition_graph.cc:113-216) of the packed puzzle `h` (its tables at blob + h.base):
+// masks[(j * H + y) * W + x] of movable j, bit a (0 .. 3 = L, R, U, D) = an edge from (x, y) in action a's direction,
+// PW_RGD_NODE = (x, y) is a node.  The least fixed point of "an object can move where no static obstacle stops it and
+// some other object (or, for the agent, nothing) can already make that move", found with a worklist.
+#define PW_RGD_NODE 0x10u
+void pw_movement_graphs(const PwPuzzleHeader& h, const uint8_t* blob, std::vector<uint8_t>& masks);
+// out[(a * N + i) * N + j]: relative positions (pusher i - pushee j) from which moving i in action a's direction pushes
+// j (pushworld_puzzle.cc:123-138), as (dx, dy) pairs without bounds; empty for j = 0 (the agent is never pushed).
+void pw_push_offsets(const PwPuzzleHeader& h, const uint8_t* blob, std::vector<std::vector<PwCell>>& out);
+
 // Makes `device` the calling thread's current HIP device for the lifetime of the guard and restores the caller's
 // device afterwards: no entry point of the C ABI changes the caller's current device (and therefore
 // torch.cuda.current_device()), and everything an entry point allocates or launches lands on the device of the

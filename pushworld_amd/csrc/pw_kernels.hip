@@ -405,4 +405,5 @@ struct PageRec {
 #include "pw_engine.inc"
 #include "pw_mailbox.inc"
 #include "pw_search.inc"
+#include "pw_rgd.inc"
 #include "pw_generate.inc"

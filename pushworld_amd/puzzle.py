@@ -80,6 +80,16 @@ def default_device_index() -> int:
     return torch.cuda.current_device()
 
 
+def masks_to_graph(masks: np.ndarray):
+    """``{(x, y): {(x, y), ...}}`` from the uint8 [H, W] masks of ``pw_puzzle_movement_graph``."""
+    graph = {}
+    for y, x in zip(*np.nonzero(masks & 0x10)):
+        m = int(masks[y, x])
+        graph[(int(x), int(y))] = {(int(x) + int(dx), int(y) + int(dy))
+                                   for a, (dx, dy) in enumerate(Actions.DISPLACEMENTS) if (m >> a) & 1}
+    return graph
+
+
 def _as_state(state) -> State:
     return tuple((int(p[0]), int(p[1])) for p in state)
 
@@ -304,6 +314,11 @@ class PushWorldPuzzle:
         if F:
             eng.expand4(0, st, succ, moved, goal)
         return succ, moved, goal
+
+    def movement_graph(self, obj: int):
+        """The feasible-movement graph of movable ``obj`` (cpp/src/heuristics/domain_transition_graph.cc:113-216) in the
+        reference's ``FeasibleMovementGraph`` shape: ``{(x, y): {(x, y), ...}}``, every node a key.  Host only."""
+        return masks_to_graph(self._parsed.movement_graph_masks(obj))
 
     # ---------------------------------------------------------------- rendering
     def render(self, state: State, border_width: int = DEFAULT_BORDER_WIDTH,

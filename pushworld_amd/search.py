@@ -215,6 +215,87 @@ class NoveltyTables:
     __del__ = close
 
 
+class RecursiveGraphDistance:
+    """Batched ``RecursiveGraphDistanceHeuristic`` (cpp/src/heuristics/recursive_graph_distance.cc:43-252) of one puzzle:
+    ``evaluate`` returns for every state what ``estimate_cost_to_goal`` returns (+inf: provably no way to the goal).
+
+    Args:
+        puzzle: a ``PushWorldPuzzle`` (or a ``SetPuzzle``).
+        fewest_tools: True (the reference default, what ``run_planner`` uses): the cost of the fewest tools that gives a
+            finite cost; False: every goal is searched with up to N - 2 tools.
+        budget: recursion frames one state may take (None: ``pw_rgd_create``'s default, 4 096).  States that need more
+            get NaN and count in ``exceeded``.
+
+    States with a movable off its own movement graph get NaN too (the reference throws); reachable states never do.
+    """
+
+    def __init__(self, puzzle, fewest_tools: bool = True, budget: Optional[int] = None):
+        self.puzzle = puzzle
+        self._engine = puzzle._engine()
+        self.device = self._engine.device
+        self.num_objects = puzzle.num_movables
+        self.fewest_tools = bool(fewest_tools)
+        if budget is not None and int(budget) <= 0:
+            raise ValueError("budget must be a positive number of frames (or None for the default)")
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib.pw_rgd_create(self._engine.handle, int(getattr(puzzle, "puzzle_index", 0)),
+                                            1 if self.fewest_tools else 0, 0 if budget is None else int(budget),
+                                            ctypes.byref(h)))
+        self.handle = h
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def evaluate(self, states: torch.Tensor) -> torch.Tensor:
+        """``states`` int32 [F, N] Position2D (x * 10000 + y) on the puzzle's device, e.g. ``expand4``'s successors
+        reshaped to [F * 4, N]; returns float32 [F] costs, computed on the current stream."""
+        if not isinstance(states, torch.Tensor) or states.dtype != torch.int32 or states.dim() != 2 or \
+                states.shape[1] != self.num_objects or not states.is_contiguous() or states.device != self.device:
+            raise ValueError("states must be a contiguous int32 tensor [F, num_movables] on the puzzle's device")
+        out = torch.empty((states.shape[0],), dtype=torch.float32, device=self.device)
+        if states.shape[0]:
+            _capi.check(_capi.lib.pw_rgd_eval(self.handle, _capi._ptr(states), _capi._ptr(out), states.shape[0],
+                                              self._stream()))
+        return out
+
+    def movement_graph(self, obj: int):
+        """``{(x, y): {(x, y), ...}}``: the feasible-movement graph of movable ``obj`` (host computed)."""
+        return self.puzzle.movement_graph(obj)
+
+    def distance(self, obj: int, src, dst):
+        """Graph distance of movable ``obj`` (``PathDistances::getDistance``).  ``src`` / ``dst`` are (x, y) pairs (a float
+        comes back) or int32 tensors [K] of Position2D on the device (a float32 tensor [K] comes back)."""
+        if not 0 <= int(obj) < self.num_objects:
+            raise ValueError("obj must be a movable index of the puzzle")
+        scalar = not isinstance(src, torch.Tensor)
+        if scalar:
+            src = torch.tensor([int(src[0]) * POSITION_LIMIT + int(src[1])], dtype=torch.int32, device=self.device)
+            dst = torch.tensor([int(dst[0]) * POSITION_LIMIT + int(dst[1])], dtype=torch.int32, device=self.device)
+        for t in (src, dst):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("src and dst must be contiguous int32 tensors [K] on the puzzle's device")
+        if src.shape != dst.shape:
+            raise ValueError("src and dst must have the same shape")
+        out = torch.empty(src.shape, dtype=torch.float32, device=self.device)
+        if src.shape[0]:
+            _capi.check(_capi.lib.pw_rgd_distances(self.handle, int(obj), _capi._ptr(src), _capi._ptr(dst), _capi._ptr(out),
+                                                   src.shape[0], self._stream()))
+        return float(out.item()) if scalar else out
+
+    @property
+    def exceeded(self) -> int:
+        """States that ran out of budget since this object was created (synchronises the current stream)."""
+        return _capi.check(_capi.lib.pw_rgd_exceeded(self.handle, self._stream()))
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and _capi.lib is not None:
+            _capi.lib.pw_rgd_destroy(h)
+            self.handle = None
+
+    __del__ = close
+
+
 VERDICT_UNSOLVABLE, VERDICT_SOLVED, VERDICT_UNKNOWN, VERDICT_NOT_SEARCHED = 0, 1, 2, 3
 
 

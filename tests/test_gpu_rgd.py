@@ -1,0 +1,238 @@
+"""RGD heuristic on the device (pw_rgd_*): distance tables and batched evaluation against the literals of the reference's
+C++ tests and the plain-Python restatement (tests/rgd_restatement.py), bit for bit including +inf."""
+import glob
+import math
+import os
+import random
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import pw_oracle
+from pushworld_amd.puzzle import PushWorldPuzzle
+from pushworld_amd.search import BreadthFirstSearch, RecursiveGraphDistance
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rgd_restatement as R  # noqa: E402
+from test_rgd_host import RGD_COSTS, TRIVIAL_DISTANCES, cpp_state  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LEVEL1 = sorted(glob.glob(os.path.join(ROOT, "pushworld_amd", "data", "puzzles", "level1", "*.pwp")))
+REF_CPP = os.path.join(ROOT, "tests", "puzzles", "ref_cpp")
+MAX_CALLS = 4000  # the restatement gives up past this many recursion frames (below the kernel's default budget, 4 096)
+
+
+def enc(state):
+    return [x * 10000 + y for x, y in state]
+
+
+def dev(states, h):
+    return torch.tensor([enc(s) for s in states], dtype=torch.int32, device=h.device)
+
+
+def solution_plan(level, name):
+    with open(os.path.join(ROOT, "pushworld_amd", "data", "solutions", level, name + ".yaml")) as f:
+        for line in f:
+            if line.startswith("plan:"):
+                return ["LRUD".index(c) for c in line.split(":", 1)[1].strip()]
+    raise ValueError(name)
+
+
+def same(a, b):
+    return (a == b) or (math.isnan(a) and math.isnan(b))
+
+
+def level1_states(path, oz, rng, n_walk=40):
+    """States along the shipped plan, random-walk states and a sample of breadth-first layers (all reachable)."""
+    name = os.path.splitext(os.path.basename(path))[0]
+    out = [oz.initial_state]
+    s = oz.initial_state
+    for a in solution_plan("level1", name):
+        s = oz.get_next_state(s, a)
+        out.append(s)
+    s = oz.initial_state
+    for _ in range(n_walk):
+        s = oz.get_next_state(s, rng.randrange(4))
+        out.append(s)
+    return out
+
+
+def compare(h_gpu, h_ref, states):
+    """(compared, skipped): every state the restatement finishes must match bit for bit."""
+    got = h_gpu.evaluate(dev(states, h_gpu)).cpu().numpy()
+    compared = skipped = 0
+    for s, g in zip(states, got):
+        try:
+            want = h_ref.estimate(s)
+        except R.GiveUp:
+            skipped += 1
+            continue
+        assert same(float(g), want), (s, float(g), want)
+        compared += 1
+    return compared, skipped
+
+
+def test_distances_equal_the_cpp_literals():
+    pz = PushWorldPuzzle(os.path.join(REF_CPP, "trivial.pwp"), order="cpp")
+    h = RecursiveGraphDistance(pz)
+    for obj, src, dst, want in TRIVIAL_DISTANCES:
+        assert h.distance(obj, src, dst) == want, (obj, src, dst)
+
+
+def test_distances_equal_the_restatement_on_every_level1_puzzle():
+    rng = random.Random(5)
+    total = 0
+    for path in LEVEL1:
+        text = open(path).read()
+        pz = PushWorldPuzzle(text=text)
+        oz = pw_oracle.OraclePuzzle(text)
+        graphs = R.movement_graphs(oz)
+        h = RecursiveGraphDistance(pz)
+        for obj in range(pz.num_movables):
+            nodes = sorted(graphs[obj])
+            dist = R.PathDistances(graphs[obj])
+            src = [rng.choice(nodes) for _ in range(64)]
+            dst = [rng.choice(nodes) for _ in range(60)] + [(1, 1), (0, 0), src[0], (pz.dimensions[0] - 1, 1)]
+            got = h.distance(obj, torch.tensor(enc(src), dtype=torch.int32, device=h.device),
+                             torch.tensor(enc(dst), dtype=torch.int32, device=h.device)).cpu().numpy()
+            for s, t, g in zip(src, dst, got):
+                assert float(g) == dist.get(s, t), (path, obj, s, t)
+            total += len(src)
+        h.close()
+    assert total >= 64 * 2 * len(LEVEL1)
+
+
+@pytest.mark.parametrize("name,actions,fewest,want", RGD_COSTS)
+def test_evaluate_returns_the_cpp_literals(name, actions, fewest, want):
+    pz = PushWorldPuzzle(os.path.join(REF_CPP, name + ".pwp"), order="cpp")
+    oz = pw_oracle.OraclePuzzle(open(os.path.join(REF_CPP, name + ".pwp")).read(), "cpp")
+    h = RecursiveGraphDistance(pz, fewest_tools=fewest)
+    s = cpp_state(oz, actions)
+    got = h.evaluate(dev([s, s], h)).cpu().numpy()
+    assert got.tolist() == [want, want]
+
+
+def test_fewest_tools_and_full_depth_match_the_restatement_on_level1():
+    rng = random.Random(11)
+    stats = {True: [0, 0], False: [0, 0]}
+    for path in LEVEL1:
+        text = open(path).read()
+        pz = PushWorldPuzzle(text=text)
+        oz = pw_oracle.OraclePuzzle(text)
+        states = level1_states(path, oz, rng)
+        bfs = BreadthFirstSearch(pz, max_states=1 << 14)
+        bfs.begin()
+        for _ in range(12):
+            if bfs.exhausted or bfs.total_states > 4000:
+                break
+            bfs.expand()
+        layer = [tuple((int(x), int(y)) for x, y in s) for s in bfs.states()]
+        states += rng.sample(layer, min(30, len(layer)))
+        bfs.close()
+        modes = (True, False) if pz.num_movables <= 6 else (True,)
+        for fewest in modes:
+            h = RecursiveGraphDistance(pz, fewest_tools=fewest)
+            c, s = compare(h, R.RecursiveGraphDistance(oz, fewest, MAX_CALLS), states)
+            assert h.exceeded == 0
+            stats[fewest][0] += c
+            stats[fewest][1] += s
+            h.close()
+    for fewest, (c, s) in stats.items():
+        assert c >= 0.95 * (c + s), (fewest, c, s)
+    assert stats[True][0] >= 4000 and stats[False][0] >= 1500, stats
+
+
+def test_expand4_successors_feed_evaluate():
+    path = os.path.join(ROOT, "pushworld_amd", "data", "puzzles", "level1", "Multiple Goals.pwp")
+    text = open(path).read()
+    pz, oz = PushWorldPuzzle(text=text), pw_oracle.OraclePuzzle(text)
+    rng = random.Random(3)
+    states = level1_states(path, oz, rng, n_walk=60)
+    succ, _, _ = pz.expand4(torch.tensor([enc(s) for s in states], dtype=torch.int32))
+    flat = succ.reshape(-1, pz.num_movables).contiguous()
+    h = RecursiveGraphDistance(pz)
+    got = h.evaluate(flat).cpu().numpy()
+    ref = R.RecursiveGraphDistance(oz)
+    for row, g in zip(flat.cpu().numpy(), got):
+        s = tuple((int(v) // 10000, int(v) % 10000) for v in row)
+        assert same(float(g), ref.estimate(s)), s
+
+
+def test_batch_shapes_streams_and_graph_capture():
+    path = LEVEL1[0]
+    text = open(path).read()
+    pz, oz = PushWorldPuzzle(text=text), pw_oracle.OraclePuzzle(text)
+    states = level1_states(path, oz, random.Random(2), n_walk=80)
+    h = RecursiveGraphDistance(pz)
+    ref = R.RecursiveGraphDistance(oz)
+    base = dev(states, h)
+    want = torch.tensor([ref.estimate(s) for s in states], dtype=torch.float32)
+    for F in (0, 1, 63, 65):
+        x = base[torch.arange(F, device=h.device) % base.shape[0]].contiguous()
+        got = h.evaluate(x).cpu()
+        assert got.shape == (F,)
+        assert torch.equal(got, want[torch.arange(F) % base.shape[0]])
+    big = base.repeat((1 << 20) // base.shape[0] + 1, 1)[: 1 << 20].contiguous()
+    got = h.evaluate(big).cpu()
+    assert torch.equal(got, want.repeat((1 << 20) // base.shape[0] + 1)[: 1 << 20])
+    side = torch.cuda.Stream(device=h.device)
+    side.wait_stream(torch.cuda.current_stream(h.device))
+    with torch.cuda.stream(side):
+        got = h.evaluate(base)
+    side.synchronize()
+    assert torch.equal(got.cpu(), want)
+    out = torch.empty((base.shape[0],), dtype=torch.float32, device=h.device)
+    g = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream(device=h.device)
+    s.wait_stream(torch.cuda.current_stream(h.device))
+    with torch.cuda.stream(s):
+        out.copy_(h.evaluate(base))  # warm-up outside the capture
+    torch.cuda.current_stream(h.device).wait_stream(s)
+    with torch.cuda.graph(g):
+        out.copy_(h.evaluate(base))
+    out.zero_()
+    g.replay()
+    torch.cuda.synchronize(h.device)
+    assert torch.equal(out.cpu(), want)
+    assert h.exceeded == 0
+
+
+def test_off_graph_states_budget_and_argument_checks():
+    pz = PushWorldPuzzle(os.path.join(REF_CPP, "transitive_pushing.pwp"), order="cpp")
+    oz = pw_oracle.OraclePuzzle(open(os.path.join(REF_CPP, "transitive_pushing.pwp")).read(), "cpp")
+    h = RecursiveGraphDistance(pz, fewest_tools=False)
+    s0 = oz.initial_state
+    graphs = R.movement_graphs(oz)
+    off = next((x, y) for y in range(pz.dimensions[1]) for x in range(pz.dimensions[0]) if (x, y) not in graphs[1])
+    bad = list(s0)
+    bad[1] = off
+    outside = list(s0)
+    outside[0] = (pz.dimensions[0] + 3, 1)
+    got = h.evaluate(dev([s0, tuple(bad), tuple(outside), s0], h)).cpu().numpy()
+    assert got[0] == 3 and got[3] == 3 and np.isnan(got[1]) and np.isnan(got[2])
+    assert h.exceeded == 0
+    # a budget of one frame: the initial state needs recursion (a tool), the solved-goal state needs none
+    ref = R.RecursiveGraphDistance(oz, fewest_tools=False)
+    ref.estimate(s0)
+    assert ref.calls > 1
+    tiny = RecursiveGraphDistance(pz, fewest_tools=False, budget=1)
+    goal_state = list(s0)
+    goal_state[1] = oz.goal_state[0]
+    got = tiny.evaluate(dev([s0, tuple(goal_state)], tiny)).cpu().numpy()
+    assert np.isnan(got[0]) and got[1] == 0
+    assert tiny.exceeded == 1
+    exact = RecursiveGraphDistance(pz, fewest_tools=False, budget=ref.calls)
+    assert exact.evaluate(dev([s0], exact)).cpu().numpy().tolist() == [3] and exact.exceeded == 0
+    x = dev([s0], h)
+    for wrong in (x.to(torch.int64), x[:, :1], x.cpu(), x.t().contiguous() if x.shape[1] > 1 else x.reshape(-1),
+                  x.reshape(-1)):
+        with pytest.raises(ValueError):
+            h.evaluate(wrong)
+    with pytest.raises(ValueError):
+        RecursiveGraphDistance(pz, budget=0)
+    with pytest.raises(ValueError):
+        h.distance(pz.num_movables, (1, 1), (1, 1))
