@@ -726,6 +726,52 @@ int pw_rgd_distances(PwRgd* r, int32_t obj, const int32_t* src, const int32_t* d
                      void* stream);
 int64_t pw_rgd_exceeded(PwRgd* r, void* stream);
 
+/* Best-first planner: the reference's run_planner (best_first_search.h:45-98 with a BucketPriorityQueue, run_planner.cc:37-61)
+ * generalised to pop `batch` = K states per round.  At K = 1 it is the reference algorithm.
+ *   mode     PW_PLAN_RGD: key = RGD cost (fewest tools); PW_PLAN_N_RGD: key = float(novelty * 1e6f) + cost (WeightedSumHeuristic).
+ *            Lowest key first, LIFO within a key (the newest state, the highest store index, pops first); +inf after every finite
+ *            key, NaN (an RGD budget overrun, counted in info[6]) last.  A finite cost at or above the bucket range (RGD: 2^22;
+ *            N+RGD: 10^6, where the key stops being a bijection of (novelty, cost)) ends pw_planner_run with PW_ELIMIT.
+ *   round    pop up to K states; expand each with the 4 actions of its action group; candidates in (pop rank, position in the
+ *            group) order; a candidate is new when its state is not stored and no earlier candidate holds it; new states are
+ *            stored in that order; the first new goal ends the search (solved), else every new state is scored (novelty
+ *            tables in that order, then RGD) and pushed in that order.  A round is not started when store size + 4 K >
+ *            max_states (status limit), nor when the queue is empty (exhausted).
+ *   flags    PW_PLAN_ACTIONS_REFERENCE: RandomActionIterator (1000 std::shuffle permutations, std::default_random_engine(42));
+ *            the state popped p-th (from 0) takes group (p + 1) mod 1000.  PW_PLAN_ACTIONS_FIXED: L, R, U, D for every parent.
+ *   memory   a PwSearch of max_states with 4 K candidates per pass (pw_search_create's formula: the store, about max_states *
+ *            (2N + 5) bytes, the closed set, 8 bytes per slot of a power of two >= 2 (max_states + 4 K), and K * (8 N + 52)
+ *            bytes of candidates), a PwRgd (<= 1 GiB), 16 bytes per state of queue entries and segments (+ 1 in N+RGD mode),
+ *            4 bytes per bucket (2^22 + 2, or 3 * 10^6 + 2 in N+RGD mode) + 1 bit per bucket of occupancy, K * (16 N + 97)
+ *            bytes of round scratch (+ 20 in N+RGD mode) + the rocPRIM radix sort's temporary storage for 4 K pairs and, in
+ *            N+RGD mode, a PwNovelty (4 N D + 2 N (N - 1) D^2 bytes, D = width * height).
+ * pw_planner_begin: from `start` (host Position2D [N]) or the initial state; a start state that is a goal is solved at once
+ *   (empty plan).  pw_planner_run: at most max_rounds rounds (<= 0: until the status is not running), enqueued without
+ *   synchronising; the status is read once per group of rounds (pw_planner_set_sync_rounds, 0 = 16), which changes nothing
+ *   in the result (after the search ends, the rest of a group costs one radix sort of 4 K keys per round, the other
+ *   kernels return at once).  info: [0] status, [1] rounds, [2] expanded (states popped), [3] visited (the start state and every new
+ *   state numbered before the goal), [4] open (states in the queue), [5] goal store index or -1, [6] RGD budget overruns,
+ *   [7] store size.  pw_planner_plan: the plan to the goal, like pw_search_plan.  pw_planner_max_key: the largest finite
+ *   key pushed so far.  pw_planner_action_groups: the 1000 reference action groups (host only; returns 1000). */
+#define PW_PLAN_RGD 0
+#define PW_PLAN_N_RGD 1
+#define PW_PLAN_ACTIONS_REFERENCE 0
+#define PW_PLAN_ACTIONS_FIXED 1
+#define PW_PLAN_RUNNING 0
+#define PW_PLAN_SOLVED 1
+#define PW_PLAN_EXHAUSTED 2
+#define PW_PLAN_LIMIT 3
+typedef struct PwPlanner PwPlanner;
+int pw_planner_create(PwEngine* e, int32_t puzzle, int32_t mode, int64_t max_states, int32_t batch, int32_t flags,
+                      int64_t rgd_budget, PwPlanner** out);
+void pw_planner_destroy(PwPlanner* p);
+int pw_planner_set_sync_rounds(PwPlanner* p, int32_t rounds);
+int pw_planner_begin(PwPlanner* p, const int32_t* start, void* stream);
+int pw_planner_run(PwPlanner* p, int64_t max_rounds, int64_t info[8], void* stream);
+int pw_planner_plan(PwPlanner* p, uint8_t* actions, int32_t cap, void* stream);
+int pw_planner_max_key(PwPlanner* p, float* out, void* stream);
+int pw_planner_action_groups(uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,14 @@ SIGNATURES = {
     "pw_rgd_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "pw_rgd_distances": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "pw_rgd_exceeded": (c_int64, [c_void_p, c_void_p]),
+    "pw_planner_create": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_int64, POINTER(c_void_p)]),
+    "pw_planner_destroy": (None, [c_void_p]),
+    "pw_planner_set_sync_rounds": (c_int, [c_void_p, c_int32]),
+    "pw_planner_begin": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "pw_planner_run": (c_int, [c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+    "pw_planner_plan": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_planner_max_key": (c_int, [c_void_p, POINTER(ctypes.c_float), c_void_p]),
+    "pw_planner_action_groups": (c_int, [c_void_p]),
 }
 
 # pw_engine_set_option keys (include/pushworld_amd.h)

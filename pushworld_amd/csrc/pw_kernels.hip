@@ -406,4 +406,5 @@ struct PageRec {
 #include "pw_mailbox.inc"
 #include "pw_search.inc"
 #include "pw_rgd.inc"
+#include "pw_planner.inc"
 #include "pw_generate.inc"

@@ -113,6 +113,8 @@ struct RgdEvalArgs {
   const uint2* offs;
   const uint16_t* off;
   unsigned long long* exceeded;
+  const unsigned long long* dcount;  // the count in device memory instead (the planner's new states), or NULL
+  const unsigned long long* halt;    // returns at once while *halt != 0, or NULL
   uint16_t goal[32];
 };
 
@@ -289,7 +291,8 @@ __global__ __launch_bounds__(64) void pw_rgd_eval_kernel(RgdEvalArgs a) {
   extern __shared__ uint4 rgd_lds[];
   const int lane = threadIdx.x;
   const int64_t s = static_cast<int64_t>(blockIdx.x) * PW_WAVE + lane;
-  if (s >= a.count) return;
+  if (a.halt && *a.halt) return;
+  if (s >= (a.dcount ? static_cast<int64_t>(*a.dcount) : static_cast<int64_t>(a.count))) return;
   uint4* stk = rgd_lds + lane;
   uint16_t* pos = reinterpret_cast<uint16_t*>(rgd_lds + a.levels * PW_WAVE) + lane;
   // every movable must stand on a node of its own graph; otherwise NaN, decided before any evaluation
@@ -491,12 +494,9 @@ int pw_rgd_create(PwEngine* e, int32_t puzzle, int32_t fewest_tools, int64_t bud
   return pw_current_exception();  // nothing C++ leaves the C ABI
 }
 
-int pw_rgd_eval(PwRgd* r, const int32_t* states, float* cost, int32_t count, void* stream) try {
-  if (!r) return pw_fail(PW_EINVAL, "null argument");
-  if (count < 0) return pw_fail(PW_EINVAL, "count must be >= 0");
-  if (count == 0) return PW_OK;
-  if (!states || !cost) return pw_fail(PW_EINVAL, "null device pointer");
-  PwDeviceGuard guard(r->device);
+}  // extern "C"
+
+static RgdEvalArgs rgd_eval_args(PwRgd* r, const int32_t* states, float* cost, int32_t count) {
   RgdEvalArgs a;
   a.states = states;
   a.cost = cost;
@@ -515,15 +515,31 @@ int pw_rgd_eval(PwRgd* r, const int32_t* states, float* cost, int32_t count, voi
   a.offs = r->d_offs;
   a.off = r->d_off;
   a.exceeded = r->d_exceeded;
+  a.dcount = nullptr;
+  a.halt = nullptr;
   std::memcpy(a.goal, r->goal, sizeof(a.goal));
-  // frames (16 B per level) + positions (2 B per movable), per lane
-  const size_t lds = static_cast<size_t>(PW_WAVE) * (16 * a.levels + 2 * r->N);
+  return a;
+}
+
+// frames (16 B per level) + positions (2 B per movable), per lane
+static size_t rgd_eval_lds(const PwRgd* r) { return static_cast<size_t>(PW_WAVE) * (16 * std::max(r->N - 2, 1) + 2 * r->N); }
+
+extern "C" int pw_rgd_eval(PwRgd* r, const int32_t* states, float* cost, int32_t count, void* stream) try {
+  if (!r) return pw_fail(PW_EINVAL, "null argument");
+  if (count < 0) return pw_fail(PW_EINVAL, "count must be >= 0");
+  if (count == 0) return PW_OK;
+  if (!states || !cost) return pw_fail(PW_EINVAL, "null device pointer");
+  PwDeviceGuard guard(r->device);
+  const RgdEvalArgs a = rgd_eval_args(r, states, cost, count);
+  const size_t lds = rgd_eval_lds(r);
   const unsigned blocks = static_cast<unsigned>((static_cast<int64_t>(count) + PW_WAVE - 1) / PW_WAVE);
   hipLaunchKernelGGL(pw_rgd_eval_kernel, dim3(blocks), dim3(PW_WAVE), lds, static_cast<hipStream_t>(stream), a);
   return check_launch("pw_rgd_eval");
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
 }
+
+extern "C" {
 
 int pw_rgd_distances(PwRgd* r, int32_t obj, const int32_t* src, const int32_t* dst, float* d, int32_t count,
                      void* stream) try {

@@ -315,6 +315,12 @@ struct SearchArgs {
   const uint64_t* ovl;      // overlap tables (PwOvlDir), or NULL
   const PwOvlDir* ovl_dir;
   const PwPushDir* push_dir;  // push tables (pw_search_expand_lane_kernel), or NULL
+  // best-first rounds (pw_planner.inc; all NULL for breadth-first search):
+  const int32_t* plist;            // [nparents] store index of the parent of each pop rank (-1: none), instead of first + rank
+  const uint8_t* pperm;            // [nparents] action group of each rank: action at position p = bits 2p..2p+1; candidate
+                                   // slot of action a = 4 rank + its position
+  const unsigned long long* halt;  // every kernel returns at once while *halt != 0
+  uint8_t* state_nov;              // [max_states] novelty of each published state
 };
 
 // position-dependent 32-bit hash of a state: per-movable mix, summed over the GS lanes of a group
@@ -366,10 +372,23 @@ __global__ __launch_bounds__(256) void pw_search_expand_kernel(SearchArgs a) {
   const int lj = threadIdx.x & (GS - 1);
   const int gbase = lane & ~(GS - 1);
   const unsigned long long gmask = ((1ull << (GS - 1) << 1) - 1ull) << gbase;
+  if (a.halt && *a.halt) return;
   const int g = blockIdx.x * kGroups + static_cast<int>(threadIdx.x) / GS;
   bool live = g < a.nparents;
   const int gg = live ? g : 0;
-  if (a.pruned && a.pruned[a.first + gg]) live = false;  // above the novelty width: closed, not expanded
+  int64_t pidx = a.first + gg;
+  if (a.plist) {  // best-first round: the popped parent of rank gg
+    const int32_t v = a.plist[gg];
+    live = live && v >= 0;
+    pidx = v >= 0 ? v : 0;
+  }
+  if (a.pruned && a.pruned[pidx]) live = false;  // above the novelty width: closed, not expanded
+  uint32_t slot_of = 0xE4u;  // 2-bit candidate slot of each action (identity: L R U D)
+  if (a.pperm) {
+    const uint32_t perm = a.pperm[gg];
+    slot_of = 0u;
+    for (int p = 0; p < 4; p++) slot_of |= static_cast<uint32_t>(p) << (2 * ((perm >> (2 * p)) & 3u));
+  }
 
   LanePuzzleT<const uint64_t*, kTab ? 2 : 0> p;
   const PwPuzzleHeader* h = a.hdrs + a.puzzle;
@@ -385,7 +404,7 @@ __global__ __launch_bounds__(256) void pw_search_expand_kernel(SearchArgs a) {
   p.N = h->N;
   p.G = h->G;
   const int N = p.N;
-  const uint16_t* srow = reinterpret_cast<const uint16_t*>(a.states + (a.first + gg) * a.nw);
+  const uint16_t* srow = reinterpret_cast<const uint16_t*>(a.states + pidx * a.nw);
   const uint64_t* smalls = reinterpret_cast<const uint64_t*>(a.blob + h->base + h->off_small);
   const int xy = (lj < N) ? static_cast<int>(srow[lj]) : 0;
   const uint32_t ot = (lj < N) ? reinterpret_cast<const uint32_t*>(h->objtab)[lj] : 0u;
@@ -412,7 +431,7 @@ __global__ __launch_bounds__(256) void pw_search_expand_kernel(SearchArgs a) {
   // action with again nothing but the agent moving, exactly its own parent as the successor -- a visited state by
   // construction.  That candidate is dropped here (like one that did not move): a quarter of the closed-set probes, the
   // search's dominant traffic, for most parents.
-  const uint32_t came = a.action[a.first + gg];
+  const uint32_t came = a.action[pidx];
 #pragma unroll 1
   for (int act = 0; act < 4; act++) {
     const int dx = act == 0 ? -1 : (act == 1 ? 1 : 0);
@@ -439,11 +458,11 @@ __global__ __launch_bounds__(256) void pw_search_expand_kernel(SearchArgs a) {
     for (int o = GS / 2; o > 0; o >>= 1) t += static_cast<uint32_t>(__shfl_xor(static_cast<int>(t), o, GS));
     t = search_final(t);
     const int hi = __shfl_down(nxy, 1, PW_WAVE);
-    const int64_t c = static_cast<int64_t>(g) * 4 + act;
+    const int64_t c = static_cast<int64_t>(g) * 4 + ((slot_of >> (2 * act)) & 3u);
     if (g < a.nparents && lj == 0) {
       a.cand_hash[c] = moved ? (t & a.mask) : PW_S_NONE;
       a.cand_goal[c] = static_cast<uint8_t>(((moved && after == p.G) ? 1 : 0) | (pushed == 1u ? 2 : 0));  // bit 1: the agent alone
-      if (a.pruned) a.cand_moved[c] = moved ? pushed : 0u;
+      if (a.cand_moved) a.cand_moved[c] = moved ? pushed : 0u;
     }
     if (moved && !(lj & 1) && lj < 2 * a.nw)
       a.cand_state[c * a.nw + (lj >> 1)] = static_cast<uint32_t>(nxy) | (static_cast<uint32_t>(hi) << 16);
@@ -591,6 +610,7 @@ __global__ __launch_bounds__(64) void pw_search_expand_lane_kernel(SearchArgs a,
 // published one smaller than any of them: atomicMin lets the first discovery in (parent, action) order own the state.
 template <bool kKey>
 __global__ __launch_bounds__(256) void pw_search_claim_kernel(SearchArgs a, int n) {
+  if (a.halt && *a.halt) return;
   const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   // Rediscoveries inside the workgroup first (its 256 candidates are the successors of 64 consecutive parents -- siblings and
   // cousins, which is where most states found twice in a pass are found): the lowest candidate id per hash in a small LDS table;
@@ -697,6 +717,7 @@ __device__ __forceinline__ bool search_owner(const SearchArgs& a, int64_t c) {
 // ---- novelty of the owners (width-limited search): 32 lanes per candidate, ids in candidate order ------
 template <bool kMark>
 __global__ __launch_bounds__(256) void pw_search_novelty_kernel(SearchArgs a) {
+  if (a.halt && *a.halt) return;
   const int lane = threadIdx.x & (PW_WAVE - 1);
   const int lj = threadIdx.x & 31;
   const int gbase = lane & ~31;
@@ -724,11 +745,12 @@ __global__ __launch_bounds__(64) void pw_search_root_novelty_kernel(SearchArgs a
   }
   const uint32_t all = a.nt.N >= 32 ? 0xFFFFFFFFu : ((1u << a.nt.N) - 1u);
   novelty_group<true>(a.nt, lj, 0, 0xFFFFFFFFull, active, pj, all, 0u);
-  if (threadIdx.x == 0) a.pruned[0] = 0;
+  if (threadIdx.x == 0 && a.pruned) a.pruned[0] = 0;
 }
 
 // ---- count: owners per block of 256 candidates -------------------------------------------------------
 __global__ __launch_bounds__(256) void pw_search_count_kernel(SearchArgs a) {
+  if (a.halt && *a.halt) return;
   __shared__ uint32_t wsum[4];
   const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   const unsigned long long m = __ballot(search_owner(a, c));
@@ -742,6 +764,7 @@ __global__ __launch_bounds__(256) void pw_search_count_kernel(SearchArgs a) {
 
 // ---- scan: block counts -> first store index of each block (single workgroup) ----------------------
 __global__ __launch_bounds__(1024) void pw_search_scan_kernel(SearchArgs a, int32_t nblocks) {
+  if (a.halt && *a.halt) return;
   __shared__ uint32_t part[1024];
   const int tid = threadIdx.x;
   const int per = (nblocks + 1023) / 1024;
@@ -776,6 +799,7 @@ __global__ __launch_bounds__(1024) void pw_search_scan_kernel(SearchArgs a, int3
 
 // ---- publish: owners -> store, table entry becomes permanent ----------------------------------------
 __global__ __launch_bounds__(256) void pw_search_publish_kernel(SearchArgs a, int n) {
+  if (a.halt && *a.halt) return;
   __shared__ uint32_t wsum[4];
   const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -791,13 +815,15 @@ __global__ __launch_bounds__(256) void pw_search_publish_kernel(SearchArgs a, in
   const uint32_t* src = a.cand_state + c * a.nw;
   uint32_t* dst = a.states + idx * a.nw;
   for (int k = 0; k < a.nw; k++) dst[k] = src[k];
-  a.parent[idx] = static_cast<int32_t>(a.first + (c >> 2));
+  a.parent[idx] = a.plist ? a.plist[c >> 2] : static_cast<int32_t>(a.first + (c >> 2));
   const uint32_t cg = a.cand_goal[c];
-  a.action[idx] = static_cast<uint8_t>((c & 3) | ((cg & 2u) << 1));  // bit 2: reached by the agent moving alone
+  const uint32_t act = a.pperm ? (static_cast<uint32_t>(a.pperm[c >> 2]) >> (2 * (c & 3))) & 3u : static_cast<uint32_t>(c & 3);
+  a.action[idx] = static_cast<uint8_t>(act | ((cg & 2u) << 1));  // bit 2: reached by the agent moving alone
   // the entry becomes (fingerprint, index + 1) -- the low word; the fingerprint stays -- or, with exact keys, the state itself
   if (a.key_bx == 0) reinterpret_cast<uint32_t*>(a.table + a.cand_slot[c])[0] = static_cast<uint32_t>(idx) + 1u;
   else a.table[a.cand_slot[c]] = search_key(src, n, a.key_bx, a.key_by);
   if (a.pruned) a.pruned[idx] = a.cand_nov[c] > a.width ? 1 : 0;
+  if (a.state_nov) a.state_nov[idx] = a.cand_nov[c];
   if (cg & 1u) atomicMin(&a.info[1], static_cast<unsigned long long>(idx));
 }
 
@@ -843,7 +869,11 @@ void pw_search_destroy(PwSearch* s) {
   delete s;
 }
 
-int pw_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_t novelty_width, PwSearch** out) try {
+}  // extern "C"
+
+// chunk > 0: parents per pass (the planner: its batch K); 0: PW_OPT_SEARCH_CHUNK or 2^20
+static int search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_t novelty_width, int64_t chunk_parents,
+                         PwSearch** out) {
   if (!e || !out) return pw_fail(PW_EINVAL, "null argument");
   if (novelty_width < 0 || novelty_width > 2) return pw_fail(PW_EINVAL, "novelty_width must be 0 (off), 1 or 2");
   if (puzzle < 0 || puzzle >= e->set->count) return pw_fail(PW_EINVAL, "puzzle index out of range");
@@ -861,7 +891,8 @@ int pw_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_t no
   s->max_states = max_states;
   s->width = novelty_width;
   const int64_t chunk = e->search_chunk > 0 ? e->search_chunk : (1 << 20);  // PW_OPT_SEARCH_CHUNK (tests: many passes per layer)
-  s->chunk = static_cast<int32_t>(std::min<int64_t>(chunk, std::max<int64_t>(max_states, 1)));
+  s->chunk = chunk_parents > 0 ? static_cast<int32_t>(chunk_parents)
+                               : static_cast<int32_t>(std::min<int64_t>(chunk, std::max<int64_t>(max_states, 1)));
   uint64_t slots = 1024;
   while (slots < 2ull * (static_cast<uint64_t>(max_states) + 4ull * s->chunk)) slots <<= 1;
   if (slots > (1ull << 31)) {
@@ -917,6 +948,10 @@ int pw_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_t no
   }
   *out = s;
   return PW_OK;
+}
+
+extern "C" int pw_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_t novelty_width, PwSearch** out) try {
+  return search_create(e, puzzle, max_states, novelty_width, 0, out);
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
 }
@@ -960,8 +995,64 @@ static SearchArgs search_args(PwSearch* s) {
   a.id_base = 0;
   if (s->nov) a.nt = s->nov->t;
   else std::memset(&a.nt, 0, sizeof(a.nt));
+  a.plist = nullptr;
+  a.pperm = nullptr;
+  a.halt = nullptr;
+  a.state_nov = nullptr;
   return a;
 }
+
+// One pass over a.nparents parents: expand, claim, (novelty), count, scan, publish.  lane_ok false keeps the lane-group
+// expand kernels (the planner's parent lists and action groups are theirs only).
+static void search_pass(PwSearch* s, SearchArgs& a, hipStream_t st, bool lane_ok) {
+  const unsigned cblocks = static_cast<unsigned>((a.ncand + 255) / 256);
+  const bool tab = !s->eng->ovl_has.empty() && s->eng->ovl_has[static_cast<size_t>(s->puzzle)];  // overlap tables
+  // One lane per parent (pw_search_expand_lane_kernel) for passes that fill the chip by themselves: puzzles with push
+  // tables; PW_OPT_STEP_KERNEL lane forces it, PW_OPT_STEP_LANE_BATCH moves the threshold.
+  const bool push_tab = !s->eng->push_has.empty() && s->eng->push_has[static_cast<size_t>(s->puzzle)];
+  const int64_t lane_from = s->eng->step_lane_batch == 0 ? kSearchLaneParents : s->eng->step_lane_batch;
+  if (lane_ok && push_tab && s->N <= 32 && (s->eng->step_kernel == 2 || (s->eng->step_kernel == 0 && a.nparents >= lane_from))) {
+    uint32_t hash_pad = 0;  // the hash sums one term per slot of the lane-group kernels (8 or 16), empty ones included
+    for (int j = s->N; j < s->gs; j++) hash_pad += search_lane_term(0u, static_cast<uint32_t>(j));
+    const int nw = s->NW;
+    // runs of per_pass * nw words, 16-byte stores when that is a multiple of 4 (nw: 1 .. 8)
+    const int per_pass = nw % 4 == 0 ? 1 : (nw % 2 == 0 ? 2 : 4);
+    const int width = 4;
+    const int np_lane = s->N <= 4 ? 4 : (s->N <= 8 ? 8 : (s->N <= 16 ? 16 : 32));  // positions in LDS: NP / 2 + 1 words per state
+    const size_t lds = static_cast<size_t>(64) * (per_pass * nw + 2 + np_lane / 2 + 1) * sizeof(int);
+    const dim3 grid(static_cast<unsigned>((a.nparents + 63) / 64)), wave(64);
+    if (s->N <= 4) hipLaunchKernelGGL(pw_search_expand_lane_kernel<4>, grid, wave, lds, st, a, hash_pad, per_pass, width);
+    else if (s->N <= 8) hipLaunchKernelGGL(pw_search_expand_lane_kernel<8>, grid, wave, lds, st, a, hash_pad, per_pass, width);
+    else if (s->N <= 16) hipLaunchKernelGGL(pw_search_expand_lane_kernel<16>, grid, wave, lds, st, a, hash_pad, per_pass, width);
+    else hipLaunchKernelGGL(pw_search_expand_lane_kernel<32>, grid, wave, lds, st, a, hash_pad, per_pass, width);
+  } else if (s->gs == 8) {
+    if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<8, true>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pw_search_expand_kernel<8, false>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
+  } else if (s->gs == 16 && !s->eng->step_wide_groups) {  // 9 .. 16 movables: 8-lane groups, two movables per lane
+    if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<8, true, true>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pw_search_expand_kernel<8, false, true>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
+  } else if (s->gs == 16) {
+    if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<16, true>), dim3((a.nparents + 15) / 16), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pw_search_expand_kernel<16, false>), dim3((a.nparents + 15) / 16), dim3(256), 0, st, a);
+  } else {
+    if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<32, true>), dim3((a.nparents + 7) / 8), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pw_search_expand_kernel<32, false>), dim3((a.nparents + 7) / 8), dim3(256), 0, st, a);
+  }
+  if (a.key_bx) hipLaunchKernelGGL(pw_search_claim_kernel<true>, dim3(cblocks), dim3(256), 0, st, a, s->N);
+  else hipLaunchKernelGGL(pw_search_claim_kernel<false>, dim3(cblocks), dim3(256), 0, st, a, s->N);
+  if (s->nov) {  // width-limited search, or the planner's N+RGD mode
+    a.id_base = s->nov->next_id;
+    s->nov->next_id += static_cast<uint32_t>(a.ncand);
+    const unsigned nblocks = static_cast<unsigned>((a.ncand + 7) / 8);
+    hipLaunchKernelGGL(pw_search_novelty_kernel<true>, dim3(nblocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pw_search_novelty_kernel<false>, dim3(nblocks), dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(pw_search_count_kernel, dim3(cblocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(pw_search_scan_kernel, dim3(1), dim3(1024), 0, st, a, static_cast<int32_t>(cblocks));
+  hipLaunchKernelGGL(pw_search_publish_kernel, dim3(cblocks), dim3(256), 0, st, a, s->N);
+}
+
+extern "C" {
 
 int pw_search_begin(PwSearch* s, const int32_t* start, void* stream) try {
   if (!s) return pw_fail(PW_EINVAL, "null search");
@@ -1052,51 +1143,7 @@ int pw_search_expand(PwSearch* s, int64_t info_out[4], void* stream) try {
     a.nparents = static_cast<int32_t>(std::min<int64_t>(s->chunk, nlayer - off));
     a.ncand = 4 * a.nparents;
     a.epoch = ++s->epoch;  // (2^32 passes: a search of 2^30 states in passes of one parent each would not get there)
-    const unsigned cblocks = static_cast<unsigned>((a.ncand + 255) / 256);
-    const bool tab = !s->eng->ovl_has.empty() && s->eng->ovl_has[static_cast<size_t>(s->puzzle)];  // overlap tables
-    // One lane per parent (pw_search_expand_lane_kernel) for passes that fill the chip by themselves: puzzles with push
-    // tables; PW_OPT_STEP_KERNEL lane forces it, PW_OPT_STEP_LANE_BATCH moves the threshold.
-    const bool push_tab = !s->eng->push_has.empty() && s->eng->push_has[static_cast<size_t>(s->puzzle)];
-    const int64_t lane_from = s->eng->step_lane_batch == 0 ? kSearchLaneParents : s->eng->step_lane_batch;
-    if (push_tab && s->N <= 32 && (s->eng->step_kernel == 2 || (s->eng->step_kernel == 0 && a.nparents >= lane_from))) {
-      uint32_t hash_pad = 0;  // the hash sums one term per slot of the lane-group kernels (8 or 16), empty ones included
-      for (int j = s->N; j < s->gs; j++) hash_pad += search_lane_term(0u, static_cast<uint32_t>(j));
-      const int nw = s->NW;
-      // runs of per_pass * nw words, 16-byte stores when that is a multiple of 4 (nw: 1 .. 8)
-      const int per_pass = nw % 4 == 0 ? 1 : (nw % 2 == 0 ? 2 : 4);
-      const int width = 4;
-      const int np_lane = s->N <= 4 ? 4 : (s->N <= 8 ? 8 : (s->N <= 16 ? 16 : 32));  // positions in LDS: NP / 2 + 1 words per state
-      const size_t lds = static_cast<size_t>(64) * (per_pass * nw + 2 + np_lane / 2 + 1) * sizeof(int);
-      const dim3 grid(static_cast<unsigned>((a.nparents + 63) / 64)), wave(64);
-      if (s->N <= 4) hipLaunchKernelGGL(pw_search_expand_lane_kernel<4>, grid, wave, lds, st, a, hash_pad, per_pass, width);
-      else if (s->N <= 8) hipLaunchKernelGGL(pw_search_expand_lane_kernel<8>, grid, wave, lds, st, a, hash_pad, per_pass, width);
-      else if (s->N <= 16) hipLaunchKernelGGL(pw_search_expand_lane_kernel<16>, grid, wave, lds, st, a, hash_pad, per_pass, width);
-      else hipLaunchKernelGGL(pw_search_expand_lane_kernel<32>, grid, wave, lds, st, a, hash_pad, per_pass, width);
-    } else if (s->gs == 8) {
-      if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<8, true>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((pw_search_expand_kernel<8, false>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
-    } else if (s->gs == 16 && !s->eng->step_wide_groups) {  // 9 .. 16 movables: 8-lane groups, two movables per lane
-      if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<8, true, true>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((pw_search_expand_kernel<8, false, true>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
-    } else if (s->gs == 16) {
-      if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<16, true>), dim3((a.nparents + 15) / 16), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((pw_search_expand_kernel<16, false>), dim3((a.nparents + 15) / 16), dim3(256), 0, st, a);
-    } else {
-      if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<32, true>), dim3((a.nparents + 7) / 8), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((pw_search_expand_kernel<32, false>), dim3((a.nparents + 7) / 8), dim3(256), 0, st, a);
-    }
-    if (a.key_bx) hipLaunchKernelGGL(pw_search_claim_kernel<true>, dim3(cblocks), dim3(256), 0, st, a, s->N);
-    else hipLaunchKernelGGL(pw_search_claim_kernel<false>, dim3(cblocks), dim3(256), 0, st, a, s->N);
-    if (s->width > 0) {
-      a.id_base = s->nov->next_id;
-      s->nov->next_id += static_cast<uint32_t>(a.ncand);
-      const unsigned nblocks = static_cast<unsigned>((a.ncand + 7) / 8);
-      hipLaunchKernelGGL(pw_search_novelty_kernel<true>, dim3(nblocks), dim3(256), 0, st, a);
-      hipLaunchKernelGGL(pw_search_novelty_kernel<false>, dim3(nblocks), dim3(256), 0, st, a);
-    }
-    hipLaunchKernelGGL(pw_search_count_kernel, dim3(cblocks), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(pw_search_scan_kernel, dim3(1), dim3(1024), 0, st, a, static_cast<int32_t>(cblocks));
-    hipLaunchKernelGGL(pw_search_publish_kernel, dim3(cblocks), dim3(256), 0, st, a, s->N);
+    search_pass(s, a, st, true);
   }
   if (int rc = check_launch("pw_search_expand")) return rc;
   unsigned long long info[4] = {0, 0, 0, 0};

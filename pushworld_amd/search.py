@@ -335,3 +335,131 @@ def shortest_plan(puzzle, max_states: int = 1 << 20, plan_cap: int = 4096):
     eng = puzzle._engine()
     v, pl, ns, plans = search_batch(eng, [int(getattr(puzzle, "puzzle_index", 0))], max_states=max_states, plan_cap=plan_cap)
     return plans[0], int(v[0])
+
+
+PLAN_RUNNING, PLAN_SOLVED, PLAN_EXHAUSTED, PLAN_LIMIT = 0, 1, 2, 3
+PLAN_STATUS = {PLAN_RUNNING: "running", PLAN_SOLVED: "solved", PLAN_EXHAUSTED: "exhausted", PLAN_LIMIT: "limit"}
+PLAN_MODES = {"RGD": 0, "N+RGD": 1}
+PLAN_ACTION_ORDERS = {"reference": 0, "fixed": 1}
+
+
+class PlannerInfo(tuple):
+    """(status, rounds, expanded, visited, open, goal_index, rgd_exceeded, stored) of a ``BestFirstSearch``."""
+
+    status = property(lambda self: PLAN_STATUS[self[0]])
+    rounds = property(lambda self: self[1])
+    expanded = property(lambda self: self[2])
+    visited = property(lambda self: self[3])
+    open = property(lambda self: self[4])
+    goal_index = property(lambda self: self[5])
+    rgd_exceeded = property(lambda self: self[6])
+    stored = property(lambda self: self[7])
+
+
+def action_groups() -> List[Tuple[int, int, int, int]]:
+    """The reference's 1000 action groups (``RandomActionIterator``, std::shuffle with std::default_random_engine(42))."""
+    buf = (ctypes.c_uint8 * 4000)()
+    _capi.check(_capi.lib.pw_planner_action_groups(buf))
+    return [tuple(buf[4 * g: 4 * g + 4]) for g in range(1000)]
+
+
+class BestFirstSearch:
+    """The reference planner (``run_planner``: best-first search over a bucket queue, best_first_search.h:45-98) on the
+    GPU, popping ``batch`` = K states per round (K = 1 is the reference algorithm).  See ``pw_planner_create`` in
+    include/pushworld_amd.h for the exact semantics.
+
+    Args:
+        puzzle: a ``PushWorldPuzzle`` (parse with ``order="cpp"`` for the reference binary's object order).
+        heuristic: ``"RGD"`` or ``"N+RGD"`` (novelty first, then RGD).
+        batch: states popped per round.
+        max_states: capacity of the state store; a round is not started when it could overflow (status ``limit``).
+        action_order: ``"reference"`` (RandomActionIterator groups) or ``"fixed"`` (L, R, U, D).
+        rgd_budget: RGD recursion frames per state (None: the default); states beyond it get NaN keys and pop last.
+    """
+
+    def __init__(self, puzzle: PushWorldPuzzle, heuristic: str = "N+RGD", batch: int = 1, max_states: int = 1 << 22,
+                 action_order: str = "reference", rgd_budget: Optional[int] = None):
+        if heuristic not in PLAN_MODES:
+            raise ValueError("heuristic must be 'RGD' or 'N+RGD'")
+        if action_order not in PLAN_ACTION_ORDERS:
+            raise ValueError("action_order must be 'reference' or 'fixed'")
+        self.puzzle = puzzle
+        self._engine = puzzle._engine()
+        self.device = self._engine.device
+        self.num_objects = puzzle.num_movables
+        self.heuristic, self.batch, self.max_states, self.action_order = heuristic, int(batch), int(max_states), action_order
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib.pw_planner_create(self._engine.handle, int(getattr(puzzle, "puzzle_index", 0)),
+                                                PLAN_MODES[heuristic], self.max_states, self.batch,
+                                                PLAN_ACTION_ORDERS[action_order], 0 if rgd_budget is None else int(rgd_budget),
+                                                ctypes.byref(h)))
+        self.handle = h
+        self.info: Optional[PlannerInfo] = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def set_sync_rounds(self, rounds: int) -> None:
+        """Rounds enqueued per status read (0: the default); the result does not depend on it."""
+        _capi.check(_capi.lib.pw_planner_set_sync_rounds(self.handle, int(rounds)))
+
+    def begin(self, start: Optional[Sequence[Tuple[int, int]]] = None) -> None:
+        """Starts a search from ``start`` (a reference-style state, default: the initial state)."""
+        arr = None
+        if start is not None:
+            if len(start) != self.num_objects:
+                raise ValueError("start must hold one (x, y) pair per movable")
+            arr = (ctypes.c_int32 * self.num_objects)(*[int(x) * POSITION_LIMIT + int(y) for x, y in start])
+        _capi.check(_capi.lib.pw_planner_begin(self.handle, arr, self._stream()))
+        self.info = None
+
+    def run(self, max_rounds: Optional[int] = None) -> PlannerInfo:
+        """Runs at most ``max_rounds`` rounds (None: until the search is solved, exhausted or at its limit)."""
+        info = (ctypes.c_int64 * 8)()
+        rounds = 0 if max_rounds is None else int(max_rounds)
+        if max_rounds is not None and rounds <= 0:
+            raise ValueError("max_rounds must be positive (or None)")
+        _capi.check(_capi.lib.pw_planner_run(self.handle, rounds, info, self._stream()))
+        self.info = PlannerInfo(int(v) for v in info)
+        return self.info
+
+    def max_key(self) -> float:
+        """The largest finite key pushed since ``begin``."""
+        v = ctypes.c_float()
+        _capi.check(_capi.lib.pw_planner_max_key(self.handle, ctypes.byref(v), self._stream()))
+        return float(v.value)
+
+    def plan(self) -> Optional[List[int]]:
+        """The plan (list of actions 0..3) when the search is solved, else None."""
+        if self.info is None or self.info.status != "solved":
+            return None
+        cap = 4096
+        while True:
+            buf = (ctypes.c_uint8 * cap)()
+            n = _capi.check(_capi.lib.pw_planner_plan(self.handle, buf, cap, self._stream()))
+            if n <= cap:
+                return list(buf[:n])
+            cap = n
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and _capi.lib is not None:
+            _capi.lib.pw_planner_destroy(h)
+            self.handle = None
+
+    __del__ = close
+
+
+def solve(puzzle: PushWorldPuzzle, mode: str = "N+RGD", batch: int = 1, max_states: int = 1 << 24,
+          action_order: str = "reference") -> Optional[List[int]]:
+    """``run_planner``'s ``solve()``: the plan found by best-first search with ``mode`` ("RGD" or "N+RGD"), or None when
+    there is none.  Raises ``RuntimeError`` when ``max_states`` runs out first."""
+    bfs = BestFirstSearch(puzzle, heuristic=mode, batch=batch, max_states=max_states, action_order=action_order)
+    try:
+        bfs.begin()
+        info = bfs.run()
+        if info.status == "limit":
+            raise RuntimeError(f"best-first search stopped at max_states = {max_states} without an answer")
+        return bfs.plan()
+    finally:
+        bfs.close()
