@@ -45,6 +45,11 @@ same clock (tools/config_suite.py): C1, C2, C3 float32 ppc 3 / ppc 20, C4 state-
 with its dominant kernel's launch time, roofline fraction, PMC traffic record and its own CPU baseline.  Non-headline
 extras (``--no-extras`` drops them): ``incremental_render`` (the persistent observation buffer maintained by
 pw_step_render_delta) and ``state_only_rollout`` (64 steps per launch).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed windows, ``--dump-outputs`` and the line, whose
+``roofline`` comes from the launches of the timed windows themselves.  Everything else above is measured only with ``--full``
+(off by default), after the headline and as described: the rocm-smi clocks under ``device``, ``scaling_efficiency``, the
+extras, ``cpu_baseline`` and ``configs``.
 """
 import argparse
 import json
@@ -52,6 +57,7 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -118,9 +124,9 @@ def git_head():
         return None
 
 
-def device_report(device_index):
-    """Name and clocks of the GPU the line was measured on (rocm-smi, best effort): what the render kernel reaches
-    differs from box to box, so the line says which box state it saw."""
+def device_report(device_index, clocks):
+    """Name and, with ``clocks``, clocks of the GPU the line was measured on (rocm-smi, best effort): what the render kernel
+    reaches differs from box to box, so the line says which box state it saw."""
     rep = {}
     try:
         props = torch.cuda.get_device_properties(device_index)
@@ -129,6 +135,8 @@ def device_report(device_index):
         rep["compute_units"] = props.multi_processor_count
     except Exception:  # noqa: BLE001
         pass
+    if not clocks:
+        return rep
     try:
         txt = subprocess.run(["rocm-smi", "-d", str(device_index), "--showclocks", "--showpower", "--showperflevel", "--json"],
                              capture_output=True, text=True, timeout=20).stdout
@@ -251,6 +259,9 @@ def main():
     ap.add_argument("--obs", choices=["uint8", "float32", "none"], default=None,
                     help="default: uint8 for c3, none (state only) for c4")
     ap.add_argument("--max-steps", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry: rocm-smi clocks, scaling efficiency, "
+                         "the extras, the CPU baselines and the other configurations (the --no-* options drop parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=2.0,
                     help="CPU work of ONE all-threads C-port sample (three are taken, the best is the value; the other CPU "
@@ -448,7 +459,7 @@ def main():
         except OSError:
             pass
 
-    device_info = device_report(device_index)  # right after the timed windows: the clocks the GPU was left at
+    device_info = device_report(device_index, clocks=args.full)  # right after the timed windows: the clocks the GPU was left at
     n_obj = eng.np
     state_bytes = 2 * n_obj * 2 + 1 + 4 + 4 * 2 + 8 + 1 + 1 + 1  # pos r/w, action, pid, steps r/w, reward, flags
     out = {
@@ -601,39 +612,41 @@ def main():
         }
         out["config"]["algorithmic_bytes_per_env_step"] = state_bytes
 
-    # Scaling efficiency against the N = 1 run of the same workload ON THIS HOST WITH THIS KERNEL SOURCE: value / (N x the
-    # N = 1 value).  An N = 1 run leaves its value in gpurun_out/bench_n1_latest.json (untracked scratch; the driver runs
-    # N = 1, 2, 4, 8 back to back from one directory); a record of other kernels, another host or another day is refused,
-    # not labelled.
-    from tools.config_suite import csrc_sha
-    sig = {"config": args.config, "obs": args.obs, "envs_per_gpu": B, "ppc": args.ppc, "bw": args.bw, "max_steps": args.max_steps,
-           "csrc_sha16": csrc_sha()}
-    n1_path = os.path.join(ROOT, "gpurun_out", "bench_n1_latest.json")
-    if world == 1 and not args.shared_device:
-        try:
-            os.makedirs(os.path.dirname(n1_path), exist_ok=True)
-            with open(n1_path, "w") as f:
-                json.dump({"signature": sig, "value": out["value"], "ms_per_step": out["ms_per_step"], "unix_time": time.time(),
-                           "host": socket.gethostname(), "git_head": git_head()}, f, indent=1)
-        except OSError:
-            pass
-    else:
-        try:
-            with open(n1_path) as f:
-                rec = json.load(f)
-            fresh = rec.get("host") == socket.gethostname() and time.time() - rec.get("unix_time", 0) < 6 * 3600
-            if rec.get("signature") == sig and rec.get("value", 0) > 0 and fresh:
-                out["scaling_efficiency"] = {
-                    "value": out["value"] / (world * rec["value"]), "n1_value": rec["value"],
-                    "n1_source": "gpurun_out/bench_n1_latest.json: N = 1 run on this host %d s ago, same kernel source" % (time.time() - rec["unix_time"]),
-                    "sum_of_per_rank_rates_over_n_x_n1": out["timing"]["sum_of_per_rank_median_rates"] / (world * rec["value"]),
-                }
-            else:
-                out["scaling_efficiency"] = {"value": None, "why": "the N = 1 record is stale (other kernel source, workload, host, or older than 6 h): refused"}
-        except (OSError, ValueError):
-            out["scaling_efficiency"] = {"value": None, "why": "no N = 1 run of this workload on this host yet (run bench.py --gpus 1 first)"}
+    if args.full:
+        # Scaling efficiency against the N = 1 run of the same workload ON THIS HOST WITH THIS KERNEL SOURCE: value / (N x the
+        # N = 1 value).  An N = 1 run leaves its value in a per-user file of the system's temporary directory, where the N > 1
+        # runs of the same host find it; a record of other kernels, another host or another day is refused, not labelled.
+        from tools.config_suite import csrc_sha
+        sig = {"config": args.config, "obs": args.obs, "envs_per_gpu": B, "ppc": args.ppc, "bw": args.bw,
+               "max_steps": args.max_steps, "csrc_sha16": csrc_sha()}
+        n1_path = os.path.join(tempfile.gettempdir(), f"pushworld_bench_n1_latest_{os.getuid()}.json")
+        if world == 1 and not args.shared_device:
+            try:
+                with open(n1_path, "w") as f:
+                    json.dump({"signature": sig, "value": out["value"], "ms_per_step": out["ms_per_step"],
+                               "unix_time": time.time(), "host": socket.gethostname(), "git_head": git_head()}, f, indent=1)
+            except OSError:
+                pass
+        else:
+            try:
+                with open(n1_path) as f:
+                    rec = json.load(f)
+                fresh = rec.get("host") == socket.gethostname() and time.time() - rec.get("unix_time", 0) < 6 * 3600
+                if rec.get("signature") == sig and rec.get("value", 0) > 0 and fresh:
+                    out["scaling_efficiency"] = {
+                        "value": out["value"] / (world * rec["value"]), "n1_value": rec["value"],
+                        "n1_source": "bench.py --full at N = 1 on this host %d s ago, same kernel source"
+                                     % (time.time() - rec["unix_time"]),
+                        "sum_of_per_rank_rates_over_n_x_n1": out["timing"]["sum_of_per_rank_median_rates"] / (world * rec["value"]),
+                    }
+                else:
+                    out["scaling_efficiency"] = {"value": None, "why": "the N = 1 record is stale (other kernel source, workload, "
+                                                                       "host, or older than 6 h): refused"}
+            except (OSError, ValueError):
+                out["scaling_efficiency"] = {"value": None, "why": "no N = 1 run of this workload on this host yet "
+                                                                   "(run bench.py --gpus 1 --full first)"}
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # extra (not the headline): the same loop with the observation buffer maintained incrementally
         # (pw_step_render_delta: same bytes in HBM after every step, only the changed pixel rows written)
         if obs_mode is not None:
@@ -672,7 +685,7 @@ def main():
                                           "steps_per_launch": Tn, "envs": B, "n_gpus": 1}
         except Exception as exc:  # noqa: BLE001
             out["state_only_rollout"] = {"error": repr(exc)}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # rank 0's host cores, N = 1 only (the contract: the CPU figure belongs to the single-GPU line)
         fh, fw = eng.obs_shape[0] // args.ppc, eng.obs_shape[1] // args.ppc
         torch.cuda.synchronize()
@@ -687,7 +700,7 @@ def main():
             out["cpu_baseline"] = {"error": repr(exc)}
     # every other BASELINE.json configuration on the same clock (N = 1, default line only): C1, C2, C3 float32 ppc 3 / ppc 20,
     # C4 state-only + uint8, C5 on three puzzles -- each with its kernel's roofline fraction and its own CPU baseline
-    if world == 1 and args.config == "c3" and not args.no_configs and not args.shared_device:
+    if args.full and world == 1 and args.config == "c3" and not args.no_configs and not args.shared_device:
         del vec, eng
         wl.clear()
         torch.cuda.empty_cache()

@@ -60,7 +60,7 @@ def test_self_spawned_two_ranks_sum_their_counters():
 
     shared = [] if torch.cuda.device_count() >= 2 else ["--shared-device"]
     # an N = 1 run of the same workload first: it leaves the reference value of `scaling_efficiency`
-    proc1, lines1 = run_bench(*SMALL, "--cpu-seconds", "0.5")
+    proc1, lines1 = run_bench("--full", *SMALL, "--cpu-seconds", "0.5")
     assert proc1.returncode == 0 and len(lines1) == 1, proc1.stderr[-2000:]
     assert "scaling_efficiency" not in lines1[0] and len(lines1[0]["roofline"]["per_rank_frac"]) == 1
     cb = lines1[0]["cpu_baseline"]
@@ -68,7 +68,7 @@ def test_self_spawned_two_ranks_sum_their_counters():
     assert cb["python_env"]["value"] > 0 and cb["python_env"]["processes"]["cores"] >= 1
     assert proc1.compact_lines[0]["cpu_baseline"]["one_thread_value"] == pytest.approx(cb["one_thread"]["value"], rel=1e-3)
     assert proc1.compact_lines[0]["config"]["ranks_in_probe_all_reduce"] is None
-    proc, lines = run_bench("--gpus", "2", *shared, *SMALL, "--cpu-seconds", "1")
+    proc, lines = run_bench("--gpus", "2", "--full", *shared, *SMALL, "--cpu-seconds", "1")
     assert proc.returncode == 0, proc.stderr[-2000:]
     assert len(lines) == 1, proc.stdout[-2000:]
     d = lines[0]
@@ -131,7 +131,7 @@ def test_ranks_sharing_the_device_report_one_row_each():
     Three ranks: with this process and bench.py's launcher that is five processes holding the device, within what a
     shared GPU host allows at once (eight ranks would be ten)."""
     n = 3
-    proc, lines = run_bench("--gpus", str(n), "--shared-device", "--steps", "2", "--warmup", "1", "--windows", "2",
+    proc, lines = run_bench("--gpus", str(n), "--full", "--shared-device", "--steps", "2", "--warmup", "1", "--windows", "2",
                             "--envs-per-gpu", "1024", "--no-extras", "--no-configs", "--no-cpu-baseline", timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
     assert len(lines) == 1
@@ -216,10 +216,24 @@ def test_single_rank_line_has_the_contract_fields():
     assert d["config"]["workload"].startswith("C3") and d["roofline"]["kernel"].startswith("pw_render")
 
 
+def test_plain_run_measures_the_headline_alone():
+    """Without ``--full`` the run is the headline and nothing else: no CPU baseline, extras, other configurations, scaling
+    efficiency or rocm-smi clocks, whatever --no-* options are left out; the roofline of the timed launches stays."""
+    proc, lines = run_bench("--steps", "3", "--warmup", "1", "--envs-per-gpu", "2048")
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    assert len(lines) == 1
+    d = lines[0]
+    for key in ("cpu_baseline", "configs", "incremental_render", "state_only_rollout", "scaling_efficiency"):
+        assert key not in d, key
+    assert "rocm_smi" not in d["device"] and d["device"]["name"]
+    assert d["roofline"]["launches_timed"] == 3 and d["counters"]["env_steps"] == 2048 * 3
+
+
 def test_extras_of_the_line_run():
-    """The non-headline extras of the line (incremental render, state-only rollouts) run and report numbers, not errors."""
-    proc, lines = run_bench("--steps", "3", "--warmup", "1", "--windows", "2", "--envs-per-gpu", "2048", "--no-cpu-baseline",
-                            "--no-configs")
+    """The non-headline extras of the line (incremental render, state-only rollouts) run with ``--full`` and report numbers,
+    not errors."""
+    proc, lines = run_bench("--full", "--steps", "3", "--warmup", "1", "--windows", "2", "--envs-per-gpu", "2048",
+                            "--no-cpu-baseline", "--no-configs")
     assert proc.returncode == 0, proc.stderr[-2000:]
     d = lines[0]
     for key in ("incremental_render", "state_only_rollout"):
@@ -229,8 +243,8 @@ def test_extras_of_the_line_run():
 def test_configs_object_of_the_line():
     """``configs``: the other BASELINE.json configurations on the same clock (here C1, C2 and C5 on `2 Obstacle`; the driver's
     run has all of them): value, kernel, launch time from the library's HIP events, roofline fraction, traffic field."""
-    proc, lines = run_bench("--steps", "3", "--warmup", "1", "--windows", "2", "--envs-per-gpu", "2048", "--no-cpu-baseline",
-                            "--no-extras", "--configs-only", "C1,C2,C5_2", timeout=900)
+    proc, lines = run_bench("--full", "--steps", "3", "--warmup", "1", "--windows", "2", "--envs-per-gpu", "2048",
+                            "--no-cpu-baseline", "--no-extras", "--configs-only", "C1,C2,C5_2", timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
     cfg = lines[0]["configs"]
     assert set(cfg) == {"C1", "C2", "C5_2_obstacle", "C3_u8_ppc3"}, set(cfg)

@@ -112,9 +112,9 @@ for name in ("pmc_kernels_latest.json", "pmc_render_latest.json"):
     except Exception:
         pass
 PY
-$T python bench.py --steps 20 --warmup 5 > $P/bench.json 2> $P/bench.err
+$T python bench.py --full --steps 20 --warmup 5 > $P/bench.json 2> $P/bench.err
 cp gpurun_out/bench_full.json $P/bench_full.json 2>/dev/null
-$T rocprofv3 --kernel-trace --stats -d $P -o trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $P/trace_bench_line.json 2> $P/trace.log
+$T rocprofv3 --kernel-trace --stats -d $P -o trace -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $P/trace_bench_line.json 2> $P/trace.log
 summ $P/trace_results.db > $P/trace_summary.txt
 rm -f $P/*.db
 tail -1 $P/bench.json | cut -c1-400

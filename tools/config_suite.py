@@ -33,7 +33,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0
-# CPU baselines of the non-headline configurations: short bounded samples (the whole default bench.py run has to fit a minute;
+# CPU baselines of the non-headline configurations: short bounded samples (the whole bench.py --full run has to fit a minute;
 # the headline's own cpu_baseline takes three samples of --cpu-seconds each)
 CPU_SECONDS, CPU_SAMPLES = 0.6, 2
 CSRC = os.path.join(ROOT, "pushworld_amd", "csrc")
