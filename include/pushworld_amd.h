@@ -772,6 +772,38 @@ int pw_planner_plan(PwPlanner* p, uint8_t* actions, int32_t cap, void* stream);
 int pw_planner_max_key(PwPlanner* p, float* out, void* stream);
 int pw_planner_action_groups(uint8_t* out);
 
+/* Batched best-first search (K9): the planner runs of MANY puzzles in ONE launch.  Persistent workgroups of one wavefront take
+ * the items off a device counter and run each one's whole search inside the kernel.  Item i's info[0..7] and plan equal
+ * pw_planner_create(e, puzzles[i], mode, max_states, batch, flags, rgd_budget) + begin(initial state) + run(max_rounds),
+ * as long as no finite cost reaches cost_range.
+ *   puzzles     host int32 [n] set indices of the items, or NULL (0 .. n - 1); an index may repeat
+ *   batch       K, 1 .. 64
+ *   max_states  1 .. 2^28 states per item (every workgroup owns a slab of that many)
+ *   cost_range  0 (65536) or 1 .. 65536: finite RGD costs 0 .. cost_range - 1 have a bucket; a larger one ends the item with
+ *               PW_PLAN_RANGE (pw_planner's ranges are 2^22 and 10^6)
+ *   memory      per workgroup: max_states * (4 ceil(N / 2) + 9) bytes + 8 bytes per slot of the closed set (a power of two
+ *               >= 2 max_states) + 4 bytes per bucket + in N+RGD mode 1 bit per novelty atom (N D + N (N - 1) / 2 D^2,
+ *               D = width * height; N, D of the largest item); one workgroup per item, at most 2 per CU, fewer when their
+ *               slabs would take more than a quarter of the free device memory.  Plus one PwRgd per item.
+ * pw_plan_batch_run: one asynchronous launch on `stream`.  info: device int64 [n][PW_PLAN_BATCH_INFO] (pw_planner_run's
+ *   eight values, then [8] the item's search time on the device in nanoseconds); plans: device uint8 [n][plan_cap] or NULL,
+ *   plan_len: device int32 [n] (length of the plan, -1 without one; a plan longer than plan_cap is cut), or NULL.
+ *   max_rounds <= 0: no round limit.  time_limit: seconds per item (0 = none), read on the device's constant clock before
+ *   every round; an item past it ends with PW_PLAN_TIMEOUT.
+ * pw_plan_batch_cancel: every launch of this handle made so far stops soon: running items after at most 32 more rounds, with
+ *   status PW_PLAN_RUNNING and the counts they reached; items not started yet report PW_PLAN_RUNNING with 0 rounds.  The
+ *   cancel word lives in pinned host memory: no stream is involved. */
+#define PW_PLAN_TIMEOUT 4
+#define PW_PLAN_RANGE 5
+#define PW_PLAN_BATCH_INFO 9
+typedef struct PwPlanBatch PwPlanBatch;
+int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t mode, int64_t max_states, int32_t batch,
+                         int32_t flags, int64_t rgd_budget, int32_t cost_range, PwPlanBatch** out);
+int pw_plan_batch_run(PwPlanBatch* b, int64_t max_rounds, double time_limit, int64_t* info, uint8_t* plans, int32_t* plan_len,
+                      int32_t plan_cap, void* stream);
+int pw_plan_batch_cancel(PwPlanBatch* b);
+void pw_plan_batch_destroy(PwPlanBatch* b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,11 @@ SIGNATURES = {
     "pw_planner_plan": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "pw_planner_max_key": (c_int, [c_void_p, POINTER(ctypes.c_float), c_void_p]),
     "pw_planner_action_groups": (c_int, [c_void_p]),
+    "pw_plan_batch_create": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32,
+                                     POINTER(c_void_p)]),
+    "pw_plan_batch_run": (c_int, [c_void_p, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_plan_batch_cancel": (c_int, [c_void_p]),
+    "pw_plan_batch_destroy": (None, [c_void_p]),
 }
 
 # pw_engine_set_option keys (include/pushworld_amd.h)

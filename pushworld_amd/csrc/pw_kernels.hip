@@ -407,4 +407,5 @@ struct PageRec {
 #include "pw_search.inc"
 #include "pw_rgd.inc"
 #include "pw_planner.inc"
+#include "pw_plan_batch.inc"
 #include "pw_generate.inc"

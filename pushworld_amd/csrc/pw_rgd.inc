@@ -287,6 +287,31 @@ __device__ uint32_t rgd_goal_cost(const RgdEvalArgs& a, const uint16_t* pos, uin
   return best;
 }
 
+// estimate_cost_to_goal (:43-66) of the state whose positions (x | y << 8, every one a node of its graph) are at pos[j * 64];
+// NaN with `over` set when the budget runs out.  Goal k belongs to movable k + 1; the sum stops at the first infinite goal.
+__device__ __forceinline__ float rgd_eval_pos(const RgdEvalArgs& a, const uint16_t* pos, uint4* stk, bool& over) {
+  int64_t frames = 0;
+  uint32_t total = 0;
+  bool dead = false;
+  for (int g = 0; g < a.G && !dead && !over; g++) {
+    const int gx = a.goal[g] & 0xff, gy = a.goal[g] >> 8;
+    uint32_t gc;
+    if (a.fewest) {  // get_fewest_tools_goal_cost (:100-112): the first pushing depth with a finite cost
+      gc = RGD_INF;
+      for (int d = 0; d < a.N - 1 && !over; d++) {
+        gc = rgd_goal_cost(a, pos, stk, g + 1, gx, gy, d, frames, over);
+        if (gc < RGD_INF) break;
+      }
+    } else {
+      gc = rgd_goal_cost(a, pos, stk, g + 1, gx, gy, a.N - 2, frames, over);
+    }
+    if (gc >= RGD_INF) dead = true;
+    else total += gc;
+  }
+  if (over) return __builtin_nanf("");
+  return dead ? __builtin_inff() : static_cast<float>(total);
+}
+
 __global__ __launch_bounds__(64) void pw_rgd_eval_kernel(RgdEvalArgs a) {
   extern __shared__ uint4 rgd_lds[];
   const int lane = threadIdx.x;
@@ -308,32 +333,10 @@ __global__ __launch_bounds__(64) void pw_rgd_eval_kernel(RgdEvalArgs a) {
     a.cost[s] = __builtin_nanf("");
     return;
   }
-  int64_t frames = 0;
   bool over = false;
-  uint32_t total = 0;
-  bool dead = false;
-  // estimate_cost_to_goal (:43-66): goal k belongs to movable k + 1; the sum stops at the first infinite goal
-  for (int g = 0; g < a.G && !dead && !over; g++) {
-    const int gx = a.goal[g] & 0xff, gy = a.goal[g] >> 8;
-    uint32_t gc;
-    if (a.fewest) {  // get_fewest_tools_goal_cost (:100-112): the first pushing depth with a finite cost
-      gc = RGD_INF;
-      for (int d = 0; d < a.N - 1 && !over; d++) {
-        gc = rgd_goal_cost(a, pos, stk, g + 1, gx, gy, d, frames, over);
-        if (gc < RGD_INF) break;
-      }
-    } else {
-      gc = rgd_goal_cost(a, pos, stk, g + 1, gx, gy, a.N - 2, frames, over);
-    }
-    if (gc >= RGD_INF) dead = true;
-    else total += gc;
-  }
-  if (over) {
-    atomicAdd(a.exceeded, 1ull);
-    a.cost[s] = __builtin_nanf("");
-    return;
-  }
-  a.cost[s] = dead ? __builtin_inff() : static_cast<float>(total);
+  const float c = rgd_eval_pos(a, pos, stk, over);
+  if (over) atomicAdd(a.exceeded, 1ull);
+  a.cost[s] = c;
 }
 
 struct RgdDistArgs {

@@ -463,3 +463,114 @@ def solve(puzzle: PushWorldPuzzle, mode: str = "N+RGD", batch: int = 1, max_stat
         return bfs.plan()
     finally:
         bfs.close()
+
+
+PLAN_TIMEOUT, PLAN_RANGE = 4, 5
+PLAN_STATUS.update({PLAN_TIMEOUT: "timeout", PLAN_RANGE: "range"})
+PLAN_BATCH_INFO = 9  # PW_PLAN_BATCH_INFO: the eight PlannerInfo values, then the search time on the device in nanoseconds
+
+
+class PlanBatch:
+    """Best-first search (``BestFirstSearch``'s semantics) of MANY puzzles in ONE launch (``pw_plan_batch_*``): persistent
+    workgroups of one wavefront run each puzzle's whole search inside the kernel.  Item i's ``PlannerInfo`` and plan equal
+    ``BestFirstSearch(puzzles[i], heuristic, batch, max_states, action_order, rgd_budget)`` + ``begin()`` + ``run(max_rounds)``
+    as long as no finite RGD cost reaches ``cost_range``; two statuses are new: ``timeout`` (past ``time_limit``) and
+    ``range`` (a cost at or above ``cost_range``).
+
+    Args:
+        puzzles: ``PushWorldPuzzle`` objects (each in its own object order), all on one device.
+        batch: K, states popped per round (1 .. 64).
+        max_states: states per puzzle; every workgroup owns a slab of that many (see ``pw_plan_batch_create``).
+        cost_range: finite costs with a bucket (None: 65536).
+    """
+
+    def __init__(self, puzzles: Sequence[PushWorldPuzzle], heuristic: str = "N+RGD", batch: int = 1,
+                 max_states: int = 1 << 20, action_order: str = "reference", rgd_budget: Optional[int] = None,
+                 cost_range: Optional[int] = None):
+        if heuristic not in PLAN_MODES:
+            raise ValueError("heuristic must be 'RGD' or 'N+RGD'")
+        if action_order not in PLAN_ACTION_ORDERS:
+            raise ValueError("action_order must be 'reference' or 'fixed'")
+        self.puzzles = list(puzzles)
+        if not self.puzzles:
+            raise ValueError("puzzles must not be empty")
+        from .puzzle import default_device_index
+
+        dev = default_device_index()
+        self._pset = _capi.PuzzleSet([p._parsed for p in self.puzzles], dev)
+        self._engine = _capi.Engine(self._pset, None, 3, 1, _capi.OBS_U8)
+        self.device = self._engine.device
+        self.n = len(self.puzzles)
+        self.heuristic, self.batch, self.max_states, self.action_order = heuristic, int(batch), int(max_states), action_order
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib.pw_plan_batch_create(self._engine.handle, None, self.n, PLAN_MODES[heuristic], self.max_states,
+                                                   self.batch, PLAN_ACTION_ORDERS[action_order],
+                                                   0 if rgd_budget is None else int(rgd_budget),
+                                                   0 if cost_range is None else int(cost_range), ctypes.byref(h)))
+        self.handle = h
+        self._out = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def run(self, max_rounds: Optional[int] = None, time_limit: Optional[float] = None, plan_cap: int = 4096) -> None:
+        """Starts the searches (one launch on the current stream; returns at once).  ``max_rounds`` per puzzle (None: no
+        limit), ``time_limit`` seconds per puzzle on the device's clock (None: none); ``results`` waits for them."""
+        if max_rounds is not None and int(max_rounds) <= 0:
+            raise ValueError("max_rounds must be positive (or None)")
+        if time_limit is not None and not float(time_limit) > 0:
+            raise ValueError("time_limit must be positive seconds (or None)")
+        if int(plan_cap) < 1:
+            raise ValueError("plan_cap must be >= 1")
+        info = torch.empty((self.n, PLAN_BATCH_INFO), dtype=torch.int64, device=self.device)
+        plans = torch.empty((self.n, int(plan_cap)), dtype=torch.uint8, device=self.device)
+        plan_len = torch.empty((self.n,), dtype=torch.int32, device=self.device)
+        _capi.check(_capi.lib.pw_plan_batch_run(self.handle, 0 if max_rounds is None else int(max_rounds),
+                                                0.0 if time_limit is None else float(time_limit), _capi._ptr(info),
+                                                _capi._ptr(plans), _capi._ptr(plan_len), int(plan_cap), self._stream()))
+        self._out = (info, plans, plan_len)
+
+    def cancel(self) -> None:
+        """Stops the searches of every ``run`` so far soon (their status stays ``running``)."""
+        _capi.check(_capi.lib.pw_plan_batch_cancel(self.handle))
+
+    def results(self) -> List[Tuple[Optional[List[int]], PlannerInfo, float]]:
+        """``(plan or None, PlannerInfo, device seconds)`` per puzzle of the last ``run`` (waits for it).  A plan longer than
+        ``plan_cap`` is None."""
+        if self._out is None:
+            raise RuntimeError("run() has not been called")
+        info, plans, plan_len = (t.cpu().numpy() for t in self._out)
+        out = []
+        for i in range(self.n):
+            pi = PlannerInfo(int(v) for v in info[i, :8])
+            n = int(plan_len[i])
+            plan = plans[i, :n].tolist() if pi.status == "solved" and 0 <= n <= plans.shape[1] else None
+            out.append((plan, pi, float(info[i, 8]) * 1e-9))
+        return out
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and _capi.lib is not None:
+            try:  # (a launch in flight still uses the slabs)
+                torch.cuda.current_stream(self.device).synchronize()
+            except Exception:
+                pass
+            _capi.lib.pw_plan_batch_destroy(h)
+            self.handle = None
+
+    __del__ = close
+
+
+def solve_many(puzzles: Sequence[PushWorldPuzzle], mode: str = "N+RGD", batch: int = 1, max_states: int = 1 << 20,
+               action_order: str = "reference", time_limit: Optional[float] = None, rgd_budget: Optional[int] = None,
+               cost_range: Optional[int] = None) -> List[Tuple[Optional[List[int]], PlannerInfo, float]]:
+    """``solve`` for many puzzles in one launch (``PlanBatch``): ``(plan or None, PlannerInfo, device seconds)`` per puzzle.
+    Unlike ``solve`` nothing is raised for a puzzle that ends at ``max_states``, ``time_limit`` or ``cost_range``: its
+    ``PlannerInfo.status`` says so."""
+    pb = PlanBatch(puzzles, heuristic=mode, batch=batch, max_states=max_states, action_order=action_order,
+                   rgd_budget=rgd_budget, cost_range=cost_range)
+    try:
+        pb.run(time_limit=time_limit)
+        return pb.results()
+    finally:
+        pb.close()
