@@ -795,12 +795,36 @@ int pw_planner_action_groups(uint8_t* out);
  *   cancel word lives in pinned host memory: no stream is involved. */
 #define PW_PLAN_TIMEOUT 4
 #define PW_PLAN_RANGE 5
+#define PW_PLAN_SKIPPED 6
 #define PW_PLAN_BATCH_INFO 9
 typedef struct PwPlanBatch PwPlanBatch;
 int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t mode, int64_t max_states, int32_t batch,
                          int32_t flags, int64_t rgd_budget, int32_t cost_range, PwPlanBatch** out);
 int pw_plan_batch_run(PwPlanBatch* b, int64_t max_rounds, double time_limit, int64_t* info, uint8_t* plans, int32_t* plan_len,
                       int32_t plan_cap, void* stream);
+/* pw_plan_batch_run_states: the same searches from given states -- e.g. the live states of a batch of environments.  Item i
+ * of the run is puzzle_id[i] from start state pos[i].  Item i's info[0..7] and plan equal pw_planner_create(e, puzzle_id[i],
+ * mode, max_states, batch, flags, rgd_budget) + pw_planner_begin(start = pos[i]) + pw_planner_run(max_rounds) with the
+ * handle's settings, as long as no finite cost reaches cost_range: the reference's best_first_search on the puzzle with its
+ * initial state replaced by pos[i].  All arrays live in device memory; nothing is read on the host, so the call is one
+ * asynchronous launch on `stream` that may follow a pw_step on the same stream without a synchronisation.
+ *   puzzle_id     int32 [n] set indices of the handle's engine (a VecPushWorld's puzzle_id as it is)
+ *   pos           int8 [n][npad][2], x then y per movable: the engine's state layout (pw_engine_npad); padding is not read
+ *   mask          uint8 [n] or NULL: 0 skips the item
+ *   first_action  int8 [n] or NULL: the plan's first action when the item is solved with a non-empty plan, -1 otherwise
+ *                 (a start at its goal is solved with an empty plan: -1)
+ *   info, plans, plan_len, plan_cap, max_rounds, time_limit: as for pw_plan_batch_run, with n rows
+ * An item is PW_PLAN_SKIPPED (info[0] = 6, info[1..8] = 0, plan_len -1, first_action -1) when it is masked out, its puzzle
+ * id is outside the set, the handle did not prepare that puzzle (pw_plan_batch_create's `puzzles`; the first item naming a
+ * puzzle lends it its tables) or a movable lies outside its grid (pw_validate_state's range test).  Walls and overlaps are
+ * not checked, as the reference does not check them.  Closed-set tags: a run uses n of them.
+ * The handle has at most one workgroup per prepared item; the first run with more items adds workgroups up to two per CU
+ * (within a quarter of the free memory), which waits for the device once.
+ * PW_EINVAL before any launch: n < 1, npad not 4 / 8 / 16 / 32, a null puzzle_id / pos / info, plans without plan_len,
+ * a null handle, npad below the largest prepared puzzle's number of movables. */
+int pw_plan_batch_run_states(PwPlanBatch* b, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask,
+                             int32_t n, int64_t max_rounds, double time_limit, int64_t* info, uint8_t* plans,
+                             int32_t* plan_len, int32_t plan_cap, int8_t* first_action, void* stream);
 int pw_plan_batch_cancel(PwPlanBatch* b);
 void pw_plan_batch_destroy(PwPlanBatch* b);
 

@@ -192,6 +192,8 @@ SIGNATURES = {
     "pw_plan_batch_create": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_int64, c_int32,
                                      POINTER(c_void_p)]),
     "pw_plan_batch_run": (c_int, [c_void_p, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_plan_batch_run_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, ctypes.c_double,
+                                         c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "pw_plan_batch_cancel": (c_int, [c_void_p]),
     "pw_plan_batch_destroy": (None, [c_void_p]),
 }

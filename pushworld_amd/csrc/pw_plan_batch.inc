@@ -32,6 +32,12 @@
 // NaN (nb - 1).  A finite cost at or above cost_range ends that puzzle with PW_PLAN_RANGE.
 // Between rounds: the wall clock against the per-puzzle time limit (PW_PLAN_TIMEOUT) and, every kPbCancelRounds rounds,
 // the cancel word in pinned host memory (the search stops as it stands: status running).
+//
+// States form (pw_plan_batch_run_states, state_pos != NULL): item i of the run is (state_pid[i], state_pos[i]) in the
+// engine's layout (int8 [n][npad][2], x then y: byte for byte the store's x | y << 8).  It searches with the tables of the
+// handle item slot_of[pid] prepared, from state_pos[i] in place of the puzzle's initial state.  An item that is masked out,
+// names a puzzle outside the set or one the handle did not prepare, or has a movable outside its grid (pw_validate_state's
+// range test) is PW_PLAN_SKIPPED: nothing of it is read past that test.
 // ====================================================================================================
 static constexpr int kPbMaxK = 64;             // states popped per round at most (4 K candidates in LDS)
 static constexpr uint32_t kPbCostRange = 65536u;  // default and largest cost_range
@@ -43,6 +49,11 @@ struct PbItem {
   int32_t pid;      // index in the engine's set
   int32_t nov_words;  // N+RGD: uint32 words of novelty bits
 };
+
+// the start of a states-form item: (x, y) of movable j as the store's x | y << 8 (bytes: any alignment of state_pos)
+__device__ __forceinline__ uint32_t pb_start_xy(const int8_t* row, int j) {
+  return static_cast<uint32_t>(static_cast<uint8_t>(row[2 * j])) | (static_cast<uint32_t>(static_cast<uint8_t>(row[2 * j + 1])) << 8);
+}
 
 struct PbArgs {
   const PwPuzzleHeader* hdrs;
@@ -70,6 +81,13 @@ struct PbArgs {
   int32_t* plan_len;      // [n] or NULL
   int32_t plan_cap;
   int32_t levels;         // RGD LDS frames per lane (the largest puzzle's)
+  // states form (pw_plan_batch_run_states); state_pos == NULL: item i is handle item i from its puzzle's initial state
+  const int32_t* state_pid;  // [n] set indices
+  const int8_t* state_pos;   // [n][npad][2] start states, or NULL
+  const uint8_t* mask;       // [n] or NULL: 0 = skip
+  const int32_t* slot_of;    // [set_count] handle item of each set index, -1 = not prepared
+  int32_t npad, set_count;
+  int8_t* first_action;      // [n] or NULL: plan[0], -1 without a non-empty plan
 };
 
 __device__ __forceinline__ uint32_t pb_hash(const uint32_t* w, int nw) {
@@ -154,7 +172,37 @@ __global__ __launch_bounds__(64) void pw_plan_batch_kernel(PbArgs a) {
     __syncthreads();
     const int item = s_item;
     if (item >= a.n) return;
-    const PbItem& it = a.items[item];
+    int slot = item;
+    const int8_t* srow = nullptr;  // states form: the item's start state
+    if (a.state_pos) {
+      const int32_t spid = a.state_pid[item];
+      bool skip = (a.mask && a.mask[item] == 0) || spid < 0 || spid >= a.set_count;
+      if (!skip) {
+        slot = a.slot_of[spid];
+        skip = slot < 0;
+      }
+      if (!skip) {  // every movable inside the grid (lanes over movables; nothing past N is read)
+        const PwPuzzleHeader* sh = a.hdrs + spid;
+        srow = a.state_pos + static_cast<int64_t>(item) * a.npad * 2;
+        bool bad = false;
+        if (lane < sh->N) {
+          const int x = srow[2 * lane], y = srow[2 * lane + 1];
+          bad = x < 0 || y < 0 || x + sh->objtab[lane].w > sh->W || y + sh->objtab[lane].h > sh->H;
+        }
+        skip = __ballot(bad) != 0ull;
+      }
+      if (skip) {
+        if (lane == 0) {
+          int64_t* sinfo = a.info + static_cast<int64_t>(item) * kPbInfo;
+          sinfo[0] = PW_PLAN_SKIPPED;
+          for (int k = 1; k < kPbInfo; k++) sinfo[k] = 0;
+          if (a.plan_len) a.plan_len[item] = -1;
+          if (a.first_action) a.first_action[item] = -1;
+        }
+        continue;
+      }
+    }
+    const PbItem& it = a.items[slot];
     const RgdEvalArgs& ra = it.rgd;
     const PwPuzzleHeader* h = a.hdrs + it.pid;
     const int N = h->N, G = h->G, W = h->W, D = h->W * h->H;
@@ -167,6 +215,7 @@ __global__ __launch_bounds__(64) void pw_plan_batch_kernel(PbArgs a) {
         for (int k = 1; k < kPbInfo; k++) info[k] = 0;
         info[5] = -1;
         if (a.plan_len) a.plan_len[item] = -1;
+        if (a.first_action) a.first_action[item] = -1;
       }
       continue;
     }
@@ -180,12 +229,12 @@ __global__ __launch_bounds__(64) void pw_plan_batch_kernel(PbArgs a) {
     const uint16_t* goal = reinterpret_cast<const uint16_t*>(h->goal);
     // (words and halves past this puzzle's movables are 0, in the store and in the candidates: a slab serves puzzles of
     //  every size, and the closed set compares all nw words)
+    auto start = [&](int j) -> uint32_t { return srow ? pb_start_xy(srow, j) : static_cast<uint32_t>(init[j]); };
     if (lane < nw)
-      store[lane] = (2 * lane < N ? static_cast<uint32_t>(init[2 * lane]) : 0u) |
-                    (2 * lane + 1 < N ? static_cast<uint32_t>(init[2 * lane + 1]) << 16 : 0u);
+      store[lane] = (2 * lane < N ? start(2 * lane) : 0u) | (2 * lane + 1 < N ? start(2 * lane + 1) << 16 : 0u);
     if (lane == 0) s_cand[0] = -1;  // the start state is scored like a round's new state, with every movable moved
     int at_goal = 0;
-    for (int g = 0; g < G; g++) at_goal += init[g + 1] == goal[g];
+    for (int g = 0; g < G; g++) at_goal += start(g + 1) == static_cast<uint32_t>(goal[g]);
     // info slots as pw_planner's: status, rounds, expanded, visited, open, goal, rgd overruns, store size
     unsigned long long status = at_goal == G ? PW_PLAN_SOLVED : PW_PLAN_RUNNING;
     unsigned long long rounds = 0, expanded = 0, visited = 1, open = 0, gidx = at_goal == G ? 0ull : ~0ull, exceeded = 0;
@@ -420,21 +469,22 @@ __global__ __launch_bounds__(64) void pw_plan_batch_kernel(PbArgs a) {
       info[6] = static_cast<int64_t>(exceeded);
       info[7] = static_cast<int64_t>(stored);
       info[8] = static_cast<int64_t>((wall_clock64() - t0) * 1000000ull / a.clock_khz);  // nanoseconds
-      if (a.plan_len) {
+      if (a.plan_len || a.first_action) {
         int32_t len = -1;
+        int first = -1;
         if (gidx != ~0ull) {
           len = 0;
           for (int64_t at = static_cast<int64_t>(gidx); at > 0 && len <= a.max_states; at = parent[at]) len++;
-          if (a.plans) {
-            uint8_t* out = a.plans + static_cast<int64_t>(item) * a.plan_cap;
-            int64_t at = static_cast<int64_t>(gidx);
-            for (int k = len - 1; k >= 0; k--) {
-              if (k < a.plan_cap) out[k] = action[at];
-              at = parent[at];
-            }
+          uint8_t* out = a.plans ? a.plans + static_cast<int64_t>(item) * a.plan_cap : nullptr;
+          int64_t at = static_cast<int64_t>(gidx);
+          for (int k = len - 1; k >= 0 && (out || a.first_action); k--) {
+            if (out && k < a.plan_cap) out[k] = action[at];
+            if (k == 0) first = action[at];
+            at = parent[at];
           }
         }
-        a.plan_len[item] = len;
+        if (a.plan_len) a.plan_len[item] = len;
+        if (a.first_action) a.first_action[item] = static_cast<int8_t>(first);
       }
     }
   }
@@ -448,6 +498,8 @@ struct PwPlanBatch {
   uint32_t cost_range;
   std::vector<PwRgd*> rgd;
   PbItem* d_items;
+  int32_t* d_slot_of;  // [set count] the first item of each set index, -1 = none (the states form)
+  int32_t max_n;       // the largest prepared puzzle's movables
   uint8_t* d_groups;
   uint8_t* d_slab;     // counter (256 B), then `groups` slabs
   int64_t groups;
@@ -464,6 +516,7 @@ extern "C" {
 void pw_plan_batch_destroy(PwPlanBatch* b) {
   if (!b) return;
   if (b->d_items) (void)hipFree(b->d_items);
+  if (b->d_slot_of) (void)hipFree(b->d_slot_of);
   if (b->d_groups) (void)hipFree(b->d_groups);
   if (b->d_slab) (void)hipFree(b->d_slab);
   if (b->h_cancel) (void)hipHostFree(b->h_cancel);
@@ -525,6 +578,9 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
     max_n = std::max<int>(max_n, h.N);
     levels = std::max(levels, std::max(h.N - 2, 1));
   }
+  b->max_n = max_n;
+  std::vector<int32_t> slot_of(static_cast<size_t>(e->set->count), -1);
+  for (int32_t i = n - 1; i >= 0; i--) slot_of[static_cast<size_t>(items[static_cast<size_t>(i)].pid)] = i;  // the first wins
   PbArgs& a = b->args;
   std::memset(static_cast<void*>(&a), 0, sizeof(a));
   a.hdrs = e->set->d_headers;
@@ -576,6 +632,7 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
     if (err == hipSuccess) err = hipMalloc(static_cast<void**>(ptr), bytes);
   };
   alloc(&b->d_items, sizeof(PbItem) * static_cast<size_t>(n));
+  alloc(&b->d_slot_of, sizeof(int32_t) * slot_of.size());
   alloc(&b->d_groups, kPlanGroups);
   alloc(&b->d_slab, 256 + static_cast<size_t>(b->groups) * static_cast<size_t>(a.slab_bytes));
   if (err == hipSuccess) err = hipHostMalloc(reinterpret_cast<void**>(&b->h_cancel), 64, hipHostMallocMapped);
@@ -584,6 +641,7 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
     err = hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_cancel), b->h_cancel, 0);
   }
   if (err == hipSuccess) err = hipMemcpy(b->d_items, items.data(), sizeof(PbItem) * static_cast<size_t>(n), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(b->d_slot_of, slot_of.data(), sizeof(int32_t) * slot_of.size(), hipMemcpyHostToDevice);
   if (err == hipSuccess) {
     uint8_t packed[kPlanGroups];
     uint8_t raw[4 * kPlanGroups];
@@ -603,6 +661,8 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
     return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
   }
   a.items = b->d_items;
+  a.slot_of = b->d_slot_of;
+  a.set_count = e->set->count;
   a.groups = flags == PW_PLAN_ACTIONS_FIXED ? nullptr : b->d_groups;
   a.slab = b->d_slab + 256;
   a.next_item = reinterpret_cast<uint32_t*>(b->d_slab);
@@ -615,21 +675,19 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
   return pw_current_exception();  // nothing C++ leaves the C ABI
 }
 
-int pw_plan_batch_run(PwPlanBatch* b, int64_t max_rounds, double time_limit, int64_t* info, uint8_t* plans, int32_t* plan_len,
-                      int32_t plan_cap, void* stream) try {
-  if (!b || !info) return pw_fail(PW_EINVAL, "null argument");
-  if (!(time_limit >= 0.0)) return pw_fail(PW_EINVAL, "time_limit must be >= 0 seconds (0 = none)");
-  if (plans && (!plan_len || plan_cap < 1)) return pw_fail(PW_EINVAL, "plans need plan_len and plan_cap >= 1");
-  PwDeviceGuard guard(b->eng->set->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  PbArgs a = b->args;
-  if (b->tags_used + static_cast<uint64_t>(b->n) >= 0xFFFFFFFFull) {  // tags would wrap: empty the slabs once more
+}  // extern "C"
+
+// the per-run fields of both forms and the launch: n items (tags tag_base .. tag_base + n - 1), at most one workgroup each
+static int pb_launch(PwPlanBatch* b, PbArgs& a, int32_t n, int64_t max_rounds, double time_limit, int64_t* info,
+                     uint8_t* plans, int32_t* plan_len, int32_t plan_cap, hipStream_t st, const char* what) {
+  if (b->tags_used + static_cast<uint64_t>(n) >= 0xFFFFFFFFull) {  // tags would wrap: empty the slabs once more
     if (hipMemsetAsync(a.slab, 0, static_cast<size_t>(b->groups) * static_cast<size_t>(a.slab_bytes), st) != hipSuccess)
-      return pw_fail(PW_EDEVICE, "pw_plan_batch_run: hipMemsetAsync failed");
+      return pw_fail(PW_EDEVICE, std::string(what) + ": hipMemsetAsync failed");
     b->tags_used = 0;
   }
+  a.n = n;
   a.tag_base = static_cast<uint32_t>(b->tags_used + 1u);
-  b->tags_used += static_cast<uint64_t>(b->n);
+  b->tags_used += static_cast<uint64_t>(n);
   a.max_rounds = max_rounds;
   const double ticks = time_limit * static_cast<double>(a.clock_khz) * 1000.0;
   a.time_ticks = time_limit > 0.0 ? (ticks >= 1.8e19 ? ~0ull : std::max<unsigned long long>(1ull, static_cast<unsigned long long>(ticks))) : 0ull;
@@ -638,9 +696,80 @@ int pw_plan_batch_run(PwPlanBatch* b, int64_t max_rounds, double time_limit, int
   a.plans = plans;
   a.plan_len = plan_len;
   a.plan_cap = plans ? plan_cap : 0;
-  if (hipMemsetAsync(a.next_item, 0, 4, st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_plan_batch_run: hipMemsetAsync failed");
-  hipLaunchKernelGGL(pw_plan_batch_kernel, dim3(static_cast<unsigned>(b->groups)), dim3(PW_WAVE), b->lds, st, a);
-  return check_launch("pw_plan_batch_run");
+  if (hipMemsetAsync(a.next_item, 0, 4, st) != hipSuccess) return pw_fail(PW_EDEVICE, std::string(what) + ": hipMemsetAsync failed");
+  const int64_t groups = std::min<int64_t>(b->groups, n);
+  hipLaunchKernelGGL(pw_plan_batch_kernel, dim3(static_cast<unsigned>(groups)), dim3(PW_WAVE), b->lds, st, a);
+  return check_launch(what);
+}
+
+// the states form's runs may hold more items than the handle prepared puzzles: up to two workgroups per CU as memory allows.
+// Replacing the slabs waits for the device once (a launch in flight on any stream still uses the old ones).
+static int pb_grow(PwPlanBatch* b, int32_t n) {
+  const int64_t want = std::min<int64_t>(n, 2ll * b->eng->num_cus);
+  if (want <= b->groups) return PW_OK;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return PW_OK;  // (keep what there is)
+  const uint64_t slab = b->args.slab_bytes;
+  const int64_t fit = static_cast<int64_t>((free_b + static_cast<uint64_t>(b->groups) * slab) / 4 / slab);
+  const int64_t groups = std::min<int64_t>(want, fit);
+  if (groups <= b->groups) return PW_OK;
+  uint8_t* fresh = nullptr;
+  const size_t bytes = 256 + static_cast<size_t>(groups) * static_cast<size_t>(slab);
+  if (hipMalloc(reinterpret_cast<void**>(&fresh), bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return PW_OK;  // (the launch runs on the workgroups it has)
+  }
+  hipError_t err = hipDeviceSynchronize();
+  if (err == hipSuccess) err = hipMemset(fresh, 0, bytes);  // tag 0 is no item's: the tables start empty
+  if (err == hipSuccess) err = hipFree(b->d_slab);
+  if (err != hipSuccess) {
+    (void)hipFree(fresh);
+    return pw_fail(PW_EDEVICE, std::string("pw_plan_batch_run_states: ") + hipGetErrorString(err));
+  }
+  b->d_slab = fresh;
+  b->groups = groups;
+  b->args.slab = fresh + 256;
+  b->args.next_item = reinterpret_cast<uint32_t*>(fresh);
+  b->tags_used = 0;
+  return PW_OK;
+}
+
+extern "C" {
+
+int pw_plan_batch_run(PwPlanBatch* b, int64_t max_rounds, double time_limit, int64_t* info, uint8_t* plans, int32_t* plan_len,
+                      int32_t plan_cap, void* stream) try {
+  if (!b || !info) return pw_fail(PW_EINVAL, "null argument");
+  if (!(time_limit >= 0.0)) return pw_fail(PW_EINVAL, "time_limit must be >= 0 seconds (0 = none)");
+  if (plans && (!plan_len || plan_cap < 1)) return pw_fail(PW_EINVAL, "plans need plan_len and plan_cap >= 1");
+  PwDeviceGuard guard(b->eng->set->device);
+  PbArgs a = b->args;
+  return pb_launch(b, a, b->n, max_rounds, time_limit, info, plans, plan_len, plan_cap, static_cast<hipStream_t>(stream),
+                   "pw_plan_batch_run");
+} catch (...) {
+  return pw_current_exception();  // nothing C++ leaves the C ABI
+}
+
+int pw_plan_batch_run_states(PwPlanBatch* b, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask,
+                             int32_t n, int64_t max_rounds, double time_limit, int64_t* info, uint8_t* plans,
+                             int32_t* plan_len, int32_t plan_cap, int8_t* first_action, void* stream) try {
+  // (every check but the last needs no handle)
+  if (n < 1) return pw_fail(PW_EINVAL, "n must be >= 1");
+  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, "npad must be 4, 8, 16 or 32");
+  if (!puzzle_id || !pos || !info) return pw_fail(PW_EINVAL, "null argument (puzzle_id, pos and info are required)");
+  if (!(time_limit >= 0.0)) return pw_fail(PW_EINVAL, "time_limit must be >= 0 seconds (0 = none)");
+  if (plans && (!plan_len || plan_cap < 1)) return pw_fail(PW_EINVAL, "plans need plan_len and plan_cap >= 1");
+  if (!b) return pw_fail(PW_EINVAL, "null handle");
+  if (npad < b->max_n) return pw_fail(PW_EINVAL, "npad is smaller than the largest prepared puzzle's number of movables");
+  PwDeviceGuard guard(b->eng->set->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = pb_grow(b, n)) return rc;
+  PbArgs a = b->args;
+  a.state_pid = puzzle_id;
+  a.state_pos = pos;
+  a.mask = mask;
+  a.npad = npad;
+  a.first_action = first_action;
+  return pb_launch(b, a, n, max_rounds, time_limit, info, plans, plan_len, plan_cap, st, "pw_plan_batch_run_states");
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
 }

@@ -574,3 +574,136 @@ def solve_many(puzzles: Sequence[PushWorldPuzzle], mode: str = "N+RGD", batch: i
         return pb.results()
     finally:
         pb.close()
+
+
+PLAN_SKIPPED = 6
+PLAN_STATUS[PLAN_SKIPPED] = "skipped"
+
+
+def _state_inputs(puzzle_id, pos, mask, npad: int, device) -> int:
+    """The checks of ``StatePlanner.plan`` on its device arrays; returns n."""
+    if not isinstance(puzzle_id, torch.Tensor) or puzzle_id.dtype != torch.int32 or puzzle_id.dim() != 1:
+        raise ValueError("puzzle_id must be an int32 tensor [n]")
+    n = int(puzzle_id.shape[0])
+    if n < 1 or n >= 1 << 31:
+        raise ValueError("puzzle_id must hold 1 .. 2^31 - 1 items")
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int8 or tuple(pos.shape) != (n, npad, 2):
+        raise ValueError(f"pos must be an int8 tensor [n, {npad}, 2] (the engine's state layout)")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool)
+                             or tuple(mask.shape) != (n,)):
+        raise ValueError("mask must be a uint8 or bool tensor [n] (or None)")
+    for name, t in (("puzzle_id", puzzle_id), ("pos", pos), ("mask", mask)):
+        if t is None:
+            continue
+        if t.device != device:
+            raise ValueError(f"{name} must live on {device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return n
+
+
+class StatePlanner:
+    """Best-first search (``BestFirstSearch``'s semantics) from given states of a puzzle set, MANY in ONE launch
+    (``pw_plan_batch_run_states``): typically the live states of a ``VecPushWorld``.  Item i's ``PlannerInfo`` and plan equal
+    ``BestFirstSearch(puzzle puzzle_id[i], heuristic, batch, max_states, action_order, rgd_budget)`` + ``begin(start=pos[i])``
+    + ``run(max_rounds)`` as long as no finite RGD cost reaches ``cost_range``.  Items that are masked out, name a puzzle
+    outside ``puzzles`` or hold a movable outside its grid are ``skipped``.
+
+    Args:
+        source: a ``VecPushWorld`` or an ``_capi.Engine``: the planner uses its puzzle set (object order, ``NP``).
+        puzzles: the set indices to prepare (None: every puzzle of the set).  Construction builds one RGD table set per
+            puzzle -- for a pool of 14 000 puzzles that is 14 000 builds and their device memory; list the ones you plan on.
+        batch: K, states popped per round (1 .. 64).
+        max_states: states per item; every workgroup owns a slab of that many (see ``pw_plan_batch_create``).
+        cost_range: finite costs with a bucket (None: 65536).
+    """
+
+    def __init__(self, source, puzzles: Optional[Sequence[int]] = None, heuristic: str = "N+RGD", batch: int = 1,
+                 max_states: int = 1 << 16, action_order: str = "reference", rgd_budget: Optional[int] = None,
+                 cost_range: Optional[int] = None):
+        if heuristic not in PLAN_MODES:
+            raise ValueError("heuristic must be 'RGD' or 'N+RGD'")
+        if action_order not in PLAN_ACTION_ORDERS:
+            raise ValueError("action_order must be 'reference' or 'fixed'")
+        engine = source if isinstance(source, _capi.Engine) else getattr(source, "engine", None)
+        if not isinstance(engine, _capi.Engine):
+            raise ValueError("source must be a VecPushWorld or an _capi.Engine")
+        self.engine = engine
+        self.device = engine.device
+        self.npad = int(engine.np)
+        count = len(engine.pset)
+        self.puzzles = list(range(count)) if puzzles is None else [int(p) for p in puzzles]
+        if not self.puzzles:
+            raise ValueError("puzzles must not be empty")
+        if min(self.puzzles) < 0 or max(self.puzzles) >= count:
+            raise ValueError(f"puzzles must be indices into the set (0 .. {count - 1})")
+        self.heuristic, self.batch, self.max_states, self.action_order = heuristic, int(batch), int(max_states), action_order
+        ids = (ctypes.c_int32 * len(self.puzzles))(*self.puzzles)
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib.pw_plan_batch_create(engine.handle, ids, len(self.puzzles), PLAN_MODES[heuristic],
+                                                   self.max_states, self.batch, PLAN_ACTION_ORDERS[action_order],
+                                                   0 if rgd_budget is None else int(rgd_budget),
+                                                   0 if cost_range is None else int(cost_range), ctypes.byref(h)))
+        self.handle = h
+        self._out = None
+
+    def plan(self, puzzle_id: torch.Tensor, pos: torch.Tensor, mask: Optional[torch.Tensor] = None,
+             max_rounds: Optional[int] = None, time_limit: Optional[float] = None, plan_cap: int = 1024):
+        """Starts the searches from ``pos`` (int8 [n, NP, 2], the engine's layout) of puzzles ``puzzle_id`` (int32 [n]), both
+        on the device, on the current stream; does not wait.  ``mask`` (uint8 / bool [n]): 0 skips an item.  ``max_rounds``
+        per item (None: no limit), ``time_limit`` seconds per item on the device's clock (None: none).
+
+        Returns device tensors ``(info int64 [n, 9], plans uint8 [n, plan_cap], plan_len int32 [n], first_action int8 [n])``:
+        ``info`` as ``PlanBatch`` (the eight ``PlannerInfo`` values, then device nanoseconds); ``plan_len`` -1 without a
+        plan (a plan longer than ``plan_cap`` is cut); ``first_action`` the plan's first action, -1 without a non-empty
+        plan.  ``plan_cap`` 0: no plans are written."""
+        n = _state_inputs(puzzle_id, pos, mask, self.npad, self.device)
+        if max_rounds is not None and int(max_rounds) <= 0:
+            raise ValueError("max_rounds must be positive (or None)")
+        if time_limit is not None and not float(time_limit) > 0:
+            raise ValueError("time_limit must be positive seconds (or None)")
+        if int(plan_cap) < 0:
+            raise ValueError("plan_cap must be >= 0")
+        info = torch.empty((n, PLAN_BATCH_INFO), dtype=torch.int64, device=self.device)
+        plans = torch.empty((n, int(plan_cap)), dtype=torch.uint8, device=self.device)
+        plan_len = torch.empty((n,), dtype=torch.int32, device=self.device)
+        first_action = torch.empty((n,), dtype=torch.int8, device=self.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _capi.check(_capi.lib.pw_plan_batch_run_states(
+            self.handle, _capi._ptr(puzzle_id), _capi._ptr(pos), self.npad, _capi._ptr(mask), n,
+            0 if max_rounds is None else int(max_rounds), 0.0 if time_limit is None else float(time_limit), _capi._ptr(info),
+            _capi._ptr(plans) if int(plan_cap) > 0 else None, _capi._ptr(plan_len), int(plan_cap), _capi._ptr(first_action),
+            stream))
+        # (the inputs stay referenced until the results are read: the launch reads them on the device)
+        self._out = (info, plans, plan_len, first_action, puzzle_id, pos, mask)
+        return info, plans, plan_len, first_action
+
+    def results(self) -> List[Tuple[Optional[List[int]], PlannerInfo, float]]:
+        """``(plan or None, PlannerInfo, device seconds)`` per item of the last ``plan`` (waits for it), as
+        ``PlanBatch.results``.  A plan longer than ``plan_cap`` (or any plan with ``plan_cap`` 0) is None."""
+        if self._out is None:
+            raise RuntimeError("plan() has not been called")
+        info, plans, plan_len = (t.cpu().numpy() for t in self._out[:3])
+        out = []
+        for i in range(info.shape[0]):
+            pi = PlannerInfo(int(v) for v in info[i, :8])
+            n = int(plan_len[i])
+            plan = plans[i, :n].tolist() if pi.status == "solved" and 0 <= n <= plans.shape[1] else None
+            out.append((plan, pi, float(info[i, 8]) * 1e-9))
+        return out
+
+    def cancel(self) -> None:
+        """Stops the searches of every ``plan`` so far soon (their status stays ``running``)."""
+        _capi.check(_capi.lib.pw_plan_batch_cancel(self.handle))
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and _capi.lib is not None:
+            try:  # (a launch in flight still uses the slabs)
+                torch.cuda.synchronize(self.device)
+            except Exception:
+                pass
+            _capi.lib.pw_plan_batch_destroy(h)
+            self.handle = None
+
+    __del__ = close

@@ -320,6 +320,24 @@ class VecPushWorld:
         """Host copy of the positions, int8 [B, NP, 2] (entries past a puzzle's movables are 0)."""
         return self.pos.cpu().numpy()
 
+    def planner(self, **kw):
+        """A ``search.StatePlanner`` over this batch's puzzle set (its object order and ``NP``); ``kw`` are its arguments
+        (``puzzles``, ``heuristic``, ``batch``, ``max_states``, ``action_order``, ``rgd_budget``, ``cost_range``)."""
+        from .search import StatePlanner
+
+        return StatePlanner(self, **kw)
+
+    def expert_actions(self, planner, mask: Optional[torch.Tensor] = None, **run_kw) -> torch.Tensor:
+        """int8 [B] on the device: the first action of ``planner``'s plan from every environment's current state, -1 where
+        there is none (unsolved within the limits, already at the goal, masked out or skipped).  One launch on the current
+        stream after whatever was queued there (e.g. ``step``), no wait.  ``run_kw``: ``max_rounds``, ``time_limit`` of
+        ``StatePlanner.plan``; ``planner.results()`` reads the whole outcome afterwards."""
+        if planner.engine is not self.engine:
+            raise ValueError("the planner must be made on this environment (VecPushWorld.planner)")
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        return planner.plan(self.puzzle_id, self.pos, mask=mask, plan_cap=0, **run_kw)[3]
+
     def set_states(self, pos: np.ndarray) -> None:
         self.pos.copy_(torch.as_tensor(np.asarray(pos), dtype=torch.int8))
         self._has_reset = True
