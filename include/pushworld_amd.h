@@ -347,6 +347,8 @@ int64_t pw_engine_obs_stride(const PwEngine* e);       /* recommended env stride
                                       bit 18 kPD (pair tables sized per pair), bits 20-23 wavefronts per workgroup, bit 24 the tile order
                                       (PW_OPT_EXPAND_TILE_ORDER & 1), bit 25 persistent workgroups, bits 32-62 the workgroups of the
                                       grid.  Bits 16-18 and 24-25 are 0 outside families 3-5. */
+#define PW_OPT_CELLS_BASE_BYTES 51   /* read-only: device bytes of the base images of the cell-grid observations (0 until the first
+                                      pw_engine_cells_shape / pw_render_cells / pw_step_cells call builds them) */
 #define PW_OPT_OBS_TUNE_MS 40        /* pw_obs_alloc_tuned: wall-clock budget of the candidate screen in milliseconds (0 = default 10 000): no
                                       further candidate is allocated once it is spent (the best so far is kept and tuned) -- bounds the
                                       constructor when several ranks of a node screen at the same time */
@@ -592,6 +594,33 @@ int pw_step_render_delta(PwEngine* e, const int32_t* puzzle_id, const uint8_t* a
                          int32_t* steps, double* reward, int8_t* dgoals, uint8_t* terminated,
                          uint8_t* truncated, void* obs, int64_t env_stride_bytes, int32_t batch,
                          uint32_t flags, void* stream);
+
+/* CELL-GRID OBSERVATIONS: a compact symbolic observation next to the RGB image, uint8 [3][Hc][Wc]
+ * per environment, channel-first, Hc x Wc = the engine's frame in cells (pad_cell_height / pad_cell_width).  A puzzle of
+ * H x W cells sits at row offset (Hc - H) / 2 and column offset (Wc - W) / 2 (the centring of the RGB frame at one pixel
+ * per cell, env_utils.py:75-91); puzzle cell (x, y) is element [y + oy][x + ox] of every plane.
+ *   plane 0  static:    0 padding, 1 floor, 2 agent wall, 3 wall (a wall is never reported as an agent wall)
+ *   plane 1  occupant:  0 empty, 1 + k where movable k (index into pos[.][k], agent = 0) covers the cell at its position
+ *   plane 2  goal:      0 none, 1 + k where the goal of movable k covers the cell (goal g is movable g + 1's shape at
+ *                       goal g), so its codes 2 .. G + 1 equal the plane-1 code of the object that belongs there
+ * Where shapes overlap (plane 1: only in invalid states) the largest k wins; cells outside the frame are dropped, so any
+ * pos is memory-safe (puzzle ids are clamped to the set as in every kernel).
+ * cells: device buffer, environment e at cells + e * env_stride_bytes, env_stride_bytes >= 3 Hc Wc and otherwise free
+ * (no alignment is required of it or of cells: the tight stride 3 Hc Wc gives a contiguous uint8 [B][3][Hc][Wc] tensor);
+ * the bytes between environments are never written.
+ * The first of these three calls on an engine builds the per-puzzle base images (planes 0 and 2, 3 Hc Wc bytes per
+ * puzzle rounded up to 16, PW_OPT_CELLS_BASE_BYTES): it allocates and copies synchronously, so it must not sit inside a
+ * graph capture -- call pw_engine_cells_shape first.  After it, pw_render_cells / pw_step_cells allocate nothing and
+ * are asynchronous on `stream` (capturable).  PW_ELIMIT when Hc Wc exceeds 65 504 cells (plane 1 is composed in LDS). */
+int pw_engine_cells_shape(PwEngine* e, int* h, int* w);
+/* the observation of every environment's state in pos (one launch) */
+int pw_render_cells(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* cells, int64_t env_stride_bytes,
+                    int32_t batch, void* stream);
+/* pw_step (same arguments, same kernel choice: bound segments, lane groups, boards, autoreset, bad actions; every state
+ * output bit-identical) followed on the same stream by pw_render_cells of the new state: two launches. */
+int pw_step_cells(PwEngine* e, const int32_t* puzzle_id, const uint8_t* actions, int8_t* pos, int32_t* steps,
+                  double* reward, int8_t* dgoals, uint8_t* terminated, uint8_t* truncated, void* cells,
+                  int64_t env_stride_bytes, int32_t batch, uint32_t flags, void* stream);
 
 /* A completion word for the single-environment adapters (gym / dm_env: batch 1, observation and state in pinned host memory):
  * `word` = 8 bytes of pinned, device-addressable host memory (NULL switches it off; the count restarts at 0).  A

@@ -134,6 +134,13 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_int64, c_int32, c_uint32, c_void_p],
     ),
+    "pw_engine_cells_shape": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "pw_render_cells": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "pw_step_cells": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int64, c_int32, c_uint32, c_void_p],
+    ),
     "pw_novelty_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "pw_novelty_destroy": (None, [c_void_p]),
     "pw_novelty_reset": (c_int, [c_void_p, c_void_p]),
@@ -239,6 +246,7 @@ OPTIONS = {
     "obs_screen_ms": 41,       # read-only: what the last screen took
     "step_one_applies": 49,    # read-only: step_render_delta on a batch of one with a completion word is ONE launch on this engine
     "mailbox_form": 48,        # read-only: 0 no mailbox open, 1 lanes / boards, 2 the segments of the bound batch
+    "cells_base_bytes": 51,    # read-only: device bytes of the cell-grid base images (0 until the first cells call)
     "expand_form": 50,         # read-only: kernel instance and grid of the last pw_expand4 launch (decode_expand_form)
     "mailbox_seg": 47,         # the resident kernel of a fully bound batch runs its segments (tables in LDS): 0 automatic, 2 never
     "step_one_fused": 46,      # step_render_delta on a batch of one with a completion word: 1 (default) one launch, 2 ... writing whole rows, 0 two launches
@@ -1031,6 +1039,40 @@ class Engine:
         check(lib.pw_step_render(self.handle, _ptr(puzzle_id), _ptr(actions), _ptr(pos), _ptr(steps),
                                  _ptr(reward), _ptr(dgoals), _ptr(terminated), _ptr(truncated),
                                  _ptr(obs_storage), self.obs_stride, pos.shape[0], flags, self._stream()))
+
+    # cell-grid observations (pw_render_cells / pw_step_cells): uint8 [B, 3, Hc, Wc], any env stride >= 3 Hc Wc
+    def cells_shape(self):
+        """``(3, Hc, Wc)`` of the cell-grid observation.  The first call builds the engine's base images (allocates:
+        not inside a graph capture); later cells calls allocate nothing."""
+        h, w = c_int(), c_int()
+        check(lib.pw_engine_cells_shape(self.handle, ctypes.byref(h), ctypes.byref(w)))
+        return (3, h.value, w.value)
+
+    def render_cells(self, puzzle_id, pos, cells, env_stride=None):
+        """``pw_render_cells`` into ``cells`` (uint8, ``env_stride`` bytes per environment, default tight)."""
+        stride = cells.stride(0) * cells.element_size() if env_stride is None else int(env_stride)
+        check(lib.pw_render_cells(self.handle, _ptr(puzzle_id), _ptr(pos), _ptr(cells), stride, pos.shape[0],
+                                  self._stream()))
+
+    def step_cells(self, puzzle_id, actions, pos, steps, reward, dgoals, terminated, truncated, cells, flags=0,
+                   env_stride=None):
+        stride = cells.stride(0) * cells.element_size() if env_stride is None else int(env_stride)
+        check(lib.pw_step_cells(self.handle, _ptr(puzzle_id), _ptr(actions), _ptr(pos), _ptr(steps), _ptr(reward),
+                                _ptr(dgoals), _ptr(terminated), _ptr(truncated), _ptr(cells), stride, pos.shape[0],
+                                flags, self._stream()))
+
+    def bind_step_cells(self, puzzle_id, pos, steps, reward, dgoals, terminated, truncated, cells, flags=0):
+        """Returns ``call(actions_data_ptr)`` == ``step_cells(...)`` on the current stream (tight stride)."""
+        fn, h, dev, batch = lib.pw_step_cells, self.handle, self.device.index, pos.shape[0]
+        stride = cells.stride(0) * cells.element_size()
+        a = [_ptr(t) for t in (puzzle_id, pos, steps, reward, dgoals, terminated, truncated, cells)]
+        keep = (puzzle_id, pos, steps, reward, dgoals, terminated, truncated, cells)
+
+        def call(actions_ptr, _keep=keep):
+            rc = fn(h, a[0], actions_ptr, a[1], a[2], a[3], a[4], a[5], a[6], a[7], stride, batch, flags, _raw_stream(dev))
+            if rc:
+                check(rc)
+        return call
 
     def step_render_delta(self, puzzle_id, actions, pos, steps, reward, dgoals, terminated, truncated, obs_storage,
                           flags=0):

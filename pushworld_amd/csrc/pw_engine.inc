@@ -909,6 +909,7 @@ void pw_engine_destroy(PwEngine* e) {
   if (e->d_estat_page) (void)hipFree(e->d_estat_page);
   if (e->d_estat_page_off) (void)hipFree(e->d_estat_page_off);
   if (e->d_simg) (void)hipFree(e->d_simg);
+  if (e->d_cells_base) (void)hipFree(e->d_cells_base);
   if (e->d_srow) (void)hipFree(e->d_srow);
   if (e->d_dirty) (void)hipFree(e->d_dirty);
   if (e->d_scratch) (void)hipFree(e->d_scratch);
@@ -2208,6 +2209,7 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
     case PW_OPT_STEP_TABLE_BYTES:
     case PW_OPT_STEP_TABLE_PUZZLES:
     case PW_OPT_EXPAND_FORM:
+    case PW_OPT_CELLS_BASE_BYTES:
       return pw_fail(PW_EINVAL, "read-only option");
     case PW_OPT_STEP_TABLES: {
       if (value < 0 || value > 3)
@@ -2268,6 +2270,7 @@ int64_t pw_engine_get_option(const PwEngine* e, int32_t option) try {
     case PW_OPT_SEARCH_BATCH_GROUPS_PER_CU: return e->search_batch_groups_per_cu;
     case PW_OPT_EXPAND_WG_WAVES: return e->expand_wg_waves;
     case PW_OPT_EXPAND_FORM: return e->expand_form;
+    case PW_OPT_CELLS_BASE_BYTES: return e->cells_base_bytes;
     case PW_OPT_STEP_BLOCK_ORDER: return e->step_reverse;
     case PW_OPT_STEP_BOARDS: return e->step_boards;
     case PW_OPT_STEP_BOARD_SET: return e->d_boards ? 1 : 0;

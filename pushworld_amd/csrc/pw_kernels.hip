@@ -238,6 +238,8 @@ struct PwEngine {
   uint32_t* d_estat_off;   // byte offset of puzzle p's table in d_estat (16 B aligned)
   uint32_t pal_rgb[16];
   float pal_f32[16][4];
+  uint8_t* d_cells_base;   // cell-grid observations (csrc/pw_cells.inc): base image of every puzzle, built by the first cells call
+  int64_t cells_base_bytes;
 };
 
 // ------------------------------------------------------------------------------------
@@ -402,7 +404,9 @@ struct PageRec {
 #include "pw_mailbox_kernels.inc"
 #include "pw_expand_kernels.inc"
 #include "pw_render_kernels.inc"
+#include "pw_cells_kernels.inc"
 #include "pw_engine.inc"
+#include "pw_cells.inc"
 #include "pw_mailbox.inc"
 #include "pw_search.inc"
 #include "pw_rgd.inc"

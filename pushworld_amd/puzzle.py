@@ -321,6 +321,40 @@ class PushWorldPuzzle:
         return masks_to_graph(self._parsed.movement_graph_masks(obj))
 
     # ---------------------------------------------------------------- rendering
+    def cells(self, state, frame: Optional[Tuple[int, int]] = None) -> np.ndarray:
+        """The cell-grid observation of ``state``, computed on the host: uint8 ``[3, Hc, Wc]``.
+
+        ``frame`` is ``(Hc, Wc)`` in cells (default: this puzzle's own ``(H, W)``); the puzzle sits at row offset
+        ``(Hc - H) // 2`` and column offset ``(Wc - W) // 2``.  Plane 0: 0 padding, 1 floor, 2 agent wall, 3 wall.
+        Plane 1: ``1 + k`` where movable ``k`` (this puzzle's object order, agent 0) covers the cell.  Plane 2:
+        ``1 + k`` where the goal of movable ``k`` covers it.  The largest ``k`` wins on overlap; cells outside the frame
+        are dropped.  This is the definition ``pw_render_cells`` is tested against."""
+        W, H = self.dimensions
+        hc, wc = (H, W) if frame is None else (int(frame[0]), int(frame[1]))
+        if hc < H or wc < W:
+            raise ValueError(f"frame {hc} x {wc} is smaller than the puzzle ({H} x {W})")
+        if len(state) != self.num_movables:
+            raise ValueError(f"state has {len(state)} positions, puzzle has {self.num_movables} movables")
+        oy, ox = (hc - H) // 2, (wc - W) // 2
+        out = np.zeros((3, hc, wc), np.uint8)
+        out[0, oy : oy + H, ox : ox + W] = 1
+        for x, y in self.agent_wall_positions:
+            out[0, y + oy, x + ox] = 2
+        for x, y in self.wall_positions:
+            out[0, y + oy, x + ox] = 3
+
+        def paint(plane, k, origin):
+            for cx, cy in self.movable_objects[k].cells:
+                fx, fy = int(origin[0]) + cx + ox, int(origin[1]) + cy + oy
+                if 0 <= fx < wc and 0 <= fy < hc:
+                    out[plane, fy, fx] = k + 1
+
+        for k in range(self.num_movables):
+            paint(1, k, state[k])
+        for g, goal in enumerate(self.goal_state):
+            paint(2, g + 1, goal)
+        return out
+
     def render(self, state: State, border_width: int = DEFAULT_BORDER_WIDTH,
                pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL) -> np.ndarray:
         """puzzle.py:426-469 on the GPU; uint8 (height, width, 3)."""

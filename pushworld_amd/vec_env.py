@@ -30,7 +30,11 @@ class VecPushWorld:
         puzzle_ids: int array [B] of pool indices (default: ``i % len(puzzles)``).  Grouping
             equal ids together keeps a workgroup's puzzle tables hot in L1/L2.
         max_steps: truncation limit (gym_env.py:223) or None.
-        observation: "uint8", "float32" or None (state only, no render kernel).
+        observation: "uint8", "float32", "cells" or None (state only, no render kernel).  "cells": the compact
+            cell-grid observation (``PushWorldPuzzle.cells``), ``obs`` is a contiguous uint8 tensor
+            [B, 3, Hc, Wc] kept current by ``pw_step_cells`` / ``pw_render_cells``; ``incremental`` and ``tune`` /
+            ``tune_allocations`` do not apply to it and are refused, ``fused`` is ignored (a step is always the step
+            launch followed by the cells launch).
         pad_cells: (height, width) of the observation frame in cells; default = pool maximum
             (gym_env.py:80-82).
         autoreset: next-step autoreset inside the step kernel.
@@ -73,8 +77,10 @@ class VecPushWorld:
                  autoreset: bool = False, fused: bool = True, resample=False, seed: int = 0,
                  incremental: bool = False, engine_options: Optional[dict] = None, tune: Optional[bool] = None,
                  tune_allocations: Optional[int] = None, bind: Optional[bool] = None):
-        if observation not in ("uint8", "float32", None):
-            raise ValueError("observation must be 'uint8', 'float32' or None")
+        if observation not in ("uint8", "float32", "cells", None):
+            raise ValueError("observation must be 'uint8', 'float32', 'cells' or None")
+        if observation == "cells" and (incremental or tune or tune_allocations):
+            raise ValueError("incremental, tune and tune_allocations apply to the RGB observations, not to observation='cells'")
         dev = default_device_index() if device is None else int(device)
         if isinstance(puzzles, _capi.PuzzleSet):  # e.g. PuzzleSet.load(packed file): no texts, no parsing
             if puzzles.device != dev:
@@ -91,7 +97,8 @@ class VecPushWorld:
         dtype = _capi.OBS_F32 if observation == "float32" else _capi.OBS_U8
         # (max_batch: the engine's per-environment scratch is sized here, once -- no step / render call allocates later)
         self.engine = _capi.Engine(self.pset, max_steps, pixels_per_cell, border_width, dtype, ph, pw,
-                                   options=engine_options, max_batch=int(num_envs) if observation is not None else 0)
+                                   options=engine_options,
+                                   max_batch=int(num_envs) if observation in ("uint8", "float32") else 0)
         self.device = self.engine.device
         self.num_envs = int(num_envs)
         self.observation = observation
@@ -136,7 +143,10 @@ class VecPushWorld:
         self._has_reset = False
         self._obs_storage, self.obs = None, None
         self.obs_owned_by_library = False
-        if observation is not None:
+        if observation == "cells":
+            # (builds the engine's base images now: no later step / render call allocates, so steps are capturable)
+            self.obs = torch.empty((self.num_envs,) + self.engine.cells_shape(), dtype=torch.uint8, device=self.device)
+        elif observation is not None:
             nbytes = self.num_envs * self.engine.obs_stride
             if tune is None:
                 tune = nbytes >= (256 << 20)
@@ -193,7 +203,11 @@ class VecPushWorld:
         self._call_step = self.engine.bind_step(self.puzzle_id, self.pos, self.steps, self.reward, self.dgoals,
                                                 self.terminated, self.truncated, self.flags)
         self._call_step_render = self._call_step_delta = None
-        if self.obs is not None:
+        if observation == "cells":
+            self._call_step_render = self.engine.bind_step_cells(
+                self.puzzle_id, self.pos, self.steps, self.reward, self.dgoals, self.terminated, self.truncated,
+                self.obs, self.flags)
+        elif self.obs is not None:
             self._call_step_render = self.engine.bind_step_render(
                 self.puzzle_id, self.pos, self.steps, self.reward, self.dgoals, self.terminated, self.truncated,
                 self._obs_storage, self.flags)
@@ -227,9 +241,15 @@ class VecPushWorld:
         if self._bind and (self.bound_info is None or self.resample or mask is None):
             self.bound_info = self.engine.bind(self.puzzle_id)  # (reads the segment count back: later launches have the exact grid)
         if self.obs is not None:
-            self.engine.render(self.puzzle_id, self.pos, self._obs_storage)
-            self._obs_current = True
+            self._render()
         return self.obs
+
+    def _render(self) -> None:
+        if self.observation == "cells":
+            self.engine.render_cells(self.puzzle_id, self.pos, self.obs)
+        else:
+            self.engine.render(self.puzzle_id, self.pos, self._obs_storage)
+        self._obs_current = True
 
     def step(self, actions: torch.Tensor):
         """gym_env.py:188-226 for every environment.
@@ -252,7 +272,9 @@ class VecPushWorld:
         if self.obs is None:
             self._call_step(actions.data_ptr())  # one ctypes call with ready arguments: the launch is host bound
             return None, self.reward, self.terminated, self.truncated
-        if self.incremental and self._obs_current:
+        if self.observation == "cells":
+            self._call_step_render(actions.data_ptr())  # pw_step_cells
+        elif self.incremental and self._obs_current:
             self._call_step_delta(actions.data_ptr())
         elif self.fused:
             self._call_step_render(actions.data_ptr())
@@ -312,8 +334,7 @@ class VecPushWorld:
         """Re-renders the current states into the observation buffer and returns it."""
         if self.obs is None:
             raise RuntimeError("this VecPushWorld was created with observation=None")
-        self.engine.render(self.puzzle_id, self.pos, self._obs_storage)
-        self._obs_current = True
+        self._render()
         return self.obs
 
     def states(self) -> np.ndarray:

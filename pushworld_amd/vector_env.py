@@ -71,17 +71,24 @@ class _VectorCore:
             raise ValueError("border_width must be >= 1")
         if pixels_per_cell < 3:
             raise ValueError("pixels_per_cell must be >= 3")
-        if observation not in ("float32", "uint8"):
-            raise ValueError("observation must be 'float32' or 'uint8'")
+        if observation not in ("float32", "uint8", "cells"):
+            raise ValueError("observation must be 'float32', 'uint8' or 'cells'")
         puzzles, pad = _load_pool(puzzle_path, standard_padding)
+        cells = observation == "cells"
         self.vec = VecPushWorld(puzzles, num_envs, max_steps=max_steps, border_width=border_width,
                                 pixels_per_cell=pixels_per_cell, observation=observation, pad_cells=pad,
                                 device=device, autoreset=True, resample=True if sample_table is None else sample_table,
-                                seed=seed, incremental=incremental)
+                                seed=seed, incremental=incremental and not cells)
         self.num_envs = int(num_envs)
         self.to_numpy = bool(to_numpy)
         self._obs_dtype = np.float32 if observation == "float32" else np.uint8
-        self._obs_high = 1.0 if observation == "float32" else 255
+        if cells:  # codes 0 .. 3 in plane 0, 0 .. 1 + largest movable index in planes 1 and 2
+            self._obs_high = max(3, max(p.num_movables for p in puzzles))
+            self._obs_shape = tuple(self.vec.obs.shape[1:])
+        else:
+            self._obs_high = 1.0 if observation == "float32" else 255
+            self._obs_shape = self.vec.engine.obs_shape
+        self._rgb = None  # RGB frames of render() in cells mode: (storage, view), allocated by the first call
         self._pending = False
         self._closed = False
 
@@ -152,7 +159,8 @@ class PushWorldVectorEnv(_VectorCore):
     Args (first five as ``PushWorldEnv``, gym_env.py:57-64):
         puzzle_path: ``.pwp`` file, directory searched recursively, or a list of paths / puzzles.
         num_envs: batch size B.
-        observation: "float32" (reference observation, values in [0, 1]) or "uint8" (4x fewer bytes).
+        observation: "float32" (reference observation, values in [0, 1]), "uint8" (4x fewer bytes) or "cells" (the
+            cell-grid observation uint8 [B, 3, Hc, Wc]; ``render()`` still returns RGB frames).
         seed: seed of the per-episode puzzle draw.
         sample_table: optional pool indices to draw from (repeats = weights); default uniform.
         to_numpy: return host numpy arrays (and python-side checks) instead of device tensors.
@@ -168,9 +176,9 @@ class PushWorldVectorEnv(_VectorCore):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
                          observation, seed, sample_table, device, to_numpy)
         self.single_action_space = _compat.make_discrete(NUM_ACTIONS)
-        self.single_observation_space = _compat.make_box(0, self._obs_high, self.vec.engine.obs_shape, self._obs_dtype)
+        self.single_observation_space = _compat.make_box(0, self._obs_high, self._obs_shape, self._obs_dtype)
         self.action_space = _BatchSpace(_compat.Discrete(NUM_ACTIONS), num_envs)
-        self.observation_space = _BatchSpace(_compat.Box(0, self._obs_high, self.vec.engine.obs_shape, self._obs_dtype),
+        self.observation_space = _BatchSpace(_compat.Box(0, self._obs_high, self._obs_shape, self._obs_dtype),
                                              num_envs)
 
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
@@ -203,6 +211,11 @@ class PushWorldVectorEnv(_VectorCore):
 
     def render(self):
         """uint8 frames [B, H, W, 3] of the current states (padded frame)."""
+        if self.vec.observation == "cells":  # RGB on demand, into a buffer of its own
+            if self._rgb is None:
+                self._rgb = self.vec.engine.alloc_obs(self.num_envs)
+            self.vec.engine.render(self.vec.puzzle_id, self.vec.pos, self._rgb[0])
+            return self._out(self._rgb[1])
         if self.vec.observation == "uint8":
             return self._out(self.vec.obs)
         return self._out((self.vec.obs * 255.0).round().to(torch.uint8))
@@ -222,7 +235,7 @@ class PushWorldDmVectorEnv(_VectorCore):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
                          observation, seed, sample_table, device, to_numpy)
         self._action_spec = _compat.make_discrete_array(NUM_ACTIONS, int, "action")
-        self._observation_spec = _compat.make_bounded_array(self.vec.engine.obs_shape, self._obs_dtype, "board", 0,
+        self._observation_spec = _compat.make_bounded_array(self._obs_shape, self._obs_dtype, "board", 0,
                                                             self._obs_high)
         self._was_done = None
 
