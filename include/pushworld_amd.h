@@ -857,6 +857,60 @@ int pw_plan_batch_run_states(PwPlanBatch* b, const int32_t* puzzle_id, const int
 int pw_plan_batch_cancel(PwPlanBatch* b);
 void pw_plan_batch_destroy(PwPlanBatch* b);
 
+/* Plan replay (K11): ONE ragged replay of a whole batch of plans on the device -- the reference's is_valid_plan verdict
+ * (puzzle.py:413-424) per plan, and every step of every accepted plan as a row of flat device arrays (state, action, reward,
+ * done), ready for pw_render / pw_render_cells over (row_puzzle_id, row_pos).  The inputs are device memory in the formats
+ * pw_plan_batch_run / pw_plan_batch_run_states write, so a planner's outputs go in as they are, on the same stream.
+ *   puzzle_id   int32 [n] set indices of the engine
+ *   pos         int8 [n][npad][2] start states in the engine's layout, or NULL: every item starts from its puzzle's initial state
+ *   npad        4, 8, 16 or 32, at least the set's largest number of movables (pw_engine_npad fits)
+ *   plans       uint8 [n][plan_cap]; plan_len int32 [n]; plan_cap 1 .. PW_PLAN_MAX_ACTIONS
+ *   mask        uint8 [n] or NULL: 0 skips the item
+ * pw_plan_replay_check replays every item and writes
+ *   verdict     int8 [n]:
+ *     PW_REPLAY_VALID     the goal holds after the last action and in no earlier state: is_valid_plan from the given start.  As
+ *                         there, the empty plan is valid exactly when the start is a goal, and any longer plan from a start
+ *                         that is a goal is PW_REPLAY_EARLY.
+ *     PW_REPLAY_NOT_GOAL  neither the final state nor an earlier one is a goal
+ *     PW_REPLAY_EARLY     some state before the last is a goal
+ *     PW_REPLAY_NONE      plan_len < 0
+ *     PW_REPLAY_CUT       plan_len > plan_cap: the stored plan is incomplete, nothing is replayed
+ *     PW_REPLAY_SKIPPED   the item is masked out, its id is outside the set or a movable lies outside its grid
+ *                         (pw_plan_batch_run_states' range test; nothing further of the item is read), or a plan byte is not in 0..3
+ *   first_goal  int32 [n] or NULL: index of the first goal state (0 = the start), -1 when there is none or nothing was replayed
+ *   final_pos   int8 [n][npad][2] or NULL: the state after the last action (zeros for an item that was not replayed)
+ *   offset      int64 [n + 1]: exclusive prefix sum of the rows every item will emit -- plan_len when the item is included,
+ *               else 0; offset[n] = the total.  include = PW_REPLAY_INCLUDE_VALID keeps the VALID items,
+ *               PW_REPLAY_INCLUDE_REPLAYED the VALID, NOT_GOAL and EARLY ones.
+ * pw_plan_replay_emit takes the same inputs with the `verdict` and `offset` of the check and writes row offset[i] + t of every
+ * included item i, t < plan_len[i] (any output may be NULL):
+ *   row_item / row_t / row_puzzle_id int32 [cap]; row_pos int8 [cap][npad][2]: the state BEFORE the action, padding zeroed as
+ *   pw_render expects; row_action uint8 [cap]; row_reward float64 [cap] and row_done uint8 [cap]: exactly pw_step's reward and
+ *   `terminated` of that step (10.0 when the next state is a goal, else the change of goals achieved - 0.01);
+ *   row_next_pos int8 [cap][npad][2]: the state after it.
+ *   Rows at or beyond `cap` are not written; *dropped (device int64, or NULL) receives how many were left out.
+ * Both are asynchronous on `stream` (a replay is one launch; the check adds rocPRIM's scan) and read nothing on the host.  The
+ * engine keeps a small workspace that grows with n (the first call of a size allocates).
+ * PW_EINVAL before any launch, pw_last_error naming the argument: n < 1; npad not 4 / 8 / 16 / 32; a null puzzle_id, plans,
+ * plan_len, verdict or offset; plan_cap outside 1 .. PW_PLAN_MAX_ACTIONS; an unknown include; cap < 0; a null engine; npad below
+ * the set's largest number of movables. */
+#define PW_REPLAY_VALID 1
+#define PW_REPLAY_NOT_GOAL 0
+#define PW_REPLAY_EARLY 2
+#define PW_REPLAY_NONE (-1)
+#define PW_REPLAY_CUT (-2)
+#define PW_REPLAY_SKIPPED (-3)
+#define PW_REPLAY_INCLUDE_VALID 0
+#define PW_REPLAY_INCLUDE_REPLAYED 1
+int pw_plan_replay_check(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* plans,
+                         const int32_t* plan_len, int32_t plan_cap, const uint8_t* mask, int32_t n, int32_t include,
+                         int8_t* verdict, int32_t* first_goal, int8_t* final_pos, int64_t* offset, void* stream);
+int pw_plan_replay_emit(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* plans,
+                        const int32_t* plan_len, int32_t plan_cap, const uint8_t* mask, int32_t n, int32_t include,
+                        const int8_t* verdict, const int64_t* offset, int64_t cap, int32_t* row_item, int32_t* row_t,
+                        int32_t* row_puzzle_id, int8_t* row_pos, uint8_t* row_action, double* row_reward, uint8_t* row_done,
+                        int8_t* row_next_pos, int64_t* dropped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

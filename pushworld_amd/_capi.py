@@ -203,7 +203,17 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "pw_plan_batch_cancel": (c_int, [c_void_p]),
     "pw_plan_batch_destroy": (None, [c_void_p]),
+    "pw_plan_replay_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_plan_replay_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                    c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
+
+# pw_plan_replay_check verdicts and the `include` choices (include/pushworld_amd.h)
+REPLAY_VALID, REPLAY_NOT_GOAL, REPLAY_EARLY, REPLAY_NONE, REPLAY_CUT, REPLAY_SKIPPED = 1, 0, 2, -1, -2, -3
+REPLAY_INCLUDE_VALID, REPLAY_INCLUDE_REPLAYED = 0, 1
+PLAN_MAX_ACTIONS = 65536
 
 # pw_engine_set_option keys (include/pushworld_amd.h)
 OPTIONS = {
@@ -1080,6 +1090,19 @@ class Engine:
         check(lib.pw_step_render_delta(self.handle, _ptr(puzzle_id), _ptr(actions), _ptr(pos), _ptr(steps),
                                        _ptr(reward), _ptr(dgoals), _ptr(terminated), _ptr(truncated),
                                        _ptr(obs_storage), self.obs_stride, pos.shape[0], flags, self._stream()))
+
+    # plan replay (pw_plan_replay_check / pw_plan_replay_emit): device tensors in, device tensors out, no wait
+    def plan_replay_check(self, puzzle_id, pos, plans, plan_len, mask, include, verdict, first_goal, final_pos, offset):
+        check(lib.pw_plan_replay_check(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(plans), _ptr(plan_len),
+                                       plans.shape[1], _ptr(mask), puzzle_id.shape[0], int(include), _ptr(verdict),
+                                       _ptr(first_goal), _ptr(final_pos), _ptr(offset), self._stream()))
+
+    def plan_replay_emit(self, puzzle_id, pos, plans, plan_len, mask, include, verdict, offset, cap, item=None, t=None,
+                         row_puzzle_id=None, row_pos=None, action=None, reward=None, done=None, next_pos=None, dropped=None):
+        check(lib.pw_plan_replay_emit(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(plans), _ptr(plan_len),
+                                      plans.shape[1], _ptr(mask), puzzle_id.shape[0], int(include), _ptr(verdict), _ptr(offset),
+                                      int(cap), _ptr(item), _ptr(t), _ptr(row_puzzle_id), _ptr(row_pos), _ptr(action),
+                                      _ptr(reward), _ptr(done), _ptr(next_pos), _ptr(dropped), self._stream()))
 
     def expand4(self, puzzle_index, states, succ, moved, goal):
         check(lib.pw_expand4(self.handle, int(puzzle_index), _ptr(states), _ptr(succ), _ptr(moved), _ptr(goal),

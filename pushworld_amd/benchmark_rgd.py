@@ -3,8 +3,8 @@
 Every puzzle below ``--puzzles-path`` is planned by best-first search (RGD or N+RGD) -- all of them in one launch
 (``search.PlanBatch``), each under its own time limit -- and one YAML result per puzzle is written under ``--results-path``,
 mirroring the puzzles' directory structure.  The files hold the reference's keys: ``planner``, ``puzzle``, ``plan`` (a string of
-L / R / U / D, or null), ``planning_time`` (seconds) and, without a plan, ``failure_reason``.  Plans are checked with
-``PushWorldPuzzle.is_valid_plan`` before they are written.  The YAML is written here, in ``yaml.dump``'s format for these
+L / R / U / D, or null), ``planning_time`` (seconds) and, without a plan, ``failure_reason``.  All plans are checked by one
+replay launch (``PlanBatch.validate``: the reference's ``is_valid_plan``) before they are written.  The YAML is written here, in ``yaml.dump``'s format for these
 flat mappings (keys sorted, plain scalars where PyYAML writes them plain): PyYAML is not needed.
 """
 from __future__ import annotations
@@ -97,7 +97,7 @@ def benchmark_rgd_planner(results_path: str = "nrgd_results", puzzles_path: Opti
     by output path."""
     from .config import BENCHMARK_PUZZLES_PATH, PUZZLE_EXTENSION
     from .puzzle import PushWorldPuzzle
-    from .search import solve_many
+    from .search import REPLAY_VALID, PlanBatch
     from .utils.filesystem import map_files_with_extension
 
     if heuristic not in PLANNER_NAMES:
@@ -111,14 +111,18 @@ def benchmark_rgd_planner(results_path: str = "nrgd_results", puzzles_path: Opti
         per_state = 4 * ((n_max + 1) // 2) + 25  # store, links, queue links, closed set at half load
         budget = MAX_STATES_CAP if memory_limit is None else int(memory_limit * GIGABYTE) // per_state
         max_states = max(4 * batch + 1, min(MAX_STATES_CAP, budget))
-    results = solve_many(puzzles, mode=heuristic, batch=batch, max_states=max_states, action_order=action_order,
-                         time_limit=time_limit)
+    pb = PlanBatch(puzzles, heuristic=heuristic, batch=batch, max_states=max_states, action_order=action_order)
+    try:
+        pb.run(time_limit=time_limit)
+        verdicts = pb.validate()  # (queued behind the searches; results() waits for both)
+        results = pb.results()
+        verdicts = verdicts.cpu().numpy()
+    finally:
+        pb.close()
     out = {}
-    for (src, dst), (plan, info, seconds) in zip(pairs, results):
+    for (src, dst), (plan, info, seconds), verdict in zip(pairs, results, verdicts):
         text = None if plan is None else "".join("LRUD"[a] for a in plan)
-        valid = True
-        if text is not None:
-            valid = PushWorldPuzzle(src).is_valid_plan(["LRUD".index(c) for c in text])
+        valid = text is None or int(verdict) == REPLAY_VALID
         name = os.path.splitext(os.path.split(src)[1])[0]
         result = planning_result(PLANNER_NAMES[heuristic], name, info.status, text, seconds, time_limit, valid)
         with open(dst, "w") as f:

@@ -910,6 +910,7 @@ void pw_engine_destroy(PwEngine* e) {
   if (e->d_estat_page_off) (void)hipFree(e->d_estat_page_off);
   if (e->d_simg) (void)hipFree(e->d_simg);
   if (e->d_cells_base) (void)hipFree(e->d_cells_base);
+  if (e->d_replay) (void)hipFree(e->d_replay);
   if (e->d_srow) (void)hipFree(e->d_srow);
   if (e->d_dirty) (void)hipFree(e->d_dirty);
   if (e->d_scratch) (void)hipFree(e->d_scratch);

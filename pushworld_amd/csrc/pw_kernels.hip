@@ -240,6 +240,9 @@ struct PwEngine {
   float pal_f32[16][4];
   uint8_t* d_cells_base;   // cell-grid observations (csrc/pw_cells.inc): base image of every puzzle, built by the first cells call
   int64_t cells_base_bytes;
+  uint8_t* d_replay;       // plan replay (csrc/pw_plan_replay.inc): 64 work counters + the offset scan's temporary storage, grown on demand
+  size_t replay_bytes;
+  uint32_t replay_seq;     // launches so far: launch k takes counter k mod 64
 };
 
 // ------------------------------------------------------------------------------------
@@ -412,4 +415,5 @@ struct PageRec {
 #include "pw_rgd.inc"
 #include "pw_planner.inc"
 #include "pw_plan_batch.inc"
+#include "pw_plan_replay.inc"
 #include "pw_generate.inc"

@@ -548,6 +548,16 @@ class PlanBatch:
             out.append((plan, pi, float(info[i, 8]) * 1e-9))
         return out
 
+    def validate(self) -> torch.Tensor:
+        """int8 [n] on the device: the ``is_valid_plan`` verdict (``REPLAY_VERDICT``) of every plan of the last ``run``, from
+        one replay launch on the current stream (``replay_plans``; no wait).  Items without a plan are ``REPLAY_NONE``, plans
+        cut at ``plan_cap`` ``REPLAY_CUT``."""
+        if self._out is None:
+            raise RuntimeError("run() has not been called")
+        _, plans, plan_len = self._out
+        ids = torch.arange(self.n, dtype=torch.int32, device=self.device)
+        return replay_plans(self._engine, ids, plans, plan_len, rows=False).verdict
+
     def close(self) -> None:
         h = getattr(self, "handle", None)
         if h and _capi.lib is not None:
@@ -692,6 +702,17 @@ class StatePlanner:
             out.append((plan, pi, float(info[i, 8]) * 1e-9))
         return out
 
+    def validate(self) -> torch.Tensor:
+        """int8 [n] on the device: the ``is_valid_plan`` verdict (``REPLAY_VERDICT``) of every plan of the last ``plan``
+        call, taken from that call's start states, from one replay launch on the current stream (``replay_plans``; no
+        wait)."""
+        if self._out is None:
+            raise RuntimeError("plan() has not been called")
+        _, plans, plan_len, _, puzzle_id, pos, mask = self._out
+        if plans.shape[1] < 1:
+            raise ValueError("the last plan() call kept no plans (plan_cap 0)")
+        return replay_plans(self.engine, puzzle_id, plans, plan_len, pos=pos, mask=mask, rows=False).verdict
+
     def cancel(self) -> None:
         """Stops the searches of every ``plan`` so far soon (their status stays ``running``)."""
         _capi.check(_capi.lib.pw_plan_batch_cancel(self.handle))
@@ -707,3 +728,100 @@ class StatePlanner:
             self.handle = None
 
     __del__ = close
+
+
+# ---- plan replay (pw_plan_replay_check / pw_plan_replay_emit) ----------------------------------------------
+REPLAY_VALID, REPLAY_NOT_GOAL, REPLAY_EARLY = _capi.REPLAY_VALID, _capi.REPLAY_NOT_GOAL, _capi.REPLAY_EARLY
+REPLAY_NONE, REPLAY_CUT, REPLAY_SKIPPED = _capi.REPLAY_NONE, _capi.REPLAY_CUT, _capi.REPLAY_SKIPPED
+REPLAY_VERDICT = {REPLAY_VALID: "valid", REPLAY_NOT_GOAL: "not_goal", REPLAY_EARLY: "early", REPLAY_NONE: "none",
+                  REPLAY_CUT: "cut", REPLAY_SKIPPED: "skipped"}
+REPLAY_INCLUDE = {"valid": _capi.REPLAY_INCLUDE_VALID, "replayed": _capi.REPLAY_INCLUDE_REPLAYED}
+
+
+def _replay_inputs(puzzle_id, plans, plan_len, pos, mask, npad: int, device) -> int:
+    """The checks of ``replay_plans`` on its device arrays; returns n."""
+    if not isinstance(puzzle_id, torch.Tensor) or puzzle_id.dtype != torch.int32 or puzzle_id.dim() != 1:
+        raise ValueError("puzzle_id must be an int32 tensor [n]")
+    n = int(puzzle_id.shape[0])
+    if n < 1 or n >= 1 << 31:
+        raise ValueError("puzzle_id must hold 1 .. 2^31 - 1 items")
+    if not isinstance(plans, torch.Tensor) or plans.dtype != torch.uint8 or plans.dim() != 2 or plans.shape[0] != n:
+        raise ValueError("plans must be a uint8 tensor [n, plan_cap]")
+    if not 1 <= int(plans.shape[1]) <= _capi.PLAN_MAX_ACTIONS:
+        raise ValueError(f"plans must hold 1 .. {_capi.PLAN_MAX_ACTIONS} actions per item (plan_cap)")
+    if not isinstance(plan_len, torch.Tensor) or plan_len.dtype != torch.int32 or tuple(plan_len.shape) != (n,):
+        raise ValueError("plan_len must be an int32 tensor [n]")
+    if pos is not None and (not isinstance(pos, torch.Tensor) or pos.dtype != torch.int8 or tuple(pos.shape) != (n, npad, 2)):
+        raise ValueError(f"pos must be an int8 tensor [n, {npad}, 2] (the engine's state layout) or None")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool)
+                             or tuple(mask.shape) != (n,)):
+        raise ValueError("mask must be a uint8 or bool tensor [n] (or None)")
+    for name, t in (("puzzle_id", puzzle_id), ("plans", plans), ("plan_len", plan_len), ("pos", pos), ("mask", mask)):
+        if t is None:
+            continue
+        if t.device != device:
+            raise ValueError(f"{name} must live on {device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return n
+
+
+class PlanReplay:
+    """What ``replay_plans`` returns; every tensor lives on the device.
+
+    Per item: ``verdict`` int8 [n] (``REPLAY_*``), ``first_goal`` int32 [n] (index of the first goal state, 0 = the start, -1
+    none), ``final_pos`` int8 [n, NP, 2], ``offset`` int64 [n + 1] (rows of item i: ``offset[i] : offset[i + 1]``).
+    Per row (``num_rows`` of them, None when no rows were asked for): ``item``, ``t``, ``puzzle_id`` int32, ``pos`` int8
+    [T, NP, 2] (the state before the action), ``action`` uint8, ``reward`` float64, ``done`` uint8, ``next_pos`` (on request);
+    ``obs`` is filled in by ``VecPushWorld.demonstrations``."""
+
+    __slots__ = ("verdict", "first_goal", "final_pos", "offset", "num_rows", "item", "t", "puzzle_id", "pos", "action",
+                 "reward", "done", "next_pos", "obs")
+
+    def __init__(self):
+        for name in self.__slots__:
+            setattr(self, name, None)
+
+
+def replay_plans(engine_or_vec, puzzle_id: torch.Tensor, plans: torch.Tensor, plan_len: torch.Tensor,
+                 pos: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, include: str = "valid",
+                 rows: bool = True, next_pos: bool = False) -> PlanReplay:
+    """Replays a batch of plans on the device (``pw_plan_replay_check`` / ``pw_plan_replay_emit``) on the current stream.
+
+    ``puzzle_id`` int32 [n], ``plans`` uint8 [n, plan_cap] and ``plan_len`` int32 [n] in the formats ``PlanBatch.run`` /
+    ``StatePlanner.plan`` leave on the device; ``pos`` int8 [n, NP, 2] start states (None: the puzzles' initial states);
+    ``mask`` 0 skips an item.  Every item gets the reference's ``is_valid_plan`` verdict (``REPLAY_VERDICT``); every step of
+    every included plan -- ``include`` "valid": the valid ones, "replayed": also those that miss the goal or reach it early --
+    becomes one row of the returned ``PlanReplay``.  ``offset[n]`` is read back once to size the rows: the call's only wait.
+    ``rows=False``: verdicts only, no wait."""
+    engine = engine_or_vec if isinstance(engine_or_vec, _capi.Engine) else getattr(engine_or_vec, "engine", None)
+    if not isinstance(engine, _capi.Engine):
+        raise ValueError("engine_or_vec must be a VecPushWorld or an _capi.Engine")
+    if include not in REPLAY_INCLUDE:
+        raise ValueError("include must be 'valid' or 'replayed'")
+    dev, npad = engine.device, int(engine.np)
+    n = _replay_inputs(puzzle_id, plans, plan_len, pos, mask, npad, dev)
+    inc = REPLAY_INCLUDE[include]
+    out = PlanReplay()
+    out.verdict = torch.empty((n,), dtype=torch.int8, device=dev)
+    out.first_goal = torch.empty((n,), dtype=torch.int32, device=dev)
+    out.final_pos = torch.empty((n, npad, 2), dtype=torch.int8, device=dev)
+    out.offset = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    engine.plan_replay_check(puzzle_id, pos, plans, plan_len, mask, inc, out.verdict, out.first_goal, out.final_pos, out.offset)
+    if not rows:
+        return out
+    T = out.num_rows = int(out.offset[n].item())
+    out.item = torch.empty((T,), dtype=torch.int32, device=dev)
+    out.t = torch.empty((T,), dtype=torch.int32, device=dev)
+    out.puzzle_id = torch.empty((T,), dtype=torch.int32, device=dev)
+    out.pos = torch.empty((T, npad, 2), dtype=torch.int8, device=dev)
+    out.action = torch.empty((T,), dtype=torch.uint8, device=dev)
+    out.reward = torch.empty((T,), dtype=torch.float64, device=dev)
+    out.done = torch.empty((T,), dtype=torch.uint8, device=dev)
+    if next_pos:
+        out.next_pos = torch.empty((T, npad, 2), dtype=torch.int8, device=dev)
+    if T > 0:
+        engine.plan_replay_emit(puzzle_id, pos, plans, plan_len, mask, inc, out.verdict, out.offset, T, out.item, out.t,
+                                out.puzzle_id, out.pos, out.action, out.reward, out.done, out.next_pos)
+    return out
+

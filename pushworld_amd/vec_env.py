@@ -359,6 +359,48 @@ class VecPushWorld:
             mask = mask.to(device=self.device, dtype=torch.uint8)
         return planner.plan(self.puzzle_id, self.pos, mask=mask, plan_cap=0, **run_kw)[3]
 
+    def demonstrations(self, planner, observation: Optional[str] = "own", include: str = "valid",
+                       mask: Optional[torch.Tensor] = None, plan_cap: int = 1024, **run_kw):
+        """A flat demonstration dataset from every environment's current state: ``planner`` plans from the live states, the
+        plans are replayed on the device (``search.replay_plans``) and every step of every included plan becomes one row --
+        ``item`` (the environment), ``t``, ``puzzle_id``, ``pos`` (the state before the action), ``action`` (the expert's),
+        ``reward`` and ``done`` as ``step`` would return them, ``next_pos`` -- plus ``obs``, the observation of ``pos``:
+        uint8 [T, 3, Hc, Wc] for "cells", [T, H, W, 3] uint8 / float32 for the RGB kind this environment was made with
+        (the engine renders one pixel format), None for ``observation=None``.  The default is the environment's own kind.
+        ``include``: "valid" keeps the plans that solve their puzzle, "replayed" also the others that were replayed.
+        The rows are rendered by ONE ``pw_render`` / ``pw_render_cells`` launch over all T of them.  Everything is queued on
+        the current stream behind whatever is there (e.g. ``step``); the call waits once, for the number of rows.  The
+        environment's own ``pos``, ``steps`` and ``obs`` are not touched.  ``run_kw``: ``max_rounds``, ``time_limit`` of
+        ``StatePlanner.plan``.  Returns a ``search.PlanReplay``."""
+        from .search import replay_plans
+
+        if planner.engine is not self.engine:
+            raise ValueError("the planner must be made on this environment (VecPushWorld.planner)")
+        if observation == "own":
+            observation = self.observation
+        if observation not in ("uint8", "float32", "cells", None):
+            raise ValueError("observation must be 'uint8', 'float32', 'cells' or None")
+        own_rgb = "uint8" if self.engine.obs_dtype == torch.uint8 else "float32"
+        if observation in ("uint8", "float32") and observation != own_rgb:
+            raise ValueError(f"this environment's engine renders {own_rgb} pixels: observation must be '{own_rgb}', 'cells' or None")
+        if int(plan_cap) < 1:
+            raise ValueError("plan_cap must be >= 1")
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        _, plans, plan_len, _ = planner.plan(self.puzzle_id, self.pos, mask=mask, plan_cap=int(plan_cap), **run_kw)
+        out = replay_plans(self.engine, self.puzzle_id, plans, plan_len, pos=self.pos, mask=mask, include=include,
+                           next_pos=True)
+        T = out.num_rows
+        if observation == "cells":
+            out.obs = torch.empty((T,) + self.engine.cells_shape(), dtype=torch.uint8, device=self.device)
+            if T > 0:
+                self.engine.render_cells(out.puzzle_id, out.pos, out.obs)
+        elif observation is not None:
+            storage, out.obs = self.engine.alloc_obs(T)
+            if T > 0:
+                self.engine.render(out.puzzle_id, out.pos, storage)
+        return out
+
     def set_states(self, pos: np.ndarray) -> None:
         self.pos.copy_(torch.as_tensor(np.asarray(pos), dtype=torch.int8))
         self._has_reset = True
