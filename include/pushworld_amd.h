@@ -698,6 +698,42 @@ int pw_search_read_flags(PwSearch* s, int64_t first, int64_t count, uint8_t* pru
  * is written: call again with a larger buffer) or a negative error. */
 int pw_search_plan(PwSearch* s, int64_t index, uint8_t* actions, int32_t cap, void* stream);
 
+/* Exact cost-to-go table over an EXHAUSTED breadth-first search (novelty_width 0, the last pw_search_expand reported 0 new
+ * states, the store did not overflow; anything else: PW_EINVAL naming the condition).  One row per state of the store:
+ *   succ  int32 [total][4]  store index of the successor under L, R, U, D; the state's own index where the action moves nothing
+ *   cost  uint16 [total]    length of a shortest action sequence to a goal state: 0 at every goal state (whatever lies beyond
+ *                           it), 0xFFFF where no goal state can be reached (a dead end: PushWorld is irreversible)
+ *   acts  uint8 [total]     bit a (0..3): action a is optimal -- succ[i][a] != i and cost[succ[i][a]] == cost[i] - 1 (none at goal
+ *                           states and dead ends); bit 4 + a: action a is safe -- cost[succ[i][a]] is finite (an action that
+ *                           moves nothing out of a solvable state is safe)
+ * pw_search_solve is synchronous: a successor pass (the store expanded again, every successor looked up in the closed set --
+ * exactly, with either entry form of PW_OPT_SEARCH_KEYS), then level-synchronous backward sweeps from the goal states.
+ *   info[0] states   info[1] goal states   info[2] dead ends   info[3] largest finite cost
+ * PW_ELIMIT when a finite cost reaches 65 535; PW_EDEVICE when a successor is missing from the closed set (an internal error).
+ * Memory: 19 bytes per state of the store as it stands (16 succ + 2 cost + 1 acts; the sweeps work in place), 256 KB of
+ * counters, and with exact keys 4 bytes per slot of the visited table (which state sits in which slot).  pw_search_begin and
+ * pw_search_destroy discard the table. */
+int pw_search_solve(PwSearch* s, int64_t info[4], void* stream);
+/* The last pw_search_solve: device milliseconds of [0] the successor pass, [1] the backward sweeps, [2] the action bits
+ * (-1: not measured); [3] successor passes, [4] how many of them ran the one-lane-per-parent expansion kernel. */
+int pw_search_solve_stats(PwSearch* s, double stats[5]);
+/* rows first .. first + count - 1 into device buffers (any of them may be NULL); asynchronous on `stream` */
+int pw_search_table_read(PwSearch* s, int64_t first, int64_t count, int32_t* succ, uint16_t* cost, uint8_t* acts, void* stream);
+/* Live states -> table rows: ONE launch, asynchronous on `stream`, no allocation, no synchronisation (capturable).
+ *   puzzle_id  device int32 [n], or NULL: every item is of the table's puzzle
+ *   pos        device int8 [n][npad][2], the engine's state layout (pw_plan_batch_run_states'); npad 4 / 8 / 16 / 32
+ *   mask       device uint8 [n] or NULL: 0 skips an item
+ * For every item of the table's puzzle that is not masked out (any output may be NULL):
+ *   index[i]   the store index, -1 when the state is not in the table (not reachable from the search's start, or a
+ *              coordinate outside the grid)
+ *   cost[i]    the cost, -1 for a dead end, -2 when the state is not in the table
+ *   acts[i]    the action bits, 0 when the state is not in the table
+ * Items of other puzzles and masked items are LEFT UNTOUCHED: several tables fill one set of outputs for a mixed batch.
+ * PW_EINVAL before any launch, pw_last_error naming the function: null handle, n < 1, null pos, npad not 4 / 8 / 16 / 32 or
+ * smaller than the puzzle's number of movables, no solved table. */
+int pw_search_table_query(PwSearch* s, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask,
+                          int32_t n, int32_t* index, int32_t* cost, uint8_t* acts, void* stream);
+
 /* Batched search of SMALL puzzles: ONE launch decides solvability for `n` puzzles of the engine's set (the filter of
  * generate.py:262-297 over a generated set; best_first_search.h:45-98 with a FIFO frontier).  Persistent workgroups take
  * puzzles off a device counter and run the whole breadth-first loop inside the kernel -- closed set in LDS (4 096 states)

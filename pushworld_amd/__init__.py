@@ -9,5 +9,15 @@ Drop-in for the hot path of google-deepmind/pushworld (``PushWorldPuzzle.get_nex
     from pushworld_amd.dm_env import PushWorldEnv as DmEnv         # pushworld.dm_env
     from pushworld_amd.vec_env import VecPushWorld                 # batched, new
     from pushworld_amd.vector_env import PushWorldVectorEnv        # gymnasium.vector surface, new
+    from pushworld_amd import SolutionTable                        # search.SolutionTable: exact cost-to-go tables, new
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package must not need the built library (``python -m pushworld_amd.build``)
+    if name == "SolutionTable":
+        from .search import SolutionTable
+
+        return SolutionTable
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

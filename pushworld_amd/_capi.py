@@ -153,6 +153,11 @@ SIGNATURES = {
     "pw_search_read_states": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "pw_search_read_links": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "pw_search_plan": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
+    "pw_search_solve": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
+    "pw_search_solve_stats": (c_int, [c_void_p, POINTER(ctypes.c_double)]),
+    "pw_search_table_read": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_search_table_query": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "pw_step_render_delta": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -280,7 +280,32 @@ struct PwSearch {
   uint8_t* d_pruned;       // [max_states]
   uint32_t* d_cand_moved;  // [4 * chunk] moved-object mask (pushworld_puzzle.cc:446-457)
   uint8_t* d_cand_nov;     // [4 * chunk]
+  // exact cost-to-go table (pw_search_solve, csrc/pw_solution.inc): one row per state of the exhausted store
+  bool exhausted;          // the last pw_search_expand found no new state
+  bool solved;             // the table below is valid
+  int64_t table_states;    // rows
+  int32_t* d_succ;         // [table_states][4] store index of the successor under L, R, U, D (the state itself: nothing moves)
+  uint16_t* d_cost;        // [table_states] length of a shortest way to a goal state, 0xFFFF = none (dead end)
+  uint8_t* d_acts;         // [table_states] bits 0..3 optimal actions, bits 4..7 safe actions
+  uint32_t* d_slot_index;  // [table_slots] exact keys only: store index of the state published in each slot
+  uint32_t* d_solve_counts;  // pw_search_solve's device words (states settled per sweep, then the totals)
+  float solve_ms[3];       // device milliseconds of the last pw_search_solve: successor pass, sweeps, action bits
+  int64_t solve_passes, solve_lane_passes;  // its successor passes, and how many of them ran one lane per parent
 };
+
+// the cost-to-go table goes with the search it was computed from (pw_search_begin, pw_search_destroy)
+static void search_table_discard(PwSearch* s) {
+  void* bufs[] = {s->d_succ, s->d_cost, s->d_acts, s->d_slot_index, s->d_solve_counts};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  s->d_succ = nullptr;
+  s->d_cost = nullptr;
+  s->d_acts = nullptr;
+  s->d_slot_index = nullptr;
+  s->d_solve_counts = nullptr;
+  s->solved = false;
+  s->table_states = 0;
+}
 
 struct SearchArgs {
   const PwPuzzleHeader* hdrs;
@@ -865,6 +890,7 @@ void pw_search_destroy(PwSearch* s) {
                   s->d_cand_moved, s->d_cand_nov};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  search_table_discard(s);
   pw_novelty_destroy(s->nov);
   delete s;
 }
@@ -1002,10 +1028,10 @@ static SearchArgs search_args(PwSearch* s) {
   return a;
 }
 
-// One pass over a.nparents parents: expand, claim, (novelty), count, scan, publish.  lane_ok false keeps the lane-group
-// expand kernels (the planner's parent lists and action groups are theirs only).
-static void search_pass(PwSearch* s, SearchArgs& a, hipStream_t st, bool lane_ok) {
-  const unsigned cblocks = static_cast<unsigned>((a.ncand + 255) / 256);
+// lane_ok false keeps the lane-group expand kernels (the planner's parent lists and action groups are theirs only).
+// The expand launch of a pass (the cost-to-go table's successor pass, csrc/pw_solution.inc, runs it too).  Returns true when
+// it was the one-lane-per-parent kernel.
+static bool search_launch_expand(PwSearch* s, SearchArgs& a, hipStream_t st, bool lane_ok) {
   const bool tab = !s->eng->ovl_has.empty() && s->eng->ovl_has[static_cast<size_t>(s->puzzle)];  // overlap tables
   // One lane per parent (pw_search_expand_lane_kernel) for passes that fill the chip by themselves: puzzles with push
   // tables; PW_OPT_STEP_KERNEL lane forces it, PW_OPT_STEP_LANE_BATCH moves the threshold.
@@ -1025,6 +1051,7 @@ static void search_pass(PwSearch* s, SearchArgs& a, hipStream_t st, bool lane_ok
     else if (s->N <= 8) hipLaunchKernelGGL(pw_search_expand_lane_kernel<8>, grid, wave, lds, st, a, hash_pad, per_pass, width);
     else if (s->N <= 16) hipLaunchKernelGGL(pw_search_expand_lane_kernel<16>, grid, wave, lds, st, a, hash_pad, per_pass, width);
     else hipLaunchKernelGGL(pw_search_expand_lane_kernel<32>, grid, wave, lds, st, a, hash_pad, per_pass, width);
+    return true;
   } else if (s->gs == 8) {
     if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<8, true>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((pw_search_expand_kernel<8, false>), dim3((a.nparents + 31) / 32), dim3(256), 0, st, a);
@@ -1038,6 +1065,13 @@ static void search_pass(PwSearch* s, SearchArgs& a, hipStream_t st, bool lane_ok
     if (tab) hipLaunchKernelGGL((pw_search_expand_kernel<32, true>), dim3((a.nparents + 7) / 8), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((pw_search_expand_kernel<32, false>), dim3((a.nparents + 7) / 8), dim3(256), 0, st, a);
   }
+  return false;
+}
+
+// One pass over a.nparents parents: expand, claim, (novelty), count, scan, publish.
+static void search_pass(PwSearch* s, SearchArgs& a, hipStream_t st, bool lane_ok) {
+  const unsigned cblocks = static_cast<unsigned>((a.ncand + 255) / 256);
+  (void)search_launch_expand(s, a, st, lane_ok);
   if (a.key_bx) hipLaunchKernelGGL(pw_search_claim_kernel<true>, dim3(cblocks), dim3(256), 0, st, a, s->N);
   else hipLaunchKernelGGL(pw_search_claim_kernel<false>, dim3(cblocks), dim3(256), 0, st, a, s->N);
   if (s->nov) {  // width-limited search, or the planner's N+RGD mode
@@ -1058,6 +1092,8 @@ int pw_search_begin(PwSearch* s, const int32_t* start, void* stream) try {
   if (!s) return pw_fail(PW_EINVAL, "null search");
   PwDeviceGuard guard(s->eng->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  search_table_discard(s);  // a cost-to-go table belongs to the search it was computed from
+  s->exhausted = false;
   const PwPuzzleHeader& h = s->eng->set->headers[s->puzzle];
   alignas(8) uint16_t packed[PW_MAX_OBJECTS + 2] = {0};
   bool goal = true;
@@ -1156,6 +1192,7 @@ int pw_search_expand(PwSearch* s, int64_t info_out[4], void* stream) try {
   s->depth += 1;
   if (s->goal_index < 0 && info[1] != ~0ull) s->goal_index = static_cast<int64_t>(info[1]);
   s->overflow = info[2] != 0ull;
+  s->exhausted = !s->overflow && s->layer_end == s->layer_begin;
   info_out[0] = s->depth;
   info_out[1] = s->layer_end - s->layer_begin;
   info_out[2] = total;

@@ -730,6 +730,152 @@ class StatePlanner:
     __del__ = close
 
 
+# ---- exact cost-to-go tables (pw_search_solve / pw_search_table_query) ------------------------------------------
+COST_DEAD_END, COST_UNKNOWN = -1, -2  # ``SolutionTable.query``'s cost of a dead end / of a state that is not in the table
+TABLE_DEAD_END = 0xFFFF               # the same in the table's own uint16 costs
+
+
+class SolutionTable:
+    """The exact cost-to-go of EVERY state reachable in one puzzle: a ``BreadthFirstSearch`` run to exhaustion, then
+    ``pw_search_solve``'s backward propagation from the goal states.  Row i belongs to state i of the search (the FIFO
+    numbering of ``states()``):
+
+    * ``successors()`` int32 [count, 4]: the index of the state each action (L, R, U, D) leads to, i itself where nothing moves;
+    * ``costs()`` uint16 [count]: the length of a shortest plan from the state, 0 at goal states, 0xFFFF at dead ends --
+      states from which no goal state can be reached any more (PushWorld is irreversible);
+    * ``actions()`` uint8 [count]: bit a = action a is optimal (it moves and its successor costs one less; none at goal
+      states and dead ends), bit 4 + a = action a is safe (its successor is no dead end).
+
+    Args:
+        puzzle: a ``PushWorldPuzzle`` or a ``SetPuzzle``.
+        max_states: capacity of the search; ``ValueError`` ("the state store is full") when the space is larger.
+        start: the state the space is explored from (default: the initial state).
+        chunk: parents per pass, as ``BreadthFirstSearch``.
+
+    Device memory: the search's, plus 19 bytes per state found.
+    """
+
+    def __init__(self, puzzle, max_states: int = 1 << 22, start: Optional[Sequence[Tuple[int, int]]] = None,
+                 chunk: Optional[int] = None):
+        self.puzzle = puzzle
+        self.puzzle_index = int(getattr(puzzle, "puzzle_index", 0))
+        self.search = BreadthFirstSearch(puzzle, max_states=max_states, chunk=chunk)
+        self.device = self.search.device
+        self.npad = int(self.search._engine.np)
+        self._host = None  # (acts, succ, cost) on the host, fetched by the first optimal_plan
+        try:
+            self.search.begin(start)
+            while not self.search.exhausted:
+                self.search.expand()
+            info = (ctypes.c_int64 * 4)()
+            _capi.check(_capi.lib.pw_search_solve(self.search.handle, info, self.search._stream()))
+            self.num_states, self.num_goal_states, self.num_dead_ends, self.max_cost = (int(v) for v in info)
+            st = (ctypes.c_double * 5)()
+            _capi.check(_capi.lib.pw_search_solve_stats(self.search.handle, st))
+            self.solve_ms = tuple(float(v) for v in st[:3])  # device ms: successor pass, backward sweeps, action bits
+            self.solve_passes, self.solve_lane_passes = int(st[3]), int(st[4])  # successor passes / one lane per parent
+            c0 = int(self.costs(0, 1).cpu().numpy()[0])
+            self.initial_cost = None if c0 == TABLE_DEAD_END else c0
+        except Exception:
+            self.search.close()
+            raise
+
+    def _read(self, which: int, first: int, count: Optional[int]) -> torch.Tensor:
+        count = self.num_states - first if count is None else count
+        shape, dtype = (((count, 4), torch.int32), ((count,), torch.uint16), ((count,), torch.uint8))[which]
+        out = torch.empty(shape if count >= 0 else (0,), dtype=dtype, device=self.device)
+        ptrs = [None, None, None]
+        ptrs[which] = _capi._ptr(out)
+        _capi.check(_capi.lib.pw_search_table_read(self.search.handle, int(first), int(count), *ptrs, self.search._stream()))
+        return out
+
+    def successors(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """int32 [count, 4] on the device: successor indices of states ``first .. first + count - 1``."""
+        return self._read(0, first, count)
+
+    def costs(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """uint16 [count] on the device: cost-to-go, 0xFFFF = dead end."""
+        return self._read(1, first, count)
+
+    def actions(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """uint8 [count] on the device: optimal (bits 0..3) and safe (bits 4..7) actions."""
+        return self._read(2, first, count)
+
+    def states(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """``BreadthFirstSearch.states``: int array [count, N, 2] of (x, y) positions."""
+        return self.search.states(first, count)
+
+    def plan(self, index: int) -> List[int]:
+        """``BreadthFirstSearch.plan``: actions from the start state to state ``index``."""
+        return self.search.plan(index)
+
+    def optimal_plan(self, index: int = 0) -> Optional[List[int]]:
+        """A shortest plan from state ``index`` to a goal state (at every step the lowest optimal action), [] at a goal
+        state, None for a dead end."""
+        if not 0 <= int(index) < self.num_states:
+            raise ValueError("state index out of bounds")
+        if self._host is None:
+            self._host = (self.actions().cpu().numpy(), self.successors().cpu().numpy(), self.costs().cpu().numpy())
+        acts, succ, cost = self._host
+        i = int(index)
+        if cost[i] == TABLE_DEAD_END:
+            return None
+        plan = []
+        while cost[i] != 0:
+            a = int(acts[i] & 15)
+            a = (a & -a).bit_length() - 1
+            plan.append(a)
+            i = int(succ[i, a])
+        return plan
+
+    def query(self, puzzle_id: Optional[torch.Tensor], pos: torch.Tensor, mask: Optional[torch.Tensor] = None, out=None):
+        """Looks states up on the device, one launch on the current stream, no wait: ``pos`` int8 [n, NP, 2] (the engine's
+        layout, e.g. ``VecPushWorld.pos``), ``puzzle_id`` int32 [n] (None: every item is this table's puzzle), ``mask`` uint8 /
+        bool [n] (0 skips an item).  Returns device tensors ``(index int32 [n], cost int32 [n], acts uint8 [n])``: the row of
+        each state, its cost (``COST_DEAD_END`` -1 for a dead end) and its action bits; a state that is not in the table
+        (not reachable from the start, or outside the grid) gives -1 / ``COST_UNKNOWN`` -2 / 0.  Items of other puzzles and
+        masked items keep what ``out`` -- the triple of an earlier call, filled in place -- held; without ``out`` they are
+        -1 / -2 / 0 too."""
+        if puzzle_id is None:  # the kernel takes NULL: no id array is made up
+            if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int8 or pos.dim() != 3 or \
+                    tuple(pos.shape[1:]) != (self.npad, 2) or not 1 <= pos.shape[0] < 1 << 31:
+                raise ValueError(f"pos must be an int8 tensor [n, {self.npad}, 2] (the engine's state layout), n >= 1")
+            n = int(pos.shape[0])
+            if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool)
+                                     or tuple(mask.shape) != (n,)):
+                raise ValueError("mask must be a uint8 or bool tensor [n] (or None)")
+            for name, t in (("pos", pos), ("mask", mask)):
+                if t is not None and t.device != self.device:
+                    raise ValueError(f"{name} must live on {self.device}")
+                if t is not None and not t.is_contiguous():
+                    raise ValueError(f"{name} must be contiguous")
+        else:
+            n = _state_inputs(puzzle_id, pos, mask, self.npad, self.device)
+        if out is None:
+            out = (torch.full((n,), -1, dtype=torch.int32, device=self.device),
+                   torch.full((n,), COST_UNKNOWN, dtype=torch.int32, device=self.device),
+                   torch.zeros((n,), dtype=torch.uint8, device=self.device))
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("out must be the (index, cost, acts) triple of an earlier query")
+            for name, t, dtype in (("index", out[0], torch.int32), ("cost", out[1], torch.int32), ("acts", out[2], torch.uint8)):
+                if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,) or t.device != self.device \
+                        or not t.is_contiguous():
+                    raise ValueError(f"out: {name} must be a contiguous {dtype} tensor [n] on {self.device}")
+            out = tuple(out)
+        _capi.check(_capi.lib.pw_search_table_query(self.search.handle, _capi._ptr(puzzle_id), _capi._ptr(pos), self.npad,
+                                                    _capi._ptr(mask), n, _capi._ptr(out[0]), _capi._ptr(out[1]),
+                                                    _capi._ptr(out[2]), self.search._stream()))
+        return out
+
+    def close(self) -> None:
+        search = getattr(self, "search", None)
+        if search is not None:
+            search.close()
+
+    __del__ = close
+
+
 # ---- plan replay (pw_plan_replay_check / pw_plan_replay_emit, DESIGN.md K11) ----------------------------------------------
 REPLAY_VALID, REPLAY_NOT_GOAL, REPLAY_EARLY = _capi.REPLAY_VALID, _capi.REPLAY_NOT_GOAL, _capi.REPLAY_EARLY
 REPLAY_NONE, REPLAY_CUT, REPLAY_SKIPPED = _capi.REPLAY_NONE, _capi.REPLAY_CUT, _capi.REPLAY_SKIPPED

@@ -401,6 +401,31 @@ class VecPushWorld:
                 self.engine.render(out.puzzle_id, out.pos, storage)
         return out
 
+    def solution_table(self, puzzle_index: int, max_states: int = 1 << 22):
+        """A ``search.SolutionTable`` -- the exact cost-to-go, optimal actions and dead ends of every reachable state -- of
+        puzzle ``puzzle_index`` of this batch's set, in the set's object order: query it with ``puzzle_id`` / ``pos`` as they
+        are (``cost_to_go``).  Explores the puzzle's whole reachable space: ``ValueError`` beyond ``max_states``."""
+        from .search import SetPuzzle, SolutionTable
+
+        if not 0 <= int(puzzle_index) < self.num_puzzles:
+            raise ValueError(f"puzzle_index must be an index into the set (0 .. {self.num_puzzles - 1})")
+        return SolutionTable(SetPuzzle(self.pset, int(puzzle_index), engine=self.engine), max_states=max_states)
+
+    def cost_to_go(self, tables):
+        """``(index int32 [B], cost int32 [B], acts uint8 [B])`` on the device for every environment's current state, from
+        a list of ``solution_table``s (one ``SolutionTable.query`` launch each on the current stream, no wait): the cost is
+        -1 at a dead end; environments whose puzzle has no table in the list keep -1 / -2 / 0."""
+        from .search import COST_UNKNOWN
+
+        out = (torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device),
+               torch.full((self.num_envs,), COST_UNKNOWN, dtype=torch.int32, device=self.device),
+               torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device))
+        for table in tables:
+            if table.search._engine is not self.engine:
+                raise ValueError("the tables must be made on this environment (VecPushWorld.solution_table)")
+            table.query(self.puzzle_id, self.pos, out=out)
+        return out
+
     def set_states(self, pos: np.ndarray) -> None:
         self.pos.copy_(torch.as_tensor(np.asarray(pos), dtype=torch.int8))
         self._has_reset = True
