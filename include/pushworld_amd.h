@@ -753,6 +753,58 @@ int pw_search_table_query(PwSearch* s, const int32_t* puzzle_id, const int8_t* p
 int pw_search_batch(PwEngine* e, const int32_t* puzzles, int32_t n, int64_t max_states_each, int32_t novelty_width,
                     uint8_t* verdict, int32_t* plan_len, int32_t* num_states, uint8_t* plans, int32_t plan_cap, void* stream);
 
+/* Exact cost-to-go tables (pw_search_solve's rows: succ, cost, acts, same definitions) of MANY small puzzles in ONE launch,
+ * in the form of pw_search_batch: persistent workgroups take puzzles off a device counter and do the exhaustive
+ * breadth-first search, the successor pass, the backward sweeps (a barrier each, not a launch each) and the action bits of
+ * a puzzle inside the kernel.  Same limits as pw_search_batch (16 x 16 cells with the border, 8 movables, overlap tables).
+ *
+ * pw_solve_batch_create: rows_cap >= 0 rows of pool for the tables of all items together (0: summaries only).
+ * pw_solve_batch_run: `puzzles` device int32 [n] set indices or NULL = 0 .. n - 1, n >= 1; asynchronous on `stream` except
+ *   when the engine's slabs or the handle's per-item arrays have to grow (first call, larger n or max_states_each).
+ * Per item, in device arrays owned by the handle (pw_solve_batch_results; valid until the next run or the destroy):
+ *   status   uint8      0 table built and stored   2 more than max_states_each states   3 not searched (beyond the limits)
+ *                       4 built, but the row pool was full: the summary is valid, the rows are not stored
+ *                       5 a finite cost reached 65 535   6 a successor was missing from the exhausted closed set (internal)
+ *   summary  int32 [5]  states, goal states, dead ends, largest finite cost, cost of the start state (-1: a dead end);
+ *                       valid for status 0 and 4 (else: states found so far, then 0 0 0 -1)
+ *   row_off  int64      first row of the item's table in the pool, -1 when it is not stored
+ * A workgroup reserves the rows of a finished table with one atomicAdd, so WHICH offset an item gets -- and the numbering
+ * of the states inside one breadth-first layer, hence which row a state has -- depends on the schedule and may differ from
+ * run to run.  Everything else does not: row 0 is the start state, rows are found by state (key / pw_solve_batch_query),
+ * succ holds row numbers within the item's table.  An item that did not fit leaves its reservation unused.
+ * pw_solve_batch_totals (synchronises `stream`): [0] the rows a pool needs to store every built table of the run (size a
+ *   second handle with it), [1] lookup slots in use, [2] missing successors (0).
+ * pw_solve_batch_read: rows first .. first + count - 1 of a stored item into device buffers (any may be NULL):
+ *   key   uint64     the state: movable j at bits 8 j (x in the low nibble, y in the high one), zeros beyond the puzzle's N
+ *   succ  int32 [4]  cost  uint16  acts  uint8   as pw_search_table_read
+ *   The first read after a run fetches the item offsets (synchronises `stream` once); asynchronous afterwards.
+ * pw_solve_batch_query: live states of a MIXED batch -> rows, ONE launch, no allocation, no synchronisation (capturable).
+ *   puzzle_id device int32 [n] (required), pos device int8 [n][npad][2] (npad 4 / 8 / 16 / 32; only the first N movables of a
+ *   row are read into the key), mask device uint8 [n] or NULL.  Outputs and conventions are pw_search_table_query's: index
+ *   (row within the item's table) -1 / cost -2 / acts 0 for a state that is not in the table (or has a coordinate outside
+ *   0 .. 15 or the grid), cost -1 at a dead end.  Masked items and items whose puzzle has no STORED table in this handle
+ *   (status other than 0, not in `puzzles`, id outside the set) are LEFT UNTOUCHED, so per-puzzle tables fill the same outputs.
+ *   A puzzle listed twice is answered from its higher item.
+ * Every argument check returns PW_EINVAL before any launch and names the function (null handle, n < 1, null puzzle_id / pos,
+ * npad, rows_cap < 0, no run yet).
+ * Memory: 27 bytes per row of pool (8 key + 16 succ + 2 cost + 1 acts) and 4 bytes per lookup slot -- a power of two
+ * >= 2 x states (at least 16) slots per stored item, reserved as 4 slots per row + 16 per item: at most 43 bytes per row
+ * of rows_cap; 37 bytes per item; 4 bytes per puzzle of the set.  The engine's slabs (shared with pw_search_batch): per
+ * persistent workgroup 26 bytes per state of max_states_each + 12 bytes per slot of the 2^16 / 2^20 / ... closed-set levels. */
+typedef struct PwSolveBatch PwSolveBatch;
+int pw_solve_batch_create(PwEngine* e, int64_t rows_cap, PwSolveBatch** out);
+void pw_solve_batch_destroy(PwSolveBatch* b);
+int pw_solve_batch_run(PwSolveBatch* b, const int32_t* puzzles, int32_t n, int64_t max_states_each, void* stream);
+/* device pointers (any may be NULL); returns the number of items of the last run */
+int pw_solve_batch_results(PwSolveBatch* b, const uint8_t** status, const int32_t** summary, const int64_t** row_off);
+/* the same arrays copied into the caller's device buffers [n], [n][5], [n] (any may be NULL), asynchronous on `stream` */
+int pw_solve_batch_copy_results(PwSolveBatch* b, uint8_t* status, int32_t* summary, int64_t* row_off, void* stream);
+int pw_solve_batch_totals(PwSolveBatch* b, int64_t totals[3], void* stream);
+int pw_solve_batch_read(PwSolveBatch* b, int32_t item, int64_t first, int64_t count, uint64_t* key, int32_t* succ,
+                        uint16_t* cost, uint8_t* acts, void* stream);
+int pw_solve_batch_query(PwSolveBatch* b, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask,
+                         int32_t n, int32_t* index, int32_t* cost, uint8_t* acts, void* stream);
+
 /* ---------------------------------------------------------- recursive graph distance (RGD) heuristic
  * RecursiveGraphDistanceHeuristic::estimate_cost_to_goal (cpp/src/heuristics/recursive_graph_distance.cc:43-252) for a
  * whole array of states of ONE puzzle of an engine's set.

@@ -10,6 +10,7 @@ Drop-in for the hot path of google-deepmind/pushworld (``PushWorldPuzzle.get_nex
     from pushworld_amd.vec_env import VecPushWorld                 # batched, new
     from pushworld_amd.vector_env import PushWorldVectorEnv        # gymnasium.vector surface, new
     from pushworld_amd import SolutionTable                        # search.SolutionTable: exact cost-to-go tables, new
+    from pushworld_amd import SolutionTableBatch                   # ... of many small puzzles in one launch, new
 """
 __version__ = "0.1.0"
 
@@ -20,4 +21,8 @@ def __getattr__(name):
         from .search import SolutionTable
 
         return SolutionTable
+    if name == "SolutionTableBatch":
+        from .search import SolutionTableBatch
+
+        return SolutionTableBatch
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

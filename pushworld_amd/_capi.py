@@ -183,6 +183,15 @@ SIGNATURES = {
     "pw_obs_free": (c_int, [c_void_p, c_void_p]),
     "pw_search_batch": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                 c_void_p]),
+    "pw_solve_batch_create": (c_int, [c_void_p, c_int64, POINTER(c_void_p)]),
+    "pw_solve_batch_destroy": (None, [c_void_p]),
+    "pw_solve_batch_run": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
+    "pw_solve_batch_results": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
+    "pw_solve_batch_copy_results": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_solve_batch_totals": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
+    "pw_solve_batch_read": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_solve_batch_query": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
     "pw_counters": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
     "pw_counters_reset": (c_int, [c_void_p, c_void_p]),
     "pw_next_state": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),

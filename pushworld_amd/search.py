@@ -735,6 +735,21 @@ COST_DEAD_END, COST_UNKNOWN = -1, -2  # ``SolutionTable.query``'s cost of a dead
 TABLE_DEAD_END = 0xFFFF               # the same in the table's own uint16 costs
 
 
+def _query_outputs(out, n: int, device):
+    """The ``(index, cost, acts)`` triple a table query fills: fresh (-1 / ``COST_UNKNOWN`` / 0) or the checked ``out``."""
+    if out is None:
+        return (torch.full((n,), -1, dtype=torch.int32, device=device),
+                torch.full((n,), COST_UNKNOWN, dtype=torch.int32, device=device),
+                torch.zeros((n,), dtype=torch.uint8, device=device))
+    if not isinstance(out, (tuple, list)) or len(out) != 3:
+        raise ValueError("out must be the (index, cost, acts) triple of an earlier query")
+    for name, t, dtype in (("index", out[0], torch.int32), ("cost", out[1], torch.int32), ("acts", out[2], torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,) or t.device != device \
+                or not t.is_contiguous():
+            raise ValueError(f"out: {name} must be a contiguous {dtype} tensor [n] on {device}")
+    return tuple(out)
+
+
 class SolutionTable:
     """The exact cost-to-go of EVERY state reachable in one puzzle: a ``BreadthFirstSearch`` run to exhaustion, then
     ``pw_search_solve``'s backward propagation from the goal states.  Row i belongs to state i of the search (the FIFO
@@ -851,18 +866,7 @@ class SolutionTable:
                     raise ValueError(f"{name} must be contiguous")
         else:
             n = _state_inputs(puzzle_id, pos, mask, self.npad, self.device)
-        if out is None:
-            out = (torch.full((n,), -1, dtype=torch.int32, device=self.device),
-                   torch.full((n,), COST_UNKNOWN, dtype=torch.int32, device=self.device),
-                   torch.zeros((n,), dtype=torch.uint8, device=self.device))
-        else:
-            if not isinstance(out, (tuple, list)) or len(out) != 3:
-                raise ValueError("out must be the (index, cost, acts) triple of an earlier query")
-            for name, t, dtype in (("index", out[0], torch.int32), ("cost", out[1], torch.int32), ("acts", out[2], torch.uint8)):
-                if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,) or t.device != self.device \
-                        or not t.is_contiguous():
-                    raise ValueError(f"out: {name} must be a contiguous {dtype} tensor [n] on {self.device}")
-            out = tuple(out)
+        out = _query_outputs(out, n, self.device)
         _capi.check(_capi.lib.pw_search_table_query(self.search.handle, _capi._ptr(puzzle_id), _capi._ptr(pos), self.npad,
                                                     _capi._ptr(mask), n, _capi._ptr(out[0]), _capi._ptr(out[1]),
                                                     _capi._ptr(out[2]), self.search._stream()))
@@ -872,6 +876,169 @@ class SolutionTable:
         search = getattr(self, "search", None)
         if search is not None:
             search.close()
+
+    __del__ = close
+
+
+# ---- cost-to-go tables of many small puzzles in one launch (pw_solve_batch_*) -----------------------------------
+TABLE_BUILT, TABLE_TOO_MANY, TABLE_NOT_SEARCHED, TABLE_SUMMARY_ONLY, TABLE_COST_RANGE, TABLE_INTERNAL = 0, 2, 3, 4, 5, 6
+
+
+class SolutionTableBatch:
+    """``SolutionTable``'s rows for MANY small puzzles of one set, built by ONE launch (``pw_solve_batch_run``: persistent
+    workgroups, the breadth-first search, the successor pass and the backward sweeps of a puzzle inside the kernel) and
+    queried for a mixed batch by one launch.  The kernel's limits are ``search_batch``'s: 16 x 16 cells with the border,
+    8 movables; bigger puzzles (status 3) and bigger spaces (status 2) are ``SolutionTable``'s.
+
+    Args:
+        source: a ``VecPushWorld`` or an ``_capi.Engine``: the tables are of its puzzle set, in its object order.
+        puzzles: set indices (item i is puzzle ``puzzles[i]``); None: every puzzle of the set.
+        max_states_each: state cap per puzzle.
+        rows: rows of the pool that holds the tables of all items together.  None: one summary-only pass sizes it, a
+            second pass stores (nothing is left out); 0: summaries only.
+
+    Device tensors, one entry per item: ``status`` uint8 (0 table stored, 2 more than ``max_states_each`` states, 3 not
+    searched, 4 built but the pool was full -- summary only, 5 a cost beyond 65 534, 6 internal error), ``num_states``,
+    ``num_goals``, ``dead_ends``, ``max_cost``, ``start_cost`` int32 (valid for status 0 and 4; ``start_cost`` -1: the start
+    state is a dead end), ``row_offset`` int64 (-1: not stored).  ``rows_needed``: the pool that stores every built table.
+
+    Row numbers inside one breadth-first layer, and which pool offset an item gets, depend on the schedule of the launch;
+    row 0 is the start state, and everything is found by state (``states(i)`` / ``query``), never by a number across runs.
+    Device memory: at most 43 bytes per row of the pool, see ``pw_solve_batch_create``.
+    """
+
+    def __init__(self, source, puzzles: Optional[Sequence[int]] = None, max_states_each: int = 1 << 16,
+                 rows: Optional[int] = None):
+        engine = source if isinstance(source, _capi.Engine) else getattr(source, "engine", None)
+        if not isinstance(engine, _capi.Engine):
+            raise ValueError("source must be a VecPushWorld or an _capi.Engine")
+        self.engine, self.device, self.npad = engine, engine.device, int(engine.np)
+        count = len(engine.pset)
+        self.puzzles = list(range(count)) if puzzles is None else [int(p) for p in puzzles]
+        if not self.puzzles:
+            raise ValueError("puzzles must not be empty")
+        if min(self.puzzles) < 0 or max(self.puzzles) >= count:
+            raise ValueError(f"puzzles must be indices into the set (0 .. {count - 1})")
+        if rows is not None and int(rows) < 0:
+            raise ValueError("rows must be >= 0 (or None)")
+        self.max_states_each = int(max_states_each)
+        self.handle = None
+        self._ids = None if puzzles is None else torch.as_tensor(np.asarray(self.puzzles, dtype=np.int32)).to(self.device)
+        self._host = {}  # item -> (acts, succ, cost) on the host, fetched by its first optimal_plan
+        if rows is None:
+            self._run(0)
+            rows = self.rows_needed
+            self.close()
+        self._run(int(rows))
+
+    def _stream(self):
+        return self.engine._stream()
+
+    def _run(self, rows: int) -> None:
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib.pw_solve_batch_create(self.engine.handle, int(rows), ctypes.byref(h)))
+        self.handle = h
+        n = len(self.puzzles)
+        try:
+            _capi.check(_capi.lib.pw_solve_batch_run(h, _capi._ptr(self._ids), n, self.max_states_each, self._stream()))
+            self.status = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            self.summary = torch.empty((n, 5), dtype=torch.int32, device=self.device)
+            self.row_offset = torch.empty((n,), dtype=torch.int64, device=self.device)
+            _capi.check(_capi.lib.pw_solve_batch_copy_results(h, _capi._ptr(self.status), _capi._ptr(self.summary),
+                                                              _capi._ptr(self.row_offset), self._stream()))
+            totals = (ctypes.c_int64 * 3)()
+            _capi.check(_capi.lib.pw_solve_batch_totals(h, totals, self._stream()))
+        except Exception:
+            self.close()
+            raise
+        self.rows, self.rows_needed = int(rows), int(totals[0])
+        self.num_states, self.num_goals, self.dead_ends, self.max_cost, self.start_cost = self.summary.unbind(1)
+        self._counts = None
+
+    def __len__(self) -> int:
+        return len(self.puzzles)
+
+    def _item(self, item: int) -> Tuple[int, int]:
+        """(item, its number of states); ``ValueError`` for an item without stored rows."""
+        if not 0 <= int(item) < len(self.puzzles):
+            raise ValueError("item out of bounds")
+        if self._counts is None:
+            self._counts = (self.status.cpu().numpy(), self.summary[:, 0].cpu().numpy())
+        if self._counts[0][int(item)] != TABLE_BUILT:
+            raise ValueError(f"item {int(item)} has no stored table (status {int(self._counts[0][int(item)])})")
+        return int(item), int(self._counts[1][int(item)])
+
+    def _read(self, which: int, item: int) -> torch.Tensor:
+        item, count = self._item(item)
+        shape, dtype = (((count,), torch.int64), ((count, 4), torch.int32), ((count,), torch.uint16),
+                        ((count,), torch.uint8))[which]
+        out = torch.empty(shape, dtype=dtype, device=self.device)
+        ptrs = [None, None, None, None]
+        ptrs[which] = _capi._ptr(out)
+        _capi.check(_capi.lib.pw_solve_batch_read(self.handle, item, 0, count, *ptrs, self._stream()))
+        return out
+
+    def keys(self, item: int) -> torch.Tensor:
+        """int64 [count] on the device: the state word of every row (movable j at bits 8 j: x | y << 4)."""
+        return self._read(0, item)
+
+    def states(self, item: int) -> np.ndarray:
+        """int array [count, N, 2] of (x, y) positions, row by row (``SolutionTable.states``)."""
+        keys = self.keys(item).cpu().numpy().astype(np.uint64)
+        n_mov = self.engine.pset.headers()[320 * self.puzzles[int(item)] + 6]
+        shifts = (np.arange(n_mov, dtype=np.uint64) * np.uint64(8))[None, :]
+        byte = (keys[:, None] >> shifts) & np.uint64(0xFF)
+        return np.stack([byte & np.uint64(15), byte >> np.uint64(4)], axis=-1).astype(np.int64)
+
+    def successors(self, item: int) -> torch.Tensor:
+        """int32 [count, 4] on the device: the row each action (L, R, U, D) leads to, the row itself where nothing moves."""
+        return self._read(1, item)
+
+    def costs(self, item: int) -> torch.Tensor:
+        """uint16 [count] on the device: cost-to-go, 0xFFFF = dead end."""
+        return self._read(2, item)
+
+    def actions(self, item: int) -> torch.Tensor:
+        """uint8 [count] on the device: optimal (bits 0..3) and safe (bits 4..7) actions."""
+        return self._read(3, item)
+
+    def optimal_plan(self, item: int, index: int = 0) -> Optional[List[int]]:
+        """A shortest plan from row ``index`` of item ``item`` (row 0: the initial state) to a goal state, at every step the
+        lowest optimal action; [] at a goal state, None for a dead end."""
+        item, count = self._item(item)
+        if not 0 <= int(index) < count:
+            raise ValueError("state index out of bounds")
+        if item not in self._host:
+            self._host[item] = (self.actions(item).cpu().numpy(), self.successors(item).cpu().numpy(),
+                                self.costs(item).cpu().numpy())
+        acts, succ, cost = self._host[item]
+        i = int(index)
+        if cost[i] == TABLE_DEAD_END:
+            return None
+        plan = []
+        while cost[i] != 0:
+            a = int(acts[i] & 15)
+            a = (a & -a).bit_length() - 1
+            plan.append(a)
+            i = int(succ[i, a])
+        return plan
+
+    def query(self, puzzle_id: torch.Tensor, pos: torch.Tensor, mask: Optional[torch.Tensor] = None, out=None):
+        """``SolutionTable.query`` for a mixed batch, one launch on the current stream, no wait: ``puzzle_id`` int32 [n],
+        ``pos`` int8 [n, NP, 2], ``mask`` uint8 / bool [n].  Returns ``(index, cost, acts)``; ``index`` is the row within the
+        puzzle's table.  Items whose puzzle has no stored table here and masked items keep what ``out`` held."""
+        n = _state_inputs(puzzle_id, pos, mask, self.npad, self.device)
+        out = _query_outputs(out, n, self.device)
+        _capi.check(_capi.lib.pw_solve_batch_query(self.handle, _capi._ptr(puzzle_id), _capi._ptr(pos), self.npad,
+                                                   _capi._ptr(mask), n, _capi._ptr(out[0]), _capi._ptr(out[1]),
+                                                   _capi._ptr(out[2]), self._stream()))
+        return out
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h is not None and _capi.lib is not None:
+            _capi.lib.pw_solve_batch_destroy(h)
+        self.handle = None
 
     __del__ = close
 

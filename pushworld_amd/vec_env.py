@@ -411,16 +411,29 @@ class VecPushWorld:
             raise ValueError(f"puzzle_index must be an index into the set (0 .. {self.num_puzzles - 1})")
         return SolutionTable(SetPuzzle(self.pset, int(puzzle_index), engine=self.engine), max_states=max_states)
 
+    def solution_tables(self, puzzles=None, **kw):
+        """A ``search.SolutionTableBatch``: the cost-to-go tables of the small puzzles of this batch's set (``puzzles``: set
+        indices, None = all), built in one launch and queried in one (``cost_to_go``).  ``kw``: ``max_states_each``, ``rows``."""
+        from .search import SolutionTableBatch
+
+        return SolutionTableBatch(self, puzzles, **kw)
+
     def cost_to_go(self, tables):
         """``(index int32 [B], cost int32 [B], acts uint8 [B])`` on the device for every environment's current state, from
-        a list of ``solution_table``s (one ``SolutionTable.query`` launch each on the current stream, no wait): the cost is
-        -1 at a dead end; environments whose puzzle has no table in the list keep -1 / -2 / 0."""
-        from .search import COST_UNKNOWN
+        a list of ``solution_table``s (one ``SolutionTable.query`` launch each on the current stream, no wait) and / or
+        ``solution_tables`` batches (one launch for all their puzzles): the cost is -1 at a dead end; environments whose
+        puzzle has no table in the list keep -1 / -2 / 0."""
+        from .search import COST_UNKNOWN, SolutionTableBatch
 
         out = (torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device),
                torch.full((self.num_envs,), COST_UNKNOWN, dtype=torch.int32, device=self.device),
                torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device))
         for table in tables:
+            if isinstance(table, SolutionTableBatch):
+                if table.engine is not self.engine:
+                    raise ValueError("the tables must be made on this environment (VecPushWorld.solution_tables)")
+                table.query(self.puzzle_id, self.pos, out=out)
+                continue
             if table.search._engine is not self.engine:
                 raise ValueError("the tables must be made on this environment (VecPushWorld.solution_table)")
             table.query(self.puzzle_id, self.pos, out=out)
