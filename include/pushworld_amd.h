@@ -805,6 +805,66 @@ int pw_solve_batch_read(PwSolveBatch* b, int32_t item, int64_t first, int64_t co
 int pw_solve_batch_query(PwSolveBatch* b, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask,
                          int32_t n, int32_t* index, int32_t* cost, uint8_t* acts, void* stream);
 
+/* Drawing from the cost-to-go tables on the device (csrc/pw_table_sample.inc): curriculum start states and optimal plans.
+ * Every entry point has a pw_solve_batch_* form (all stored tables of the handle's last run, a MIXED batch, puzzle_id
+ * required) and a pw_search_table_* form (the one table of a solved search; puzzle_id may be NULL = every item is of the
+ * table's puzzle).  Each returns a status; every argument check returns PW_EINVAL before any launch and names the function.
+ *
+ * ..._index: the COST INDEX of every stored table, built on demand, idempotent, discarded by the next pw_solve_batch_run /
+ *   pw_search_begin / destroy.  Per table:
+ *     rows_by_cost  int32 [rows]           a permutation of the table's rows: all rows of cost 0, then cost 1, ... max_cost,
+ *                                          then the dead ends (0xFFFF) as the last bucket
+ *     cost_start    uint32 [max_cost + 3]  bucket c is [cost_start[c], cost_start[c + 1]); the dead ends are bucket
+ *                                          max_cost + 1; the last entry is the number of rows
+ *   Histogram, scan, scatter with atomics -- three launches for all tables of the handle.  The order INSIDE a bucket is
+ *   whatever the build leaves and may differ from build to build (like pw_solve_batch_run's row numbers); it is fixed once
+ *   built.  The batch form synchronises `stream` once when the run's summaries are not on the host yet (they size the
+ *   arrays); both forms allocate.  Memory: 4 bytes per row (the batch form: per row of rows_cap) plus 4 bytes per bucket
+ *   (max_cost + 3 per stored table), and 8 bytes per item of the batch.
+ * ..._index_read: one table's two arrays copied into caller device buffers (either may be NULL), asynchronous on `stream`.
+ *
+ * ..._sample: ONE launch, no allocation, no synchronisation (capturable); the index must exist.  One start state per
+ *   environment, drawn uniformly from the states of its puzzle whose cost-to-go lies in a band:
+ *     puzzle_id  device int32 [n]            mask  device uint8 [n] or NULL: 0 skips an environment
+ *     counter    device uint32 [n]           draws so far, per environment
+ *     band       lo_n == hi_n == NULL: the scalars lo, hi (0 <= lo <= hi); else device int32 [n] each, hi_n[i] < lo_n[i]
+ *                read as hi_n[i] = lo_n[i]
+ *     pos        device int8 [n][npad][2]    npad 4 / 8 / 16 / 32 (the search form: >= the puzzle's number of movables)
+ *     steps      device int32 [n]            term, trunc  device uint8 [n] or NULL
+ *     out_row, out_cost  device int32 [n]
+ *   Masked environments and environments whose puzzle has no stored, indexed table in the handle are LEFT ENTIRELY UNTOUCHED,
+ *   the counter included (pw_solve_batch_query's convention: several tables fill one batch).  Otherwise the band is clamped to
+ *   [0, max_cost] (lo > max_cost: lo = hi = max_cost; dead ends are never drawn).  A table without a finite-cost row gives
+ *   out_row = out_cost = -1 and leaves everything else untouched.  Else
+ *     counter[i] += 1;  r = mix64(seed ^ PW_TABLE_K_SAMPLE, i, counter[i])   (pw_mix64, K_SAMPLE = 0xA0761D6478BD642F)
+ *     count = cost_start[hi + 1] - cost_start[lo];  u = floor(r * count / 2^64);  row = rows_by_cost[cost_start[lo] + u]
+ *   and the environment is written as pw_reset writes it: the row's state in pos (zeros from the puzzle's N to npad - 1),
+ *   steps = 0, term = trunc = 0; out_row = row, out_cost = its cost.
+ *
+ * ..._plans: ONE launch (capturable): a shortest plan from every given row (the batch form needs no index).
+ *     index      device int32 [n] rows, as the query returns them         tie  0 / 1         plan_cap >= 1
+ *     plans      device uint8 [n][plan_cap]                                plan_len  device int32 [n]
+ *   One thread per item walks acts / succ down to cost 0.  tie 0 takes the lowest optimal action at every step; tie 1 takes,
+ *   at step t, the j-th set bit of acts & 15 with k = popcount(acts & 15) and
+ *     j = floor(mix64(seed ^ PW_TABLE_K_PLAN, i, t) * k / 2^64)              (K_PLAN = 0xE7037ED1A0B428DB)
+ *   plan_len is the row's cost when 0 <= cost <= plan_cap; -1 for index < 0 (or beyond the table), a dead end, or a puzzle
+ *   without a stored table here (plans untouched); -2 when the cost exceeds plan_cap (nothing is written).  Masked items are
+ *   untouched. */
+int pw_solve_batch_index(PwSolveBatch* b, void* stream);
+int pw_solve_batch_index_read(PwSolveBatch* b, int32_t item, int32_t* rows_by_cost, uint32_t* cost_start, void* stream);
+int pw_solve_batch_sample(PwSolveBatch* b, const int32_t* puzzle_id, const uint8_t* mask, int32_t n, int32_t npad, uint64_t seed,
+                          uint32_t* counter, int32_t lo, int32_t hi, const int32_t* lo_n, const int32_t* hi_n, int8_t* pos,
+                          int32_t* steps, uint8_t* term, uint8_t* trunc, int32_t* out_row, int32_t* out_cost, void* stream);
+int pw_solve_batch_plans(PwSolveBatch* b, const int32_t* index, const int32_t* puzzle_id, const uint8_t* mask, int32_t n,
+                         int32_t tie, uint64_t seed, uint8_t* plans, int32_t plan_cap, int32_t* plan_len, void* stream);
+int pw_search_table_index(PwSearch* s, void* stream);
+int pw_search_table_index_read(PwSearch* s, int32_t* rows_by_cost, uint32_t* cost_start, void* stream);
+int pw_search_table_sample(PwSearch* s, const int32_t* puzzle_id, const uint8_t* mask, int32_t n, int32_t npad, uint64_t seed,
+                           uint32_t* counter, int32_t lo, int32_t hi, const int32_t* lo_n, const int32_t* hi_n, int8_t* pos,
+                           int32_t* steps, uint8_t* term, uint8_t* trunc, int32_t* out_row, int32_t* out_cost, void* stream);
+int pw_search_table_plans(PwSearch* s, const int32_t* index, const int32_t* puzzle_id, const uint8_t* mask, int32_t n,
+                          int32_t tie, uint64_t seed, uint8_t* plans, int32_t plan_cap, int32_t* plan_len, void* stream);
+
 /* ---------------------------------------------------------- recursive graph distance (RGD) heuristic
  * RecursiveGraphDistanceHeuristic::estimate_cost_to_goal (cpp/src/heuristics/recursive_graph_distance.cc:43-252) for a
  * whole array of states of ONE puzzle of an engine's set.

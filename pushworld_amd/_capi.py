@@ -192,6 +192,18 @@ SIGNATURES = {
     "pw_solve_batch_read": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_solve_batch_query": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
+    "pw_solve_batch_index": (c_int, [c_void_p, c_void_p]),
+    "pw_solve_batch_index_read": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pw_solve_batch_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_solve_batch_plans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_int32,
+                                     c_void_p, c_void_p]),
+    "pw_search_table_index": (c_int, [c_void_p, c_void_p]),
+    "pw_search_table_index_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_search_table_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_int32, c_int32,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_search_table_plans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_int32,
+                                      c_void_p, c_void_p]),
     "pw_counters": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
     "pw_counters_reset": (c_int, [c_void_p, c_void_p]),
     "pw_next_state": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),

@@ -414,6 +414,7 @@ struct PageRec {
 #include "pw_search.inc"
 #include "pw_solution.inc"
 #include "pw_solution_batch.inc"
+#include "pw_table_sample.inc"
 #include "pw_rgd.inc"
 #include "pw_planner.inc"
 #include "pw_plan_batch.inc"

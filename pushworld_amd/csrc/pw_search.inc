@@ -291,10 +291,24 @@ struct PwSearch {
   uint32_t* d_solve_counts;  // pw_search_solve's device words (states settled per sweep, then the totals)
   float solve_ms[3];       // device milliseconds of the last pw_search_solve: successor pass, sweeps, action bits
   int64_t solve_passes, solve_lane_passes;  // its successor passes, and how many of them ran one lane per parent
+  // cost index of the table (pw_search_table_index, csrc/pw_table_sample.inc)
+  int64_t table_max_cost;  // largest finite cost of the table
+  bool index_valid;
+  int32_t* d_rows_by_cost;  // [table_states] the rows grouped by cost, the dead ends last
+  uint32_t* d_cost_start;   // [table_max_cost + 3]
 };
+
+static void search_index_discard(PwSearch* s) {
+  if (s->d_rows_by_cost) (void)hipFree(s->d_rows_by_cost);
+  if (s->d_cost_start) (void)hipFree(s->d_cost_start);
+  s->d_rows_by_cost = nullptr;
+  s->d_cost_start = nullptr;
+  s->index_valid = false;
+}
 
 // the cost-to-go table goes with the search it was computed from (pw_search_begin, pw_search_destroy)
 static void search_table_discard(PwSearch* s) {
+  search_index_discard(s);
   void* bufs[] = {s->d_succ, s->d_cost, s->d_acts, s->d_slot_index, s->d_solve_counts};
   for (void* b : bufs)
     if (b) (void)hipFree(b);

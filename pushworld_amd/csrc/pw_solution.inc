@@ -349,6 +349,7 @@ int pw_search_solve(PwSearch* s, int64_t info[4], void* stream) try {
   s->solve_lane_passes = lane_passes;
   s->solved = true;
   s->table_states = total;
+  s->table_max_cost = max_cost;
   info[0] = total;
   info[1] = goals;
   info[2] = tail[1];

@@ -466,7 +466,40 @@ struct PwSolveBatch {
   std::vector<uint8_t> h_status;
   std::vector<int32_t> h_summary;
   std::vector<int64_t> h_row_off;
+  // cost index of the last run's stored tables (pw_solve_batch_index, csrc/pw_table_sample.inc); new members go HERE, at the end
+  bool index_valid;
+  int32_t* d_rows_by_cost;   // [rows_cap], parallel to the pool: item i's permutation of its rows at row_off[i]
+  uint32_t* d_cost_start;    // ragged: max_cost + 3 words per stored item
+  int64_t* d_cs_off;         // [n] where an item's cost_start begins, -1: none
+  std::vector<int64_t> h_cs_off;
 };
+
+static void solve_batch_free_index(PwSolveBatch* b) {
+  void* bufs[] = {b->d_rows_by_cost, b->d_cost_start, b->d_cs_off};
+  for (void* p : bufs)
+    if (p) (void)hipFree(p);
+  b->d_rows_by_cost = nullptr;
+  b->d_cost_start = nullptr;
+  b->d_cs_off = nullptr;
+  b->index_valid = false;
+}
+
+// host copies of the last run's status / summary / row_off, once per run (synchronises `st` then): what the item offsets are
+// is only known on the device
+static int solve_batch_host_copies(PwSolveBatch* b, hipStream_t st, const char* fn) {
+  if (b->host_valid) return PW_OK;
+  const size_t n = static_cast<size_t>(b->n);
+  b->h_status.resize(n);
+  b->h_summary.resize(n * 5);
+  b->h_row_off.resize(n);
+  hipError_t err = hipMemcpyAsync(b->h_status.data(), b->d_status, n, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipMemcpyAsync(b->h_summary.data(), b->d_summary, n * 20, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipMemcpyAsync(b->h_row_off.data(), b->d_row_off, n * 8, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  if (err != hipSuccess) return pw_fail(PW_EDEVICE, std::string(fn) + ": " + hipGetErrorString(err));
+  b->host_valid = true;
+  return PW_OK;
+}
 
 static void solve_batch_free_items(PwSolveBatch* b) {
   void* bufs[] = {b->d_slots, b->d_status, b->d_summary, b->d_row_off, b->d_slot_off, b->d_slot_log2};
@@ -488,6 +521,7 @@ void pw_solve_batch_destroy(PwSolveBatch* b) {
   if (!b) return;
   PwDeviceGuard guard(b->eng->set->device);
   solve_batch_free_items(b);
+  solve_batch_free_index(b);
   void* bufs[] = {b->d_key, b->d_succ, b->d_cost, b->d_acts, b->d_item_of_puzzle, b->d_counters};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
@@ -536,6 +570,7 @@ int pw_solve_batch_run(PwSolveBatch* b, const int32_t* puzzles, int32_t n, int64
   PwDeviceGuard guard(e->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   b->host_valid = false;
+  b->index_valid = false;  // the cost index goes with the run it was built from (its arrays are freed by the next build)
   if (n > b->n_cap) {  // the per-item arrays and the lookup pool (4 slots per row + 16 per item always hold what the rows hold)
     if (hipStreamSynchronize(st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_solve_batch_run: stream error");
     solve_batch_free_items(b);
@@ -686,18 +721,7 @@ int pw_solve_batch_read(PwSolveBatch* b, int32_t item, int64_t first, int64_t co
   if (first < 0 || count < 0) return pw_fail(PW_EINVAL, "pw_solve_batch_read: row range out of bounds");
   PwDeviceGuard guard(b->eng->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!b->host_valid) {  // once per run: what the item offsets are is only known on the device
-    const size_t n = static_cast<size_t>(b->n);
-    b->h_status.resize(n);
-    b->h_summary.resize(n * 5);
-    b->h_row_off.resize(n);
-    hipError_t err = hipMemcpyAsync(b->h_status.data(), b->d_status, n, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(b->h_summary.data(), b->d_summary, n * 20, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(b->h_row_off.data(), b->d_row_off, n * 8, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) return pw_fail(PW_EDEVICE, std::string("pw_solve_batch_read: ") + hipGetErrorString(err));
-    b->host_valid = true;
-  }
+  if (int rc = solve_batch_host_copies(b, st, "pw_solve_batch_read")) return rc;
   const size_t it = static_cast<size_t>(item);
   if (b->h_status[it] != PW_SB_BUILT || b->h_row_off[it] < 0)
     return pw_fail(PW_EINVAL, "pw_solve_batch_read: the item has no stored rows (status " + std::to_string(b->h_status[it]) + ")");

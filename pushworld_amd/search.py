@@ -750,6 +750,124 @@ def _query_outputs(out, n: int, device):
     return tuple(out)
 
 
+# ---- drawing from the tables (pw_*_index / pw_*_sample / pw_*_plans) --------------------------------------------
+TABLE_K_SAMPLE, TABLE_K_PLAN = 0xA0761D6478BD642F, 0xE7037ED1A0B428DB  # PW_TABLE_K_SAMPLE / PW_TABLE_K_PLAN
+TABLE_TIES = {"lowest": 0, "uniform": 1}
+PLANS_NONE, PLANS_CUT = -1, -2  # ``plans``' plan_len: no plan from there (dead end, not in a table) / longer than plan_cap
+_COST_MAX = (1 << 31) - 1
+
+
+def _dev_tensor(name: str, t, dtype, shape, device, optional: bool = False):
+    """One device array of a table call: dtype, shape, device and contiguity, in the words of ``_state_inputs``."""
+    if t is None and optional:
+        return None
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != tuple(shape):
+        kind = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise ValueError(f"{name} must be a {kind} tensor {list(shape)}" + (" (or None)" if optional else ""))
+    if t.device != device:
+        raise ValueError(f"{name} must live on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t
+
+
+def _pos_inputs(puzzle_id, pos, mask, npad: int, device, ids_optional: bool) -> int:
+    """``_state_inputs``, with ``puzzle_id`` None allowed for the one-puzzle tables; returns n."""
+    if puzzle_id is not None or not ids_optional:
+        return _state_inputs(puzzle_id, pos, mask, npad, device)
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int8 or pos.dim() != 3 or \
+            tuple(pos.shape[1:]) != (npad, 2) or not 1 <= pos.shape[0] < 1 << 31:
+        raise ValueError(f"pos must be an int8 tensor [n, {npad}, 2] (the engine's state layout), n >= 1")
+    n = int(pos.shape[0])
+    _dev_tensor("pos", pos, torch.int8, (n, npad, 2), device)
+    _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
+    return n
+
+
+def _sample_call(table, ids_optional: bool, puzzle_id, pos, steps, terminated, truncated, cost, mask, seed, counter, out):
+    """The checks and the one launch of ``SolutionTable.sample`` / ``SolutionTableBatch.sample``."""
+    npad, device = table.npad, table.device
+    n = _pos_inputs(puzzle_id, pos, mask, npad, device, ids_optional)
+    _dev_tensor("steps", steps, torch.int32, (n,), device)
+    _dev_tensor("terminated", terminated, (torch.uint8, torch.bool), (n,), device, optional=True)
+    _dev_tensor("truncated", truncated, (torch.uint8, torch.bool), (n,), device, optional=True)
+    if not isinstance(cost, (tuple, list)) or len(cost) != 2:
+        raise ValueError("cost must be a (lo, hi) pair of ints (hi None: no upper limit) or of int32 tensors [n]")
+    lo, hi = cost
+    lo_n = hi_n = None
+    if isinstance(lo, torch.Tensor) or isinstance(hi, torch.Tensor):
+        lo_n = _dev_tensor("cost: lo", lo, torch.int32, (n,), device)
+        hi_n = _dev_tensor("cost: hi", hi, torch.int32, (n,), device)
+        lo = hi = 0
+    else:
+        lo, hi = int(lo), _COST_MAX if hi is None else int(hi)
+        if not 0 <= lo <= hi <= _COST_MAX:
+            raise ValueError("cost must be a band 0 <= lo <= hi")
+    if counter is None:
+        counter = torch.zeros((n,), dtype=torch.int32, device=device)
+    # (uint32 counter bits; an int32 tensor holds them as well, like VecPushWorld.episode)
+    _dev_tensor("counter", counter, (torch.int32, torch.uint32), (n,), device)
+    if out is None:
+        out = (torch.full((n,), -1, dtype=torch.int32, device=device), torch.full((n,), -1, dtype=torch.int32, device=device))
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError("out must be the (row, cost) pair of an earlier sample")
+    _dev_tensor("out: row", out[0], torch.int32, (n,), device)
+    _dev_tensor("out: cost", out[1], torch.int32, (n,), device)
+    fn, handle, stream = table._entry("sample")  # (the first call builds the cost index: not capturable)
+    _capi.check(fn(handle, _capi._ptr(puzzle_id), _capi._ptr(mask), n, npad, int(seed) & 0xFFFFFFFFFFFFFFFF, _capi._ptr(counter),
+                   lo, hi, _capi._ptr(lo_n), _capi._ptr(hi_n), _capi._ptr(pos), _capi._ptr(steps), _capi._ptr(terminated),
+                   _capi._ptr(truncated), _capi._ptr(out[0]), _capi._ptr(out[1]), stream))
+    return tuple(out)
+
+
+def _plans_call(table, ids_optional: bool, index, puzzle_id, mask, tie, seed, plan_cap, out):
+    """The checks and the one launch of ``SolutionTable.plans`` / ``SolutionTableBatch.plans``."""
+    device = table.device
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1:
+        raise ValueError("index must be an int32 tensor [n] (rows, as query returns them)")
+    n = int(index.shape[0])
+    if n < 1 or n >= 1 << 31:
+        raise ValueError("index must hold 1 .. 2^31 - 1 items")
+    _dev_tensor("index", index, torch.int32, (n,), device)
+    _dev_tensor("puzzle_id", puzzle_id, torch.int32, (n,), device, optional=ids_optional)
+    _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
+    if tie not in TABLE_TIES:
+        raise ValueError("tie must be 'lowest' or 'uniform'")
+    plan_cap = int(plan_cap)
+    if not 1 <= plan_cap <= _capi.PLAN_MAX_ACTIONS:
+        raise ValueError(f"plan_cap must be in 1 .. {_capi.PLAN_MAX_ACTIONS}")
+    if out is None:
+        out = (torch.zeros((n, plan_cap), dtype=torch.uint8, device=device),
+               torch.full((n,), PLANS_NONE, dtype=torch.int32, device=device))
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError("out must be the (plans, plan_len) pair of an earlier call")
+    _dev_tensor("out: plans", out[0], torch.uint8, (n, plan_cap), device)
+    _dev_tensor("out: plan_len", out[1], torch.int32, (n,), device)
+    fn, handle, stream = table._entry("plans")
+    _capi.check(fn(handle, _capi._ptr(index), _capi._ptr(puzzle_id), _capi._ptr(mask), n, TABLE_TIES[tie],
+                   int(seed) & 0xFFFFFFFFFFFFFFFF, _capi._ptr(out[0]), plan_cap, _capi._ptr(out[1]), stream))
+    return tuple(out)
+
+
+_SAMPLE_DOC = """Draws one start state per environment from this table's states with a cost-to-go in ``cost`` -- ``(lo, hi)`` ints
+        (``hi`` None: up to the table's ``max_cost``) or two int32 tensors [n], a band per environment -- uniformly over those
+        states, and writes it as a reset would: the state into ``pos`` (int8 [n, NP, 2], zeros beyond the puzzle's movables),
+        ``steps`` = 0, ``terminated`` = ``truncated`` = 0 (either may be None).  One launch on the current stream, no wait, no
+        allocation when ``counter`` and ``out`` are given (capturable).  The band is clamped to ``0 .. max_cost``; dead ends are
+        never drawn.  ``counter`` (int32 / uint32 [n], None: zeros) counts the draws of every environment and is advanced in
+        place: draw = f(``seed``, environment, counter).  Returns ``(row, cost)`` int32 [n] (``out``, filled in place): the
+        row drawn and its cost; -1 / -1 where the puzzle has no solvable state.  Masked environments and environments of
+        puzzles without a stored table here keep everything they held, the counter included."""
+
+_PLANS_DOC = """A shortest plan from every row of ``index`` (int32 [n], as ``query`` returns them) in one launch on the current
+        stream, no wait: ``(plans uint8 [n, plan_cap], plan_len int32 [n])``.  ``tie`` "lowest" takes the lowest optimal
+        action at every step (``optimal_plan``'s plan), "uniform" draws among the optimal actions (f(``seed``, item, step)).
+        ``plan_len`` is the row's cost; ``PLANS_NONE`` -1 for ``index`` < 0, a dead end or a puzzle without a stored table
+        here, ``PLANS_CUT`` -2 for a plan longer than ``plan_cap`` (``plans`` untouched in both cases).  Masked items keep
+        what ``out`` -- the pair of an earlier call -- held."""
+
+
 class SolutionTable:
     """The exact cost-to-go of EVERY state reachable in one puzzle: a ``BreadthFirstSearch`` run to exhaustion, then
     ``pw_search_solve``'s backward propagation from the goal states.  Row i belongs to state i of the search (the FIFO
@@ -872,6 +990,43 @@ class SolutionTable:
                                                     _capi._ptr(out[2]), self.search._stream()))
         return out
 
+    def _entry(self, what: str):
+        """(function, handle, stream) of the sample / plans launch; the first sample builds the cost index."""
+        if what == "sample" and not getattr(self, "_indexed", False):
+            _capi.check(_capi.lib.pw_search_table_index(self.search.handle, self.search._stream()))
+            self._indexed = True
+        fn = _capi.lib.pw_search_table_sample if what == "sample" else _capi.lib.pw_search_table_plans
+        return fn, self.search.handle, self.search._stream()
+
+    def cost_index(self):
+        """``(rows_by_cost int32 [count], cost_start uint32 [max_cost + 3])`` on the device: the rows grouped by cost-to-go,
+        the dead ends last; bucket c is ``rows_by_cost[cost_start[c] : cost_start[c + 1]]``, the dead ends are bucket
+        ``max_cost + 1``.  Built by the first call (three launches), kept until the search is restarted.  The order inside
+        a bucket is whatever the build left."""
+        _capi.check(_capi.lib.pw_search_table_index(self.search.handle, self.search._stream()))
+        rows = torch.empty((self.num_states,), dtype=torch.int32, device=self.device)
+        start = torch.empty((self.max_cost + 3,), dtype=torch.uint32, device=self.device)
+        _capi.check(_capi.lib.pw_search_table_index_read(self.search.handle, _capi._ptr(rows), _capi._ptr(start),
+                                                         self.search._stream()))
+        return rows, start
+
+    def sample(self, puzzle_id: Optional[torch.Tensor], pos: torch.Tensor, steps: torch.Tensor,
+               terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None, cost=(1, None),
+               mask: Optional[torch.Tensor] = None, seed: int = 0, counter: Optional[torch.Tensor] = None, out=None):
+        return _sample_call(self, True, puzzle_id, pos, steps, terminated, truncated, cost, mask, seed, counter, out)
+
+    sample.__doc__ = _SAMPLE_DOC
+
+    def plans(self, index: torch.Tensor, puzzle_id: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+              tie: str = "lowest", seed: int = 0, plan_cap: int = 1024, out=None):
+        return _plans_call(self, True, index, puzzle_id, mask, tie, seed, plan_cap, out)
+
+    plans.__doc__ = _PLANS_DOC
+
+    def covers(self, puzzle_id: torch.Tensor) -> torch.Tensor:
+        """bool [n] on the device: the items of ``puzzle_id`` this table answers for."""
+        return puzzle_id == self.puzzle_index
+
     def close(self) -> None:
         search = getattr(self, "search", None)
         if search is not None:
@@ -954,6 +1109,7 @@ class SolutionTableBatch:
         self.rows, self.rows_needed = int(rows), int(totals[0])
         self.num_states, self.num_goals, self.dead_ends, self.max_cost, self.start_cost = self.summary.unbind(1)
         self._counts = None
+        self._indexed, self._max_costs, self._covered = False, None, None
 
     def __len__(self) -> int:
         return len(self.puzzles)
@@ -1034,6 +1190,54 @@ class SolutionTableBatch:
                                                    _capi._ptr(out[2]), self._stream()))
         return out
 
+    def _index(self) -> None:
+        if not self._indexed:  # (the first call builds the cost index of every stored table: not capturable)
+            _capi.check(_capi.lib.pw_solve_batch_index(self.handle, self._stream()))
+            self._indexed = True
+
+    def _entry(self, what: str):
+        """(function, handle, stream) of the sample / plans launch; the first sample builds the cost index."""
+        if what == "sample":
+            self._index()
+        fn = _capi.lib.pw_solve_batch_sample if what == "sample" else _capi.lib.pw_solve_batch_plans
+        return fn, self.handle, self._stream()
+
+    def cost_index(self, item: int):
+        """``SolutionTable.cost_index`` of item ``item``: ``(rows_by_cost int32 [count], cost_start uint32 [max_cost + 3])``
+        on the device.  The first call builds the index of every stored table (three launches)."""
+        item, count = self._item(item)
+        self._index()
+        if self._max_costs is None:
+            self._max_costs = self.summary[:, 3].cpu().numpy()
+        rows = torch.empty((count,), dtype=torch.int32, device=self.device)
+        start = torch.empty((int(self._max_costs[item]) + 3,), dtype=torch.uint32, device=self.device)
+        _capi.check(_capi.lib.pw_solve_batch_index_read(self.handle, item, _capi._ptr(rows), _capi._ptr(start), self._stream()))
+        return rows, start
+
+    def sample(self, puzzle_id: torch.Tensor, pos: torch.Tensor, steps: torch.Tensor,
+               terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None, cost=(1, None),
+               mask: Optional[torch.Tensor] = None, seed: int = 0, counter: Optional[torch.Tensor] = None, out=None):
+        return _sample_call(self, False, puzzle_id, pos, steps, terminated, truncated, cost, mask, seed, counter, out)
+
+    sample.__doc__ = _SAMPLE_DOC
+
+    def plans(self, index: torch.Tensor, puzzle_id: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+              tie: str = "lowest", seed: int = 0, plan_cap: int = 1024, out=None):
+        return _plans_call(self, False, index, puzzle_id, mask, tie, seed, plan_cap, out)
+
+    plans.__doc__ = _PLANS_DOC
+
+    def covers(self, puzzle_id: torch.Tensor) -> torch.Tensor:
+        """bool [n] on the device: the items of ``puzzle_id`` whose puzzle has a stored table here."""
+        if self._covered is None:
+            has = torch.zeros((len(self.engine.pset),), dtype=torch.bool, device=self.device)
+            ids = self._ids if self._ids is not None else torch.arange(len(self.puzzles), device=self.device)
+            has[ids[self.status == TABLE_BUILT].long()] = True
+            self._covered = has
+        pid = puzzle_id.long()
+        inside = (pid >= 0) & (pid < self._covered.shape[0])
+        return inside & self._covered[pid.clamp(0, self._covered.shape[0] - 1)]
+
     def close(self) -> None:
         h = getattr(self, "handle", None)
         if h is not None and _capi.lib is not None:
@@ -1086,10 +1290,11 @@ class PlanReplay:
     none), ``final_pos`` int8 [n, NP, 2], ``offset`` int64 [n + 1] (rows of item i: ``offset[i] : offset[i + 1]``).
     Per row (``num_rows`` of them, None when no rows were asked for): ``item``, ``t``, ``puzzle_id`` int32, ``pos`` int8
     [T, NP, 2] (the state before the action), ``action`` uint8, ``reward`` float64, ``done`` uint8, ``next_pos`` (on request);
-    ``obs`` is filled in by ``VecPushWorld.demonstrations``."""
+    ``obs`` is filled in by ``VecPushWorld.demonstrations``; ``cost`` int32 [T] and ``acts`` uint8 [T] -- the cost-to-go and the
+    optimal / safe action bits of the row's state -- by ``VecPushWorld.optimal_demonstrations``."""
 
     __slots__ = ("verdict", "first_goal", "final_pos", "offset", "num_rows", "item", "t", "puzzle_id", "pos", "action",
-                 "reward", "done", "next_pos", "obs")
+                 "reward", "done", "next_pos", "obs", "cost", "acts")
 
     def __init__(self):
         for name in self.__slots__:

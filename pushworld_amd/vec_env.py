@@ -234,15 +234,19 @@ class VecPushWorld:
         if seed is not None:
             self.seed = int(seed)
             self.episode.zero_()
+        self._reset_states(mask)
+        if self.obs is not None:
+            self._render()
+        return self.obs
+
+    def _reset_states(self, mask: Optional[torch.Tensor]) -> None:
+        """``reset`` up to its render: the (masked) environments draw their puzzle and return to its initial state."""
         if self.resample:
             self.engine.resample(self.puzzle_id, self.episode, self.seed, terminated=mask, table=self.sample_table)
         self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, mask)
         self._has_reset = True
         if self._bind and (self.bound_info is None or self.resample or mask is None):
             self.bound_info = self.engine.bind(self.puzzle_id)  # (reads the segment count back: later launches have the exact grid)
-        if self.obs is not None:
-            self._render()
-        return self.obs
 
     def _render(self) -> None:
         if self.observation == "cells":
@@ -437,6 +441,107 @@ class VecPushWorld:
             if table.search._engine is not self.engine:
                 raise ValueError("the tables must be made on this environment (VecPushWorld.solution_table)")
             table.query(self.puzzle_id, self.pos, out=out)
+        return out
+
+    def _own_tables(self, tables) -> list:
+        from .search import SolutionTableBatch
+
+        tables = list(tables)
+        for table in tables:
+            engine = table.engine if isinstance(table, SolutionTableBatch) else table.search._engine
+            if engine is not self.engine:
+                raise ValueError("the tables must be made on this environment (VecPushWorld.solution_table / solution_tables)")
+        return tables
+
+    def reset_from_tables(self, tables, cost=(1, None), mask: Optional[torch.Tensor] = None, seed: Optional[int] = None):
+        """``reset(mask)`` with start states drawn from cost-to-go tables (a reverse curriculum): every (masked) environment
+        whose puzzle has a table in ``tables`` -- a mixed list of ``solution_table``s and ``solution_tables`` batches, as
+        ``cost_to_go`` takes -- starts from a state drawn uniformly among the states of its puzzle with a cost-to-go in
+        ``cost`` = ``(lo, hi)`` (``hi`` None: up to each table's own largest cost; two int32 tensors [B]: a band per
+        environment).  The band is clamped to each table's costs and dead ends are never drawn, so the default ``(1, None)``
+        is "any solvable state that is not solved yet"; grow ``hi`` from 1 for a curriculum.  Environments without a table
+        (or whose puzzle has no solvable state) start from the initial state.  One ``pw_reset`` launch, one sample launch
+        per table, one render; no wait.  Returns the observation tensor.
+
+        ``self.start_row`` / ``self.start_cost`` (int32 [B]) hold the table row and the cost-to-go every environment started
+        from (-1 / -1 without a table); ``self.table_draws`` counts the draws per environment -- a draw is a function of
+        (seed, environment, count), ``seed`` restarts the counts.  Autoreset inside ``step`` does not draw from tables: step
+        with ``autoreset=False`` and call ``reset_from_tables(tables, mask=terminated | truncated)``."""
+        tables = self._own_tables(tables)
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        if getattr(self, "table_draws", None) is None:
+            self.table_seed = self.seed
+            # (uint32 counter bits over an int32 allocation, like `episode`)
+            self.table_draws = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device).view(torch.uint32)
+            self.start_row = torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device)
+            self.start_cost = torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device)
+        if seed is not None:
+            self.table_seed = int(seed)
+            self.table_draws.view(torch.int32).zero_()
+        self._reset_states(mask)
+        if mask is None:
+            self.start_row.fill_(-1), self.start_cost.fill_(-1)
+        else:
+            self.start_row.masked_fill_(mask.bool(), -1), self.start_cost.masked_fill_(mask.bool(), -1)
+        for table in tables:
+            table.sample(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, cost=cost, mask=mask,
+                         seed=self.table_seed, counter=self.table_draws, out=(self.start_row, self.start_cost))
+        self._obs_current = False
+        if self.obs is not None:
+            self._render()
+        return self.obs
+
+    def optimal_demonstrations(self, tables, tie: str = "lowest", seed: int = 0, observation: Optional[str] = "own",
+                               mask: Optional[torch.Tensor] = None, plan_cap: int = 1024):
+        """``demonstrations`` with SHORTEST plans read off cost-to-go tables instead of a planner's: from every (unmasked)
+        environment's current state, one ``cost_to_go`` over ``tables`` (a mixed list, as there), one plans launch per
+        table (``tie`` "lowest": the lowest optimal action at every step, "uniform": drawn among the optimal actions with
+        ``seed``), the replay of ``demonstrations`` (every step of every plan becomes one row), one query launch per table
+        over the rows and one render launch.  Environments at a dead end, outside every table or with a plan longer than
+        ``plan_cap`` contribute no rows.  Returns the same ``search.PlanReplay`` as ``demonstrations`` plus ``cost`` int32
+        [T], the cost-to-go of each row's state (it falls by 1 per row to 1), and ``acts`` uint8 [T], its optimal (bits
+        0..3) and safe (bits 4..7) actions.  Waits once, for the number of rows."""
+        from .search import PLANS_NONE, replay_plans
+
+        tables = self._own_tables(tables)
+        if observation == "own":
+            observation = self.observation
+        if observation not in ("uint8", "float32", "cells", None):
+            raise ValueError("observation must be 'uint8', 'float32', 'cells' or None")
+        own_rgb = "uint8" if self.engine.obs_dtype == torch.uint8 else "float32"
+        if observation in ("uint8", "float32") and observation != own_rgb:
+            raise ValueError(f"this environment's engine renders {own_rgb} pixels: observation must be '{own_rgb}', 'cells' or None")
+        if tie not in ("lowest", "uniform"):
+            raise ValueError("tie must be 'lowest' or 'uniform'")
+        if int(plan_cap) < 1:
+            raise ValueError("plan_cap must be >= 1")
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        index, _, _ = self.cost_to_go(tables)
+        plans = torch.zeros((self.num_envs, int(plan_cap)), dtype=torch.uint8, device=self.device)
+        plan_len = torch.full((self.num_envs,), PLANS_NONE, dtype=torch.int32, device=self.device)
+        for table in tables:  # (a table answers for its own puzzles only: the others keep what another table wrote)
+            own = table.covers(self.puzzle_id)
+            if mask is not None:
+                own &= mask.bool()
+            table.plans(index, self.puzzle_id, mask=own, tie=tie, seed=seed, plan_cap=int(plan_cap), out=(plans, plan_len))
+        out = replay_plans(self.engine, self.puzzle_id, plans, plan_len, pos=self.pos, mask=mask, include="valid", next_pos=True)
+        T = out.num_rows
+        out.cost = torch.full((T,), -2, dtype=torch.int32, device=self.device)
+        out.acts = torch.zeros((T,), dtype=torch.uint8, device=self.device)
+        if T > 0:
+            rows = (torch.full((T,), -1, dtype=torch.int32, device=self.device), out.cost, out.acts)
+            for table in tables:
+                table.query(out.puzzle_id, out.pos, out=rows)
+        if observation == "cells":
+            out.obs = torch.empty((T,) + self.engine.cells_shape(), dtype=torch.uint8, device=self.device)
+            if T > 0:
+                self.engine.render_cells(out.puzzle_id, out.pos, out.obs)
+        elif observation is not None:
+            storage, out.obs = self.engine.alloc_obs(T)
+            if T > 0:
+                self.engine.render(out.puzzle_id, out.pos, storage)
         return out
 
     def set_states(self, pos: np.ndarray) -> None:
