@@ -456,3 +456,34 @@ def test_difficulty_labels(world):
     for i, h in enumerate(world.hosts):
         assert (plan_len[i], states[i]) == (h.summary[4], h.summary[0]) and share[i] == h.summary[2] / h.summary[0]
     assert plan_len[-1] == -1 and states[-1] == 0 and np.isnan(share[-1])
+
+
+@pytest.mark.parametrize("per_cu", [1, 8])
+def test_deep_and_large_tables_in_one_launch(golden, per_cu):
+    """Both 14-wide serpentines (largest cost 102 and 101: a hundred sweeps inside the persistent workgroup, a barrier each),
+    the 42 832 rows of the open room with two boxes and three tiny puzzles in ONE launch, at 1 and at 8 workgroups per CU:
+    every table BUILT, summaries and -- state by state -- successors, costs and action bits equal to the host reference."""
+    import deep_puzzles
+    from pushworld_amd import _capi
+    from pushworld_amd.search import SolutionTableBatch
+
+    names, texts, hosts = deep_puzzles.batch_set(golden)
+    pset = _capi.PuzzleSet([_capi.ParsedPuzzle(t) for t in texts], 0)
+    eng = _capi.Engine(pset, None, 3, 1, _capi.OBS_U8)
+    eng.set_option("search_batch_groups_per_cu", per_cu)
+    try:
+        b = SolutionTableBatch(eng, max_states_each=deep_puzzles.BATCH_CAP)
+        try:
+            status, summary, _ = _summaries(b)
+            assert status.tolist() == [BUILT] * len(names)
+            assert b.rows_needed == b.rows == sum(len(h.states) for h in hosts)
+            for i, (k, h) in enumerate(zip(names, hosts)):
+                c0 = -1 if h.summary[4] == INF else h.summary[4]
+                assert tuple(summary[i]) == tuple(h.summary[:4]) + (c0,), k
+                _assert_exact(b, i, h, k)
+            for i, k in enumerate(deep_puzzles.BATCH_DEEP):
+                assert tuple(summary[i])[:4] == deep_puzzles.EXPECT[k][:4], k
+        finally:
+            b.close()
+    finally:
+        eng.set_option("search_batch_groups_per_cu", 0)

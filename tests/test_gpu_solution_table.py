@@ -379,3 +379,42 @@ def test_mixed_batch_cost_to_go(golden):
     finally:
         for t in tables:
             t.close()
+
+
+# ---- deep spaces (tests/deep_puzzles.py): the sweep loop of pw_search_solve beyond two batches of 16 sweeps ---------------------
+# largest cost 15 / 16 / 17 / 31 / 32 / 33: the last settling sweep is the last of a batch, the first of the next one, and one
+# further; 253 / 254: the cost_start tables of 256 and 257 words; 1950 / 1949: 122 batches of sweeps
+DEEP = (["corridor %d" % L for L in (17, 18, 19, 33, 34, 35)] +
+        ["serpentine 30x29 max 253", "serpentine 30x29 max 254", "serpentine 62x61", "serpentine 62x61 overshoot"])
+
+
+@pytest.mark.parametrize("name", DEEP)
+def test_deep_table_equals_host_reference(name):
+    """successors / costs / actions row by row and the summary, max_cost included, on path puzzles whose largest cost is 15 ..
+    1950; optimal_plan(0) replayed on the oracle reaches a goal state at exactly step cost[0] and not before."""
+    import deep_puzzles
+    from pushworld_amd.puzzle import PushWorldPuzzle
+    from pushworld_amd.search import SolutionTable
+
+    want = deep_puzzles.host_table(name)
+    assert want.summary == deep_puzzles.EXPECT[name]
+    pz = PushWorldPuzzle(text=deep_puzzles.text(name))
+    tab = SolutionTable(pz, max_states=CAP + 8)
+    try:
+        assert (tab.num_states, tab.num_goal_states, tab.num_dead_ends, tab.max_cost, tab.initial_cost) == want.summary
+        got = tab.states()
+        assert (got == np.array(want.states, dtype=np.int64).reshape(got.shape)).all()
+        succ, cost, acts = tab.successors().cpu().numpy(), tab.costs().cpu().numpy(), tab.actions().cpu().numpy()
+        assert succ.shape == want.succ.shape and (succ == want.succ).all()
+        assert (cost == want.cost).all()
+        assert (acts == want.acts).all()
+        plan = tab.optimal_plan(0)
+        assert len(plan) == int(want.cost[0]) == want.summary[4]
+        assert pz.is_valid_plan(plan)
+        s = want.states[0]
+        for a in plan:
+            assert not want.oz.py.is_goal_state(s)
+            s = want.oz.get_next_state(s, a)
+        assert want.oz.py.is_goal_state(s)
+    finally:
+        tab.close()

@@ -125,19 +125,24 @@ def test_the_puzzle_set_covers_the_cases(worlds):
     assert h8["eight"].n_mov == 8 and h8["far"].states.max() == 14 and w16.host[0].n_mov == 9
 
 
+def assert_index(t, tag=None):
+    """The cost index of one table (a Table): what every index test asserts, here and in tests/test_gpu_table_deep.py."""
+    rows, start = t.rows_by_cost, t.cost_start.astype(np.int64)
+    assert (np.sort(rows) == np.arange(len(t.cost))).all(), tag  # a permutation of the rows
+    bucket = np.where(t.cost == INF, t.max_cost + 1, t.cost).astype(np.int64)
+    want = np.concatenate([[0], np.cumsum(np.bincount(bucket, minlength=t.max_cost + 2))])
+    assert len(start) == t.max_cost + 3 and (start == want).all(), tag
+    for c in range(t.max_cost + 2):  # every row of bucket c has cost c; the dead ends are the last bucket
+        assert (bucket[rows[start[c]:start[c + 1]]] == c).all(), (tag, c)
+    assert start[-1] == len(rows)
+
+
 @pytest.mark.parametrize("npad", [4, 8, 16])
 def test_index(worlds, npad):
     w = worlds[npad]
     assert len(w.host) >= 3
     for p, t in w.host.items():
-        rows, start = t.rows_by_cost, t.cost_start.astype(np.int64)
-        assert (np.sort(rows) == np.arange(len(t.cost))).all(), p  # a permutation of the rows
-        bucket = np.where(t.cost == INF, t.max_cost + 1, t.cost).astype(np.int64)
-        want = np.concatenate([[0], np.cumsum(np.bincount(bucket, minlength=t.max_cost + 2))])
-        assert len(start) == t.max_cost + 3 and (start == want).all(), p
-        for c in range(t.max_cost + 2):  # every row of bucket c has cost c; the dead ends are the last bucket
-            assert (bucket[rows[start[c]:start[c + 1]]] == c).all(), (p, c)
-        assert start[-1] == len(rows)
+        assert_index(t, p)
     # built once: a second read returns the same arrays
     item = int(np.flatnonzero(w.status == BUILT)[0])
     again = w.batch.cost_index(item)[0].cpu().numpy()
