@@ -127,11 +127,13 @@ class GiveUp(Exception):
 
 
 class RecursiveGraphDistance:
-    def __init__(self, pz, fewest_tools=True, max_calls=None):
+    def __init__(self, pz, fewest_tools=True, max_calls=None, graphs=None):
+        """``graphs``: movement graphs computed before (``movement_graphs(pz)``, or the library's host-built ones where a
+        host test has pinned them equal), to spare the slowest step of this class."""
         self.pz = pz
         self.fewest_tools = fewest_tools
         self.max_calls = max_calls
-        self.graphs = movement_graphs(pz)
+        self.graphs = movement_graphs(pz) if graphs is None else graphs
         self.dist = [PathDistances(g) for g in self.graphs]
         self.calls = 0
 

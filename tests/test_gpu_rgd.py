@@ -1,7 +1,6 @@
 """RGD heuristic on the device (pw_rgd_*): distance tables and batched evaluation against the literals of the reference's
 C++ tests and the plain-Python restatement (tests/rgd_restatement.py), bit for bit including +inf."""
 import glob
-import math
 import os
 import random
 import sys
@@ -16,6 +15,7 @@ from pushworld_amd.search import BreadthFirstSearch, RecursiveGraphDistance
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import rgd_restatement as R  # noqa: E402
+from rgd_helpers import MAX_CALLS, compare, dev, enc, same, solution_plan  # noqa: E402
 from test_rgd_host import RGD_COSTS, TRIVIAL_DISTANCES, cpp_state  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -23,27 +23,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEVEL1 = sorted(glob.glob(os.path.join(ROOT, "pushworld_amd", "data", "puzzles", "level1", "*.pwp")))
 REF_CPP = os.path.join(ROOT, "tests", "puzzles", "ref_cpp")
-MAX_CALLS = 4000  # the restatement gives up past this many recursion frames (below the kernel's default budget, 4 096)
-
-
-def enc(state):
-    return [x * 10000 + y for x, y in state]
-
-
-def dev(states, h):
-    return torch.tensor([enc(s) for s in states], dtype=torch.int32, device=h.device)
-
-
-def solution_plan(level, name):
-    with open(os.path.join(ROOT, "pushworld_amd", "data", "solutions", level, name + ".yaml")) as f:
-        for line in f:
-            if line.startswith("plan:"):
-                return ["LRUD".index(c) for c in line.split(":", 1)[1].strip()]
-    raise ValueError(name)
-
-
-def same(a, b):
-    return (a == b) or (math.isnan(a) and math.isnan(b))
 
 
 def level1_states(path, oz, rng, n_walk=40):
@@ -59,21 +38,6 @@ def level1_states(path, oz, rng, n_walk=40):
         s = oz.get_next_state(s, rng.randrange(4))
         out.append(s)
     return out
-
-
-def compare(h_gpu, h_ref, states):
-    """(compared, skipped): every state the restatement finishes must match bit for bit."""
-    got = h_gpu.evaluate(dev(states, h_gpu)).cpu().numpy()
-    compared = skipped = 0
-    for s, g in zip(states, got):
-        try:
-            want = h_ref.estimate(s)
-        except R.GiveUp:
-            skipped += 1
-            continue
-        assert same(float(g), want), (s, float(g), want)
-        compared += 1
-    return compared, skipped
 
 
 def test_distances_equal_the_cpp_literals():
