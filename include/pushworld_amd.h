@@ -1059,6 +1059,46 @@ int pw_plan_replay_emit(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos
                         int32_t* row_puzzle_id, int8_t* row_pos, uint8_t* row_action, double* row_reward, uint8_t* row_done,
                         int8_t* row_next_pos, int64_t* dropped, void* stream);
 
+/* Walk regions and push moves (K15): what a search over pushes, a push-level action space or an "is any push available" mask
+ * needs, for a whole batch of states in one launch.  Everything is defined through the step function, for states with
+ * overlaps too.  Take a state s with agent position q0 (the origin of the agent's bounding box):
+ *   walk move (q, a)   stepping s with the agent placed at q by action a moves the agent and nothing else
+ *   walk region R(s)   the agent positions reachable from q0 by walk moves, the other movables fixed; dist(q) is the
+ *                      breadth-first distance, dist(q0) = 0.  A position at which the agent leaves its grid is not in R.
+ *   parent(q), q != q0 the lowest action a for which q' = q - d_a is in R, dist(q') = dist(q) - 1 and (q', a) is a walk move
+ *   push move (q, a)   q in R and that step moves the agent and at least one other movable; its successor is the state after
+ *                      the step.  A step that moves nothing is neither.
+ *   canon(s)           the position of R(s) smallest in (y, x) order
+ * puzzle_id / pos / npad / mask as pw_plan_replay_check (pos NULL: the initial states; nothing beyond a puzzle's N movables
+ * is read).  pw_walk_regions writes
+ *   region_size int32 [n]      positions of R (>= 1); -1 for an item that is masked out, has an id outside the set or a movable
+ *                              outside its grid (nothing further of it is read)
+ *   canon       int8 [n][2] or NULL: canon(s) as (x, y), zeros for a skipped item
+ *   offset      int64 [n + 1]  exclusive prefix sum of the push moves per item (0 for a skipped one); offset[n] = the total
+ *   walk_map    uint16 [n][map_h][map_w] or NULL; map_h / map_w at least the set's largest dimensions (pw_puzzleset_max_dims)
+ *               and at most PW_MAX_DIM.  Entry [y][x]: 0xFFFF where (x, y) is not in R, else dist | parent << 12 (q0 holds 0;
+ *               a board has at most 62 x 62 cells inside its border, so dist fits 12 bits).  Every entry of every item's map
+ *               is written: 2 * map_h * map_w bytes per item.
+ * pw_walk_pushes takes the same inputs and the offset of the first call, recomputes, and writes row offset[i] + k for the k-th
+ * push move of item i, ordered by (y, x) of the agent position it starts from, then by action (any output may be NULL):
+ *   row_item int32 [cap]; row_from int8 [cap][2] the position q; row_action uint8 [cap]; row_walk int32 [cap] dist(q);
+ *   row_moved uint32 [cap] bit j = movable j moved (as pw_expand4); row_goal uint8 [cap] 1 when the successor is a goal state;
+ *   row_next_pos int8 [cap][npad][2] the successor, padding zeroed as pw_render and pw_validate_state require.
+ *   Rows at or beyond `cap` are not written; *dropped (device int64, or NULL) receives how many were left out.
+ * Both are asynchronous on `stream` (one launch each; the first adds a fill of the maps and rocPRIM's scan) and read nothing on
+ * the host; they share the plan replay's workspace.  pos, canon, row_from and row_next_pos are read and written as 2-byte (x, y)
+ * pairs: they must be 2-byte aligned (as pos and the rows of pw_plan_replay_emit; any device allocation is).
+ * PW_EINVAL before any launch, pw_last_error naming the function and the argument: n < 1; npad not 4 / 8 / 16 / 32; a null
+ * puzzle_id, offset, region_size or engine; cap < 0; map_h / map_w outside 1 .. PW_MAX_DIM or below the set's largest
+ * dimensions when walk_map is given; npad below the set's largest number of movables. */
+int pw_walk_regions(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask, int32_t n,
+                    int32_t* region_size, int8_t* canon, int64_t* offset, uint16_t* walk_map, int32_t map_h, int32_t map_w,
+                    void* stream);
+int pw_walk_pushes(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask, int32_t n,
+                   const int64_t* offset, int64_t cap, int32_t* row_item, int8_t* row_from, uint8_t* row_action,
+                   int32_t* row_walk, uint32_t* row_moved, uint8_t* row_goal, int8_t* row_next_pos, int64_t* dropped,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,10 @@ SIGNATURES = {
     "pw_plan_replay_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
                                     c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_walk_regions": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int32, c_int32, c_void_p]),
+    "pw_walk_pushes": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # pw_plan_replay_check verdicts and the `include` choices (include/pushworld_amd.h)
@@ -1129,6 +1133,18 @@ class Engine:
                                       plans.shape[1], _ptr(mask), puzzle_id.shape[0], int(include), _ptr(verdict), _ptr(offset),
                                       int(cap), _ptr(item), _ptr(t), _ptr(row_puzzle_id), _ptr(row_pos), _ptr(action),
                                       _ptr(reward), _ptr(done), _ptr(next_pos), _ptr(dropped), self._stream()))
+
+    # walk regions and push moves (pw_walk_regions / pw_walk_pushes): device tensors in, device tensors out, no wait
+    def walk_regions(self, puzzle_id, pos, mask, region_size, canon, offset, walk_map=None):
+        mh, mw = (walk_map.shape[1], walk_map.shape[2]) if walk_map is not None else (0, 0)
+        check(lib.pw_walk_regions(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(mask), puzzle_id.shape[0],
+                                  _ptr(region_size), _ptr(canon), _ptr(offset), _ptr(walk_map), mh, mw, self._stream()))
+
+    def walk_pushes(self, puzzle_id, pos, mask, offset, cap, item=None, frm=None, action=None, walk=None, moved=None,
+                    goal=None, next_pos=None, dropped=None):
+        check(lib.pw_walk_pushes(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(mask), puzzle_id.shape[0],
+                                 _ptr(offset), int(cap), _ptr(item), _ptr(frm), _ptr(action), _ptr(walk), _ptr(moved),
+                                 _ptr(goal), _ptr(next_pos), _ptr(dropped), self._stream()))
 
     def expand4(self, puzzle_index, states, succ, moved, goal):
         check(lib.pw_expand4(self.handle, int(puzzle_index), _ptr(states), _ptr(succ), _ptr(moved), _ptr(goal),

@@ -419,4 +419,5 @@ struct PageRec {
 #include "pw_planner.inc"
 #include "pw_plan_batch.inc"
 #include "pw_plan_replay.inc"
+#include "pw_walk.inc"
 #include "pw_generate.inc"

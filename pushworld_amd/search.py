@@ -1343,3 +1343,248 @@ def replay_plans(engine_or_vec, puzzle_id: torch.Tensor, plans: torch.Tensor, pl
                                 out.puzzle_id, out.pos, out.action, out.reward, out.done, out.next_pos)
     return out
 
+
+
+# ---- walk regions and push moves (pw_walk_regions / pw_walk_pushes) ----------------------------------------------
+WALK_OUTSIDE = 0xFFFF  # walk_map entry of a position outside the region
+_WALK_D = ((-1, 0), (1, 0), (0, -1), (0, 1))
+
+
+def _walk_inputs(puzzle_id, pos, mask, npad: int, device) -> int:
+    """The checks of ``walk_regions`` on its device arrays; returns n."""
+    if not isinstance(puzzle_id, torch.Tensor) or puzzle_id.dtype != torch.int32 or puzzle_id.dim() != 1:
+        raise ValueError("puzzle_id must be an int32 tensor [n]")
+    n = int(puzzle_id.shape[0])
+    if n < 1 or n >= 1 << 31:
+        raise ValueError("puzzle_id must hold 1 .. 2^31 - 1 items")
+    if pos is not None and (not isinstance(pos, torch.Tensor) or pos.dtype != torch.int8 or tuple(pos.shape) != (n, npad, 2)):
+        raise ValueError(f"pos must be an int8 tensor [n, {npad}, 2] (the engine's state layout) or None")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool)
+                             or tuple(mask.shape) != (n,)):
+        raise ValueError("mask must be a uint8 or bool tensor [n] (or None)")
+    for name, t in (("puzzle_id", puzzle_id), ("pos", pos), ("mask", mask)):
+        if t is None:
+            continue
+        if t.device != device:
+            raise ValueError(f"{name} must live on {device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return n
+
+
+class PushMoves:
+    """The rows of ``WalkRegions.pushes``, on the device: ``item`` int32 [T], ``frm`` int8 [T, 2] (the agent position the push
+    starts from), ``action`` uint8 [T], ``walk`` int32 [T] (walk distance to ``frm``), ``moved`` int32 [T] holding the 32 bits
+    of the C ABI's uint32 mask (bit j: movable j moved; with 32 movables bit 31 makes the number negative: test bits, or take
+    ``moved.to(torch.int64) & 0xFFFFFFFF``), ``goal`` uint8 [T], ``next_pos`` int8 [T, NP, 2]; ``dropped`` int64 [1]: rows
+    beyond ``cap``."""
+
+    __slots__ = ("num_rows", "item", "frm", "action", "walk", "moved", "goal", "next_pos", "dropped")
+
+    def __init__(self):
+        for name in self.__slots__:
+            setattr(self, name, None)
+
+
+class WalkRegions:
+    """What ``walk_regions`` returns; every tensor lives on the device.  ``region_size`` int32 [n] (-1: skipped item),
+    ``canon`` int8 [n, 2] (x, y), ``offset`` int64 [n + 1] (push rows of item i: ``offset[i] : offset[i + 1]``), ``walk_map``
+    uint16 [n, map_h, map_w] or None (``WALK_OUTSIDE`` outside the region, else ``dist | parent << 12``)."""
+
+    def __init__(self, engine, puzzle_id, pos, mask):
+        self.engine, self.puzzle_id, self.pos, self.mask = engine, puzzle_id, pos, mask
+        self.region_size = self.canon = self.offset = self.walk_map = None
+        self._num_pushes = None
+        self._host_maps = {}
+
+    @property
+    def num_pushes(self) -> int:
+        """The total number of push moves (``offset[n]``; read back once: the object's only wait)."""
+        if self._num_pushes is None:
+            self._num_pushes = int(self.offset[-1].item())
+        return self._num_pushes
+
+    def pushes(self, cap: Optional[int] = None) -> PushMoves:
+        """Every push move of every item as rows (``pw_walk_pushes``); ``cap`` rows at the most (default: all of them)."""
+        T = self.num_pushes if cap is None else int(cap)
+        if T < 0:
+            raise ValueError("cap must be >= 0")
+        dev, npad = self.engine.device, int(self.engine.np)
+        out = PushMoves()
+        out.num_rows = T
+        out.item = torch.empty((T,), dtype=torch.int32, device=dev)
+        out.frm = torch.empty((T, 2), dtype=torch.int8, device=dev)
+        out.action = torch.empty((T,), dtype=torch.uint8, device=dev)
+        out.walk = torch.empty((T,), dtype=torch.int32, device=dev)
+        out.moved = torch.empty((T,), dtype=torch.int32, device=dev)
+        out.goal = torch.empty((T,), dtype=torch.uint8, device=dev)
+        out.next_pos = torch.empty((T, npad, 2), dtype=torch.int8, device=dev)
+        out.dropped = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.engine.walk_pushes(self.puzzle_id, self.pos, self.mask, self.offset, T, out.item, out.frm, out.action, out.walk,
+                                out.moved, out.goal, out.next_pos, out.dropped)
+        return out
+
+    def path(self, i: int, xy) -> List[int]:
+        """The walk actions from item ``i``'s agent position to ``xy`` along the parent actions of its walk map (on the host)."""
+        if self.walk_map is None:
+            raise ValueError("the walk maps were not requested (walk_regions(..., maps=True))")
+        i = int(i)
+        if not 0 <= i < self.walk_map.shape[0]:
+            raise ValueError("item index out of range")
+        m = self._host_maps.get(i)
+        if m is None:
+            m = self._host_maps[i] = self.walk_map[i].cpu().numpy()
+        x, y = int(xy[0]), int(xy[1])
+        acts: List[int] = []
+        while True:
+            if not (0 <= y < m.shape[0] and 0 <= x < m.shape[1]) or int(m[y, x]) == WALK_OUTSIDE:
+                raise ValueError(f"({xy[0]}, {xy[1]}) is not in the walk region of item {i}")
+            e = int(m[y, x])
+            if e & 0xFFF == 0:
+                return acts[::-1]
+            if len(acts) > m.size:
+                raise ValueError("the walk map holds a cycle")
+            a = e >> 12
+            acts.append(a)
+            x, y = x - _WALK_D[a][0], y - _WALK_D[a][1]
+
+
+def walk_regions(engine_or_vec, puzzle_id: torch.Tensor, pos: Optional[torch.Tensor] = None,
+                 mask: Optional[torch.Tensor] = None, maps: bool = False) -> WalkRegions:
+    """The agent's walk region of every state of a batch (``pw_walk_regions``) on the current stream, no wait: where the agent
+    can go without displacing anything, the canonical agent position, and how many push moves are available anywhere in the
+    region (``offset``; ``region_size > 0`` and ``offset[i + 1] > offset[i]`` is the "any push available" mask).
+    ``puzzle_id`` int32 [n]; ``pos`` int8 [n, NP, 2] (None: the initial states); ``mask`` 0 skips an item; ``maps``: also the
+    walk maps (2 bytes per cell of the set's largest board and item).  ``.pushes()`` lists the push moves."""
+    engine = engine_or_vec if isinstance(engine_or_vec, _capi.Engine) else getattr(engine_or_vec, "engine", None)
+    if not isinstance(engine, _capi.Engine):
+        raise ValueError("engine_or_vec must be a VecPushWorld or an _capi.Engine")
+    dev, npad = engine.device, int(engine.np)
+    n = _walk_inputs(puzzle_id, pos, mask, npad, dev)
+    out = WalkRegions(engine, puzzle_id, pos, mask)
+    out.region_size = torch.empty((n,), dtype=torch.int32, device=dev)
+    out.canon = torch.empty((n, 2), dtype=torch.int8, device=dev)
+    out.offset = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    if maps:
+        out.walk_map = torch.empty((n, engine.pset.max_height, engine.pset.max_width), dtype=torch.uint16, device=dev)
+    engine.walk_regions(puzzle_id, pos, mask, out.region_size, out.canon, out.offset, out.walk_map)
+    return out
+
+
+class PushSearch:
+    """Breadth-first search over pushes: the nodes are canonical states (the other movables, and the agent at the smallest
+    position of its walk region), the successors of a node are the push moves available anywhere in the region.  One layer
+    of pushes per round: ``pw_walk_regions`` + ``pw_walk_pushes`` on the frontier, ``pw_walk_regions`` on the successors for
+    their canonical positions, an exact dedupe against the closed set on the device (``torch.unique`` over the packed rows).
+
+    After ``solve``: ``layer_states`` -- the new canonical states of every completed layer before the one that met a goal;
+    ``num_states`` -- the canonical states closed (when a goal was met: up to and including the goal row's successor, what a
+    FIFO search has closed at its first goal); ``pushes`` -- the pushes of the plan (None without one); ``push_rows`` and
+    ``largest_region`` -- push moves listed and the largest walk region seen."""
+
+    def __init__(self, puzzle, max_states: int = 1 << 20):
+        self.puzzle = puzzle
+        self._engine = puzzle._engine()
+        self.device = self._engine.device
+        self.num_objects = puzzle.num_movables
+        self.puzzle_index = int(getattr(puzzle, "puzzle_index", 0))
+        self.max_states = int(max_states)
+        if self.max_states < 1:
+            raise ValueError("max_states must be >= 1")
+        self.layer_states: List[int] = []
+        self.num_states = 0
+        self.pushes: Optional[int] = None
+        self.push_rows = 0
+        self.largest_region = 0
+
+    def _ids(self, n: int) -> torch.Tensor:
+        return torch.full((n,), self.puzzle_index, dtype=torch.int32, device=self.device)
+
+    def _keys(self, pos: torch.Tensor, canon: torch.Tensor) -> torch.Tensor:
+        """The packed canonical states: the rows of ``pos`` with the agent's slot replaced by ``canon``, as bytes."""
+        k = pos.clone()
+        k[:, 0, :] = canon
+        return k.view(torch.uint8).reshape(pos.shape[0], -1)
+
+    def solve(self, start: Optional[Sequence[Tuple[int, int]]] = None, max_pushes: Optional[int] = None,
+              stop_at_goal: bool = True) -> Optional[List[int]]:
+        """Primitive actions of a plan with the fewest pushes (the first goal row in frontier order, then row order; the walks
+        between pushes are shortest), ``[]`` for a start that is a goal, or None when the space (or ``max_pushes``) is exhausted
+        without one.  ``stop_at_goal=False`` searches on through goal states until the space is exhausted and returns None.
+        ``ValueError`` beyond ``max_states`` closed states."""
+        eng, dev, npad, N = self._engine, self.device, int(self._engine.np), self.num_objects
+        state0 = tuple(tuple(int(v) for v in xy) for xy in (self.puzzle.initial_state if start is None else start))
+        if len(state0) != N:
+            raise ValueError("start must hold one (x, y) pair per movable")
+        self.layer_states, self.pushes, self.push_rows, self.largest_region = [], None, 0, 0
+        self.num_states = 1
+        if any(not -128 <= v <= 127 for xy in state0 for v in xy):
+            raise ValueError("start has a movable outside the grid")
+        frontier = torch.zeros((1, npad, 2), dtype=torch.int8, device=dev)
+        frontier[0, :N] = torch.tensor(state0, dtype=torch.int8)
+        first = walk_regions(eng, self._ids(1), frontier)
+        if int(first.region_size[0].item()) < 0:
+            raise ValueError("start has a movable outside the grid")
+        if stop_at_goal and self.puzzle.is_goal_state(state0):
+            self.pushes = 0
+            return []
+        closed = self._keys(frontier, first.canon)
+        # per closed state: the state as it was reached, and the push that reached it (parent index, from, action)
+        real, parent = [frontier], [torch.full((1,), -1, dtype=torch.int64, device=dev)]
+        frm, action = [torch.zeros((1, 2), dtype=torch.int8, device=dev)], [torch.zeros((1,), dtype=torch.uint8, device=dev)]
+        base, depth, goal = 0, 0, None  # base: closed index of the frontier's first state
+        while frontier.shape[0] > 0 and (max_pushes is None or depth < max_pushes):
+            depth += 1
+            F = frontier.shape[0]
+            reg = walk_regions(eng, self._ids(F), frontier)
+            rows = reg.pushes()
+            T = rows.num_rows
+            self.push_rows += T
+            self.largest_region = max(self.largest_region, int(reg.region_size.max().item()))
+            if T == 0:
+                self.layer_states.append(0)
+                break
+            succ = walk_regions(eng, self._ids(T), rows.next_pos)
+            ok = succ.region_size > 0
+            keys = self._keys(rows.next_pos, succ.canon)
+            C = closed.shape[0]
+            _, inv = torch.unique(torch.cat([closed, keys]), dim=0, return_inverse=True)
+            lowest = torch.full((int(inv.max().item()) + 1,), C + T, dtype=torch.int64, device=dev)
+            lowest.scatter_reduce_(0, inv, torch.arange(C + T, device=dev), "amin")
+            # a row is new when it is the first of its canonical state and no closed state holds it
+            is_new = (lowest[inv[C:]] == torch.arange(C, C + T, device=dev)) & ok
+            new_rows = torch.nonzero(is_new).reshape(-1)  # (ascending: frontier order, then row order)
+            goal_rows = torch.nonzero(rows.goal != 0).reshape(-1) if stop_at_goal else new_rows[:0]
+            if goal_rows.numel() > 0:
+                g = int(goal_rows[0].item())
+                self.num_states = C + int((new_rows <= g).sum().item())
+                goal = (base + int(rows.item[g].item()), tuple(int(v) for v in rows.frm[g].tolist()), int(rows.action[g].item()))
+                break
+            M = int(new_rows.numel())
+            if C + M > self.max_states:
+                raise ValueError(f"PushSearch: more than max_states = {self.max_states} canonical states")
+            self.layer_states.append(M)
+            self.num_states = C + M
+            frontier = rows.next_pos[new_rows].contiguous()
+            closed = torch.cat([closed, keys[new_rows]])
+            real.append(frontier)
+            parent.append(base + rows.item[new_rows].to(torch.int64))
+            frm.append(rows.frm[new_rows])
+            action.append(rows.action[new_rows])
+            base = C
+        if goal is None:
+            return None
+        # the chain of pushes back to the start, then the walks between them from the walk maps of the states on the chain
+        par, frs, acs = torch.cat(parent).cpu().numpy(), torch.cat(frm).cpu().numpy(), torch.cat(action).cpu().numpy()
+        chain = [goal]
+        while par[chain[-1][0]] >= 0:
+            k = chain[-1][0]
+            chain.append((int(par[k]), (int(frs[k][0]), int(frs[k][1])), int(acs[k])))
+        chain.reverse()
+        states = torch.cat(real)[torch.tensor([k for k, _, _ in chain], device=dev)].contiguous()
+        maps = walk_regions(eng, self._ids(len(chain)), states, maps=True)
+        plan: List[int] = []
+        for i, (_, q, a) in enumerate(chain):
+            plan += maps.path(i, q) + [a]
+        self.pushes = len(chain)
+        return plan

@@ -405,6 +405,19 @@ class VecPushWorld:
                 self.engine.render(out.puzzle_id, out.pos, storage)
         return out
 
+    def walk_regions(self, maps: bool = False):
+        """A ``search.WalkRegions`` of every environment's current state: where the agent can walk without displacing anything
+        (``region_size``, the canonical position ``canon``, the walk maps on request) and how many push moves are available
+        (``offset``).  One launch on the current stream over the live ``puzzle_id`` / ``pos``, no wait, no host round trip."""
+        from .search import walk_regions
+
+        return walk_regions(self.engine, self.puzzle_id, self.pos, maps=maps)
+
+    def push_moves(self):
+        """A ``search.PushMoves``: every push move available to every environment from its current state (``item`` is the
+        environment) -- the push-level action space.  Waits once, for the number of rows."""
+        return self.walk_regions().pushes()
+
     def solution_table(self, puzzle_index: int, max_states: int = 1 << 22):
         """A ``search.SolutionTable`` -- the exact cost-to-go, optimal actions and dead ends of every reachable state -- of
         puzzle ``puzzle_index`` of this batch's set, in the set's object order: query it with ``puzzle_id`` / ``pos`` as they
