@@ -1099,6 +1099,59 @@ int pw_walk_pushes(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int
                    int32_t* row_walk, uint32_t* row_moved, uint8_t* row_goal, int8_t* row_next_pos, int64_t* dropped,
                    void* stream);
 
+/* Breadth-first search over pushes with its closed set on the device (K16).  A node is a canonical state: the packed positions
+ * with the agent's pair replaced by canon(s).  The store keeps, per node, the state as reached (the agent where the push left
+ * it) and its canon; state 0 is the start.  Layer d + 1 holds the successors of the push moves of layer d's states: the states
+ * in store order, a state's push moves in pw_walk_pushes' (y, x, action) order; a successor is appended when it lies inside
+ * its grid, its canonical state is not in the closed set, and it is the first row in that order with that canonical state.
+ * The numbering is therefore that of a sequential search and independent of PW_OPT_SEARCH_CHUNK (parents per pass, read at
+ * creation; 0 = 2^16) and of the order in which workgroups ran.  The closed set is a table in HBM of fingerprint | store index
+ * entries, a power of two of at least 2 (max_states + 1) slots; a fingerprint match is always confirmed against the canonical
+ * state in the store, so two different canonical states are never merged and equal ones never both kept, at every number of
+ * movables.  PW_OPT_PUSH_SEARCH_FP_BITS (read at creation) keeps fewer fingerprint bits and changes no result.
+ * Links of a state: parent (store index, -1 for the start), from (the agent position the push started from), action (0xFF for
+ * the start), walk (dist(from) in the parent's walk region), goal (1: a goal state).
+ * With stop_at_goal the search ends in the first layer that holds a push move into a goal state: the successor of the first
+ * such row is the last state of the store (states == goal index + 1) and the rows after it are not published; a start that is
+ * a goal state ends it at once (pw_push_search_expand then returns PW_EINVAL).  Without, it runs on through goal states until
+ * a layer is empty.
+ * Device memory: 2 NP + 22 bytes per state of max_states (NP = the engine's padded number of movables) and 16 .. 32 bytes of
+ * table; per push row of the largest pass 2 NP + 4 ceil(N / 2) + 52 bytes of workspace, which starts at 4 096 rows and grows on demand;
+ * pw_push_search_begin clears the table (8 bytes per slot).  The search
+ * owns its workspace: a pw_walk_regions call of the user's does not disturb it.  A state's walk region is flooded once, as a
+ * successor: its region size and push count are kept in the store (8 of those bytes).
+ * pw_push_search_expand waits once per pass for the pass's row count and once at the end of the layer.
+ * PW_EINVAL before any launch, pw_last_error naming the function and the argument: a null handle, engine, out or info;
+ * max_states outside 1 .. 2^31 - 1; a puzzle index outside the set; a start with a movable outside its grid; a range or an
+ * index outside the store; a call before pw_push_search_begin.  PW_ELIMIT from pw_push_search_expand when the store is full:
+ * the layer is incomplete, info is filled in, and every later call of it fails until the next pw_push_search_begin. */
+#define PW_OPT_PUSH_SEARCH_FP_BITS 52 /* pw_push_search_create (read at creation): fingerprint bits of the closed set's entries, 1 .. 32
+                                         (0 = default, 32).  With 1 or 2 almost every probe meets an equal fingerprint and the exact
+                                         comparison decides: for tests */
+typedef struct PwPushSearch PwPushSearch;
+int  pw_push_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, PwPushSearch** out);
+void pw_push_search_destroy(PwPushSearch* s);
+/* start: host int8 [N][2] (x, y) or NULL = the initial state.  PW_EINVAL for a movable outside its grid. */
+int  pw_push_search_begin(PwPushSearch* s, const int8_t* start, int32_t stop_at_goal, void* stream);
+/* one layer of pushes; synchronises.
+   info[0] depth of the new layer
+   info[1] states in it (0: exhausted)
+   info[2] states in the store
+   info[3] goal index, or -1
+   info[4] push rows listed in this layer
+   info[5] largest walk region seen so far */
+int  pw_push_search_expand(PwPushSearch* s, int64_t info[6], void* stream);
+/* device outputs, any may be NULL:
+   pos int8 [count][npad][2], the state as reached, padding zeroed
+   canon int8 [count][2] */
+int  pw_push_search_read_states(PwPushSearch* s, int64_t first, int64_t count, int8_t* pos, int8_t* canon, void* stream);
+int  pw_push_search_read_links(PwPushSearch* s, int64_t first, int64_t count, int32_t* parent, int8_t* from,
+                               uint8_t* action, int32_t* walk, uint8_t* goal, void* stream);
+/* Primitive actions from the start to state `index`, ending with the push that reached it.  The walks between pushes are the
+   parent actions of pw_walk_regions' map.  Host buffer.  Returns the length (nothing written if > cap), or an error.
+   pushes (may be NULL) receives the number of pushes on the chain. */
+int  pw_push_search_plan(PwPushSearch* s, int64_t index, uint8_t* actions, int32_t cap, int32_t* pushes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -238,6 +238,13 @@ SIGNATURES = {
                                 c_void_p, c_int32, c_int32, c_void_p]),
     "pw_walk_pushes": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_create": (c_int, [c_void_p, c_int32, c_int64, POINTER(c_void_p)]),
+    "pw_push_search_destroy": (None, [c_void_p]),
+    "pw_push_search_begin": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_push_search_expand": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_read_states": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_read_links": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_plan": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
 }
 
 # pw_plan_replay_check verdicts and the `include` choices (include/pushworld_amd.h)
@@ -277,6 +284,7 @@ OPTIONS = {
     "search_batch_groups_per_cu": 28,  # pw_search_batch: persistent workgroups per CU (0 = automatic)
     "expand_groups_per_cu": 27,  # ... persistent workgroups per CU (0 = automatic)
     "step_quad16": 31,         # 16 x 16 whole-grid boards, four lanes per environment: 0 / "auto", 2 / "never"
+    "push_search_fp_bits": 52, # closed set of the push searches created afterwards: fingerprint bits kept, 1 .. 32 (0 = default, 32)
     "search_keys": 33,         # closed set of the searches created afterwards: 0 / "fingerprint" (default), 1 / "exact" 63-bit keys where they fit
     "expand_pair_dims": 34,    # pw_expand4 (tables in LDS): 0 / "auto" pair tables sized per pair where the uniform ones exceed 16 KB, 2 / "never"
     "step_quad16_puzzles": 32, # read-only: puzzles of the set that fit
@@ -1159,3 +1167,50 @@ class Engine:
                 mb.handle = None  # (pw_engine_destroy closes an open mailbox itself)
             lib.pw_engine_destroy(h)
             self.handle = None
+
+
+class PushSearchHandle:
+    """A ``PwPushSearch`` (``pw_push_search_*``: breadth-first search over pushes, closed set on the device) of puzzle
+    ``puzzle_index`` of ``engine``'s set.  Thin: every method is one call of the C ABI on the current stream."""
+
+    def __init__(self, engine: "Engine", puzzle_index: int, max_states: int):
+        self.engine = engine  # (keeps the engine alive as long as the search)
+        self.handle = None
+        h = c_void_p()
+        check(lib.pw_push_search_create(engine.handle, int(puzzle_index), int(max_states), ctypes.byref(h)))
+        self.handle = h
+
+    def begin(self, start, stop_at_goal: bool) -> None:
+        """``start``: None, or a bytes object of N (x, y) int8 pairs."""
+        check(lib.pw_push_search_begin(self.handle, start, 1 if stop_at_goal else 0, self.engine._stream()))
+
+    def expand(self):
+        """(return code, the six info values): PW_ELIMIT comes back with the info filled in."""
+        info = (c_int64 * 6)()
+        rc = lib.pw_push_search_expand(self.handle, info, self.engine._stream())
+        return rc, tuple(int(v) for v in info)
+
+    def read_states(self, first, count, pos, canon) -> None:
+        check(lib.pw_push_search_read_states(self.handle, int(first), int(count), _ptr(pos), _ptr(canon), self.engine._stream()))
+
+    def read_links(self, first, count, parent, frm, action, walk, goal) -> None:
+        check(lib.pw_push_search_read_links(self.handle, int(first), int(count), _ptr(parent), _ptr(frm), _ptr(action),
+                                            _ptr(walk), _ptr(goal), self.engine._stream()))
+
+    def plan(self, index: int):
+        """(actions, pushes) of the way from the start to state ``index``."""
+        cap, pushes = 256, c_int32()
+        while True:
+            buf = (ctypes.c_uint8 * cap)()
+            n = check(lib.pw_push_search_plan(self.handle, int(index), buf, cap, ctypes.byref(pushes), self.engine._stream()))
+            if n <= cap:
+                return [int(buf[i]) for i in range(n)], int(pushes.value)
+            cap = n
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.pw_push_search_destroy(h)
+        self.handle = None
+
+    __del__ = close

@@ -666,6 +666,7 @@ int pw_engine_create(const PwPuzzleSet* s, const PwEngineConfig* cfg, PwEngine**
   e->page_slice_envs = 0;
   e->search_chunk = 0;
   e->search_keys = 0;
+  e->push_search_fp_bits = 0;
   e->expand_pair_dims = 0;
   e->step_lds_tables = 0;
   e->step_wide_groups = 0;
@@ -2121,6 +2122,10 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
       if (value != 0 && value != 1) return pw_fail(PW_EINVAL, "PW_OPT_SEARCH_KEYS: 0 fingerprinted entries, 1 exact keys where they fit");
       e->search_keys = static_cast<int>(value);
       return PW_OK;
+    case PW_OPT_PUSH_SEARCH_FP_BITS:
+      if (value < 0 || value > 32) return pw_fail(PW_EINVAL, "PW_OPT_PUSH_SEARCH_FP_BITS: 0 default, 1 .. 32 fingerprint bits");
+      e->push_search_fp_bits = static_cast<int>(value);
+      return PW_OK;
     case PW_OPT_STEP_QUAD16:
       if (value != 0 && value != 2) return pw_fail(PW_EINVAL, "PW_OPT_STEP_QUAD16: 0 automatic, 2 never");
       e->step_quad16 = static_cast<int>(value);
@@ -2297,6 +2302,7 @@ int64_t pw_engine_get_option(const PwEngine* e, int32_t option) try {
       return n;
     }
     case PW_OPT_SEARCH_KEYS: return e->search_keys;
+    case PW_OPT_PUSH_SEARCH_FP_BITS: return e->push_search_fp_bits;
     case PW_OPT_MAILBOX_MODE: return e->mailbox_mode;
     case PW_OPT_EXPAND_PAIR_DIMS: return e->expand_pair_dims;
     case PW_OPT_STEP_QUAD16_PUZZLES: return e->quad_puzzles;

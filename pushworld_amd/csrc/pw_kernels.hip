@@ -148,6 +148,7 @@ struct PwEngine {
   int64_t page_slice_envs; // PW_OPT_PAGE_SLICE_ENVS: environments per page-kernel launch (0 = what 2^31 chunks allow)
   int64_t search_chunk;    // PW_OPT_SEARCH_CHUNK: parents per pw_search_expand pass (0 = 2^20)
   int search_keys;         // PW_OPT_SEARCH_KEYS: closed set of pw_search_*: 0 fingerprinted entries, 1 exact 63-bit keys where the state packs
+  int push_search_fp_bits;  // PW_OPT_PUSH_SEARCH_FP_BITS: fingerprint bits of pw_push_search_create's closed set (0 = 32)
   int step_mixed;          // PW_OPT_STEP_MIXED_GROUPS: lanes per environment chosen per workgroup on N_pad 8 / 16 sets (0 auto, 2 never)
   int step_wide_groups;    // PW_OPT_STEP_WIDE_GROUPS: 32 lanes per environment for N_pad 32 instead of two movables per lane
   int64_t step_lane_batch; // PW_OPT_STEP_LANE_BATCH: state-only launches from this batch size on run one lane per environment
@@ -420,4 +421,5 @@ struct PageRec {
 #include "pw_plan_batch.inc"
 #include "pw_plan_replay.inc"
 #include "pw_walk.inc"
+#include "pw_push_search.inc"
 #include "pw_generate.inc"

@@ -354,7 +354,8 @@ static void walk_launch(PwEngine* e, WalkArgs& a, hipStream_t st) {
   a.ovl_dir = e->d_ovl_dir;
   a.num_puzzles = e->set->count;
   a.rows = std::min(std::max(e->set->max_h, 1), PW_MAX_DIM);
-  a.next_item = reinterpret_cast<uint32_t*>(e->d_replay + 64 * (e->replay_seq++ & 63u));
+  // the item counter: the caller's own (pw_push_search.inc), else the next of the replay workspace's
+  if (!a.next_item) a.next_item = reinterpret_cast<uint32_t*>(e->d_replay + 64 * (e->replay_seq++ & 63u));
   (void)hipMemsetAsync(a.next_item, 0, 4, st);
   const int tab = e->ovl_puzzles == 0 ? 0 : (e->ovl_puzzles == e->set->count ? 2 : 1);
   const int gs = a.npad <= 8 ? 8 : a.npad;

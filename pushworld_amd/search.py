@@ -1588,3 +1588,157 @@ class PushSearch:
             plan += maps.path(i, q) + [a]
         self.pushes = len(chain)
         return plan
+
+
+class PushLayerInfo(tuple):
+    """(depth, new_states, total_states, goal_index, push_rows, largest_region) of one ``PushBreadthFirstSearch.expand``."""
+
+    depth = property(lambda self: self[0])
+    new_states = property(lambda self: self[1])
+    total_states = property(lambda self: self[2])
+    goal_index = property(lambda self: self[3])
+    push_rows = property(lambda self: self[4])
+    largest_region = property(lambda self: self[5])
+
+
+class PushBreadthFirstSearch:
+    """Breadth-first search over pushes with the closed set, the store and the links on the device (``pw_push_search_*``,
+    DESIGN.md K16): ``PushSearch``'s nodes, numbering, plans and counters, shaped like ``BreadthFirstSearch``.  A layer is one
+    ``expand``; the closed set is a hash table in HBM, exact at every number of movables.
+
+    Args:
+        puzzle: a ``PushWorldPuzzle`` or ``SetPuzzle``.
+        max_states: capacity of the store (device memory ~ ``max_states * (2 NP + 22)`` bytes plus 16 .. 32 bytes of table).
+        stop_at_goal: end in the first layer that holds a push into a goal state; False: search on until a layer is empty.
+        chunk: parents per pass (default 2^16; tests use small values to force many passes per layer).
+
+    After ``solve`` (or any ``expand``): ``layer_states``, ``num_states``, ``pushes``, ``push_rows``, ``largest_region`` with
+    ``PushSearch``'s meaning; ``layers`` [(first index, count)] per depth, ``goal_index``, ``exhausted``."""
+
+    def __init__(self, puzzle, max_states: int = 1 << 20, stop_at_goal: bool = True, chunk: Optional[int] = None):
+        self._handle = None
+        self.max_states = int(max_states)
+        if not 1 <= self.max_states < 1 << 31:  # (before an engine is asked for)
+            raise ValueError("max_states must be in 1 .. 2^31 - 1")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError("chunk must be >= 1")
+        self.puzzle = puzzle
+        self._engine = puzzle._engine()
+        self.device = self._engine.device
+        self.num_objects = puzzle.num_movables
+        self.puzzle_index = int(getattr(puzzle, "puzzle_index", 0))
+        self.stop_at_goal = bool(stop_at_goal)
+        self._engine.set_option("search_chunk", 0 if chunk is None else int(chunk))
+        try:
+            self._handle = _capi.PushSearchHandle(self._engine, self.puzzle_index, self.max_states)
+        finally:
+            self._engine.set_option("search_chunk", 0)
+        self._reset()
+        self._begun = False
+
+    def _reset(self) -> None:
+        self.layer_states: List[int] = []
+        self.layers: List[Tuple[int, int]] = []
+        self.num_states = 0
+        self.pushes: Optional[int] = None
+        self.push_rows = 0
+        self.largest_region = 0
+        self.goal_index = -1
+        self.exhausted = False
+
+    def begin(self, start: Optional[Sequence[Tuple[int, int]]] = None) -> None:
+        """Starts a search from ``start`` (a reference-style state, default: the initial state).  ``ValueError`` for a start
+        with a movable outside the grid."""
+        state0 = tuple(tuple(int(v) for v in xy) for xy in (self.puzzle.initial_state if start is None else start))
+        if len(state0) != self.num_objects or any(len(xy) != 2 for xy in state0):
+            raise ValueError("start must hold one (x, y) pair per movable")
+        if self._handle is None:
+            raise ValueError("the search is closed")
+        if any(not -128 <= v <= 127 for xy in state0 for v in xy):
+            raise ValueError("start has a movable outside the grid")
+        self._begun = False
+        self._reset()
+        try:
+            self._handle.begin(None if start is None else bytes(v & 0xFF for xy in state0 for v in xy), self.stop_at_goal)
+        except ValueError as exc:
+            raise ValueError(f"start has a movable outside the grid ({exc})") from None
+        self._begun = True
+        self.num_states = 1
+        self.layers = [(0, 1)]
+        if self.stop_at_goal and self.puzzle.is_goal_state(state0):
+            self.goal_index, self.pushes = 0, 0
+
+    def expand(self) -> PushLayerInfo:
+        """One layer of pushes from the newest layer; ``ValueError`` when the store is full."""
+        if not self._begun:
+            raise ValueError("begin() has not been called")
+        rc, info = self._handle.expand()
+        if rc in (_capi.PW_OK, _capi.PW_ELIMIT):
+            depth, new, total, goal, rows, largest = info
+            if rc == _capi.PW_OK or total > self.num_states:
+                self.push_rows += rows
+                self.largest_region = largest
+                self.num_states = total
+                self.goal_index = goal
+                if new:
+                    self.layers.append((total - new, new))
+        _capi.check(rc)
+        if goal >= 0:
+            self.pushes = depth
+        else:
+            self.layer_states.append(new)
+            self.exhausted = new == 0
+        return PushLayerInfo(info)
+
+    def states(self, first: int = 0, count: Optional[int] = None):
+        """(pos int8 [count, NP, 2] the states as reached, canon int8 [count, 2]) of states ``first .. first + count - 1``,
+        on the device."""
+        count = self.num_states - first if count is None else count
+        pos = torch.empty((count, int(self._engine.np), 2), dtype=torch.int8, device=self.device)
+        canon = torch.empty((count, 2), dtype=torch.int8, device=self.device)
+        self._handle.read_states(first, count, pos, canon)
+        return pos, canon
+
+    def links(self, first: int = 0, count: Optional[int] = None):
+        """(parent int32, from int8 [count, 2], action uint8, walk int32, goal uint8) device tensors; the start state has
+        parent -1 and action 0xFF."""
+        count = self.num_states - first if count is None else count
+        parent = torch.empty((count,), dtype=torch.int32, device=self.device)
+        frm = torch.empty((count, 2), dtype=torch.int8, device=self.device)
+        action = torch.empty((count,), dtype=torch.uint8, device=self.device)
+        walk = torch.empty((count,), dtype=torch.int32, device=self.device)
+        goal = torch.empty((count,), dtype=torch.uint8, device=self.device)
+        self._handle.read_links(first, count, parent, frm, action, walk, goal)
+        return parent, frm, action, walk, goal
+
+    def plan(self, index: int) -> List[int]:
+        """Primitive actions from the start to state ``index``: shortest walks between the pushes of its chain of links."""
+        if not self._begun:
+            raise ValueError("begin() has not been called")
+        return self._handle.plan(index)[0]
+
+    def solve(self, max_pushes: Optional[int] = None) -> Optional[List[int]]:
+        """As ``PushSearch.solve``: a plan with the fewest pushes, ``[]`` for a start that is a goal state, None when the space
+        (or ``max_pushes``) is exhausted without one.  ``ValueError`` beyond ``max_states``."""
+        if not self._begun:
+            self.begin()
+        while self.goal_index < 0 and not self.exhausted:
+            if max_pushes is not None and len(self.layer_states) >= max_pushes:
+                return None
+            self.expand()
+        return self.plan(self.goal_index) if self.goal_index >= 0 else None
+
+    def close(self) -> None:
+        h = getattr(self, "_handle", None)
+        if h is not None:
+            h.close()
+        self._handle = None
+        self._begun = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
