@@ -1114,7 +1114,10 @@ int pw_walk_pushes(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int
  * With stop_at_goal the search ends in the first layer that holds a push move into a goal state: the successor of the first
  * such row is the last state of the store (states == goal index + 1) and the rows after it are not published; a start that is
  * a goal state ends it at once (pw_push_search_expand then returns PW_EINVAL).  Without, it runs on through goal states until
- * a layer is empty.
+ * a layer is empty.  From a state with overlaps a push move can carry a movable out of its grid.  Such a successor is no
+ * candidate of the closed set and is never appended -- unless it is that first goal row's: then it is still the last state of
+ * the store, as reached, with canon (0, 0) and region size -1 (what pw_walk_regions gives a skipped item), and it is the one
+ * state of a store that owns no entry of the closed set.
  * Device memory: 2 NP + 22 bytes per state of max_states (NP = the engine's padded number of movables) and 16 .. 32 bytes of
  * table; per push row of the largest pass 2 NP + 4 ceil(N / 2) + 52 bytes of workspace, which starts at 4 096 rows and grows on demand;
  * pw_push_search_begin clears the table (8 bytes per slot).  The search

@@ -1550,7 +1550,11 @@ class PushSearch:
             C = closed.shape[0]
             _, inv = torch.unique(torch.cat([closed, keys]), dim=0, return_inverse=True)
             lowest = torch.full((int(inv.max().item()) + 1,), C + T, dtype=torch.int64, device=dev)
-            lowest.scatter_reduce_(0, inv, torch.arange(C + T, device=dev), "amin")
+            # a successor outside its grid (canon (0, 0), which a successor inside can share) closes nothing: it takes no
+            # part in the choice of the first row of a canonical state
+            order = torch.arange(C + T, device=dev)
+            order[C:][~ok] = C + T
+            lowest.scatter_reduce_(0, inv, order, "amin")
             # a row is new when it is the first of its canonical state and no closed state holds it
             is_new = (lowest[inv[C:]] == torch.arange(C, C + T, device=dev)) & ok
             new_rows = torch.nonzero(is_new).reshape(-1)  # (ascending: frontier order, then row order)
