@@ -167,7 +167,11 @@ void build_overlap_tables(const PwPuzzleSet* s, int mode, std::vector<uint64_t>&
       for (int y = -1; y <= H - oj.h + 1; y++) {
         uint64_t bits = 0;
         for (int x = -1; x <= W - oj.w + 1; x++) {
-          bool ov = false;
+          // a position that is not entirely inside the grid counts as "overlapping a wall now": a movable there is never
+          // stopped by a wall (the bounds clause, puzzle.py:557-561 -- the reference's tables hold in-bounds positions only),
+          // whatever gaps its shape has where the border wall is.  (An object entering such a position comes from the edge
+          // of the grid, where its tight bounding box overlaps the border wall already: no new verdict for positions inside.)
+          bool ov = x < 0 || y < 0 || x + oj.w > W || y + oj.h > H;
           for (int r = 0; r < oj.h && !ov; r++) {
             const int yy = y + r;
             if (yy < 0 || yy >= H) continue;

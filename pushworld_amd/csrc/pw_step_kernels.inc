@@ -426,9 +426,28 @@ __device__ __forceinline__ uint64_t lane_row_shifted(const P& p, const LaneObj& 
   return act == 0 ? r >> 1 : (act == 1 ? r << 1 : r);
 }
 
+// the object lies entirely inside its grid: only there can a wall stop it (the bounds clause, puzzle.py:557-561 -- the
+// reference's wall tables hold in-bounds positions only).  The row tests below place an object's rows at its grid column,
+// which they can do for an object inside the grid alone.
+template <typename P>
+__device__ __forceinline__ bool lane_inside(const P& p, const LaneObj& o) {
+  return o.x >= 0 && o.y >= 0 && o.x + o.w <= static_cast<int>(p.h->W) && o.y + o.h <= static_cast<int>(p.h->H);
+}
+
+// row yy of object o in the frame whose column 0 is grid column x0, wherever on or around the grid the object lies
+// (cells left of x0 or 64 and more columns right of it vanish)
+template <typename P>
+__device__ __forceinline__ uint64_t lane_row_rel(const P& p, const LaneObj& o, int yy, int x0) {
+  const int rr = yy - o.y, sh = o.x - x0;
+  uint64_t r = 0;
+  if (static_cast<unsigned>(rr) < static_cast<unsigned>(o.h)) r = p.shapes[o.off + rr];
+  return sh >= 0 ? (sh < 64 ? r << sh : 0ull) : (sh > -64 ? r >> -sh : 0ull);
+}
+
 // moving o collides with the static rows and o does not overlap them now (puzzle.py:522-564)
 template <typename P, typename Rows>
 __device__ __forceinline__ bool lane_blocked(const P& p, const LaneObj& o, Rows rows, int act) {
+  if (!lane_inside(p, o)) return false;
   uint64_t hit = 0, now = 0;
   const int dyy = act == 2 ? -1 : (act == 3 ? 1 : 0);  // rows of the object now and after the move
   for (int yy = o.y + min(dyy, 0); yy < o.y + o.h + max(dyy, 0); yy++) {
@@ -448,11 +467,13 @@ __device__ __forceinline__ bool lane_pushes(const P& p, const LaneObj& a, const 
   uint64_t hit = 0, now = 0;
   // only the rows that hold cells of b AND of the pusher (where it is or where it goes): a one-row agent against a
   // 27-row object is two iterations, not 27
+  // (in b's frame, so that the verdict does not depend on where the pair lies: a movable one cell beyond the grid, at
+  // x = -1 or y = -1, pushes and is pushed like any other)
   const int y0 = max(b.y, a.y + min(dy, 0)), y1 = min(b.y + b.h, a.y + a.h + max(dy, 0));
   for (int yy = y0; yy < y1; yy++) {
-    const uint64_t rb = lane_row(p, b, yy);
-    hit |= lane_row_shifted(p, a, yy, act) & rb;
-    now |= lane_row(p, a, yy) & rb;
+    const uint64_t rb = p.shapes[b.off + yy - b.y];
+    hit |= lane_row_rel(p, a, yy - dy, b.x - dx) & rb;
+    now |= lane_row_rel(p, a, yy, b.x) & rb;
   }
   return hit != 0 && now == 0;
 }
@@ -488,6 +509,7 @@ __device__ __forceinline__ bool small_pushes(uint64_t sa, const LaneObj& a, uint
 // lane_blocked for a small object with board s
 template <typename P, typename Rows>
 __device__ __forceinline__ bool small_blocked(const P& p, uint64_t s, const LaneObj& o, Rows rows, int dx, int dy) {
+  if (!lane_inside(p, o)) return false;
   uint64_t hit = 0, now = 0;
   for (int rr = 0; rr < o.h; rr++) {
     const int yy = o.y + rr, yh = yy + dy;
@@ -547,6 +569,7 @@ __device__ __forceinline__ bool table_blocked(const P& p, int j, const LaneObj& 
 template <typename P>
 __device__ __forceinline__ bool lane_agent_blocked(const P& p, const LaneObj& o, int act) {
   if (o.h > 6) return lane_blocked(p, o, p.awall, act);
+  if (!lane_inside(p, o)) return false;
   uint64_t g[8], sh[8];
 #pragma unroll
   for (int k = 0; k < 8; k++) {
@@ -1071,7 +1094,7 @@ __device__ __forceinline__ bool group_agent_blocked(const P& p, int xy, uint32_t
       hit = ((act == 0 ? src >> 1 : (act == 1 ? src << 1 : src)) & g) != 0ull;
     }
     const unsigned long long hm = __ballot(hit) & gmask, nm = __ballot(now) & gmask;
-    return hm != 0ull && nm == 0ull;
+    return hm != 0ull && nm == 0ull && lane_inside(p, ag);
   }
   if (__ballot(ag.h + 2 > GS) != 0ull) {
     // (the plain row loop, not lane_agent_blocked's unrolled 8-row window: inlined here that window costs every
@@ -1088,7 +1111,7 @@ __device__ __forceinline__ bool group_agent_blocked(const P& p, int xy, uint32_t
     hit = (lane_row_shifted(p, ag, yy, act) & g) != 0ull;
   }
   const unsigned long long hm = __ballot(hit) & gmask, nm = __ballot(now) & gmask;
-  return hm != 0ull && nm == 0ull;
+  return hm != 0ull && nm == 0ull && lane_inside(p, ag);
 }
 
 // The push set of one action for the environment / state held by a lane group (lane j = movable j):
@@ -1312,7 +1335,7 @@ __device__ __forceinline__ uint32_t group_agent_blocked4(const P& p, int xy, uin
   if ((__ballot(((sh << 1) & g) != 0ull) & gmask) != 0ull) m |= 2u;
   if ((__ballot((up & g) != 0ull) & gmask) != 0ull) m |= 4u;
   if ((__ballot((dn & g) != 0ull) & gmask) != 0ull) m |= 8u;
-  return overlapping ? 0u : m;
+  return (overlapping || !lane_inside(p, ag)) ? 0u : m;
 }
 
 // ------------------------------------------------------------------------------------
