@@ -1155,6 +1155,60 @@ int  pw_push_search_read_links(PwPushSearch* s, int64_t first, int64_t count, in
    pushes (may be NULL) receives the number of pushes on the chain. */
 int  pw_push_search_plan(PwPushSearch* s, int64_t index, uint8_t* actions, int32_t cap, int32_t* pushes, void* stream);
 
+/* Best-first search over pushes (K17): K16's nodes, store, closed set and links, expanded in the order of the reference's RGD
+ * heuristic instead of layer by layer.  A node is a canonical state; the store keeps the state as reached and its canon; state 0
+ * is the start; the fields per state are K16's (pos, canon, parent, from, action, walk, goal, region size, push count).
+ * Key: the RGD cost in fewest-tools mode (the reference default) of the state as reached -- the agent stands where the push
+ * left it -- from pw_rgd_* with the handle's budget.  The queue is pw_planner's: integer buckets for finite costs (range 2^22),
+ * then +inf, then NaN (a budget overrun, or a movable off its movement graph).  A finite cost beyond the range ends the run with
+ * PW_ELIMIT; it is never clamped.  Within a bucket the newest entry pops first; the states of one round enter in store order,
+ * so the highest store index pops first.  +inf and NaN states are pushed and popped last, so that "exhausted" means exhausted.
+ * Begin: a start that is a goal state is solved at once (goal index 0, empty plan, nothing pushed).  Otherwise the start is
+ * flooded and published as state 0, as pw_push_search_begin does, and pushed under its key.
+ * A round, in this order:
+ *   1 pop     an empty queue: status PW_PLAN_EXHAUSTED.  Otherwise up to K states, lowest bucket first; rounds += 1, expanded +=
+ *             the number popped, open -= the number popped.
+ *   2 count   T = the sum of the popped states' stored push counts; push rows += T.
+ *   3 limit   states + T > max_states: status PW_PLAN_LIMIT; nothing is appended and the counters keep what 1 and 2 did
+ *             (conservative and deterministic, as pw_planner's stored + 4 K).
+ *   4 rows    the push moves of the popped states in pop order, a state's in pw_walk_pushes' (y, x, action) order.
+ *   5 append  a successor is appended when it lies inside its grid, its canonical state is not closed, and it is the first row
+ *             in that order with that canonical state (the lowest row owns it: K16's atomicMin rule, so the numbering does not
+ *             depend on which workgroup ran first).
+ *   6 goal    the successor of the first row (in that order) into a goal state is the last state of the store, published even
+ *             if it owns no entry of the closed set (K16's stop_at_goal rule, its out-of-grid goal row included); status
+ *             PW_PLAN_SOLVED, goal index = states - 1; nothing is pushed in that round.
+ *   7 push    otherwise every new state is evaluated and pushed in store order; largest region takes the maximum of the new
+ *             states' region sizes.
+ * The plan is pw_push_search_plan's: the chain of parents (bounded by the number of states, not by a depth), the walks between
+ * pushes taken from the parent actions of the walk maps.
+ * pw_push_planner_run runs at most max_rounds rounds (<= 0: to the end) and waits once per round: it reads the status and T
+ * together, grows the row workspace if T asks for it, and enqueues the rest of the round.  After an end (solved, exhausted,
+ * limit) it returns the same info again; pw_push_planner_begin starts afresh.
+ *   info[0] status (PW_PLAN_RUNNING, PW_PLAN_SOLVED, PW_PLAN_EXHAUSTED, PW_PLAN_LIMIT)
+ *   info[1] rounds           info[2] expanded         info[3] states in the store    info[4] open
+ *   info[5] goal index, or -1                         info[6] RGD budget overruns since begin
+ *   info[7] push rows        info[8] largest region   info[9] largest finite key pushed, or -1
+ * Device memory: K16's per state and per row, 16 bytes of queue per state of max_states, 16 MiB of bucket heads, and per push
+ * row of the largest round 4 N + 20 bytes of keys.  PW_OPT_PUSH_SEARCH_FP_BITS applies as in K16.
+ * PW_EINVAL before any launch, pw_last_error naming the function and the argument: a null handle, engine, out or info;
+ * max_states outside 1 .. 2^31 - 1; batch outside 1 .. 65 536; a negative rgd_budget; a puzzle index outside the set; a start
+ * with a movable outside its grid; a range outside the store; run, plan or a read before begin; plan when the search is not
+ * solved. */
+typedef struct PwPushPlanner PwPushPlanner;
+int  pw_push_planner_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_t batch /* K, 1 .. 65536 */,
+                            int64_t rgd_budget /* 0 = default */, PwPushPlanner** out);
+void pw_push_planner_destroy(PwPushPlanner* p);
+/* start: host int8 [N][2] (x, y) or NULL = the initial state.  Synchronises. */
+int  pw_push_planner_begin(PwPushPlanner* p, const int8_t* start, void* stream);
+int  pw_push_planner_run(PwPushPlanner* p, int64_t max_rounds /* <= 0: to the end */, int64_t info[10], void* stream);
+/* as pw_push_search_read_states / pw_push_search_read_links, over the states counted by the last run (1 after begin) */
+int  pw_push_planner_read_states(PwPushPlanner* p, int64_t first, int64_t count, int8_t* pos, int8_t* canon, void* stream);
+int  pw_push_planner_read_links(PwPushPlanner* p, int64_t first, int64_t count, int32_t* parent, int8_t* from,
+                                uint8_t* action, int32_t* walk, uint8_t* goal, void* stream);
+/* The plan to the goal state, as pw_push_search_plan (host buffer; returns the length, nothing written if > cap). */
+int  pw_push_planner_plan(PwPushPlanner* p, uint8_t* actions, int32_t cap, int32_t* pushes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -245,6 +245,13 @@ SIGNATURES = {
     "pw_push_search_read_states": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "pw_push_search_read_links": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_search_plan": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pw_push_planner_create": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int64, POINTER(c_void_p)]),
+    "pw_push_planner_destroy": (None, [c_void_p]),
+    "pw_push_planner_begin": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "pw_push_planner_run": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "pw_push_planner_read_states": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "pw_push_planner_read_links": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_planner_plan": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
 }
 
 # pw_plan_replay_check verdicts and the `include` choices (include/pushworld_amd.h)
@@ -1211,6 +1218,54 @@ class PushSearchHandle:
         h = getattr(self, "handle", None)
         if h and lib is not None:
             lib.pw_push_search_destroy(h)
+        self.handle = None
+
+    __del__ = close
+
+
+class PushPlannerHandle:
+    """A ``PwPushPlanner`` (``pw_push_planner_*``: best-first search over pushes, RGD-ordered) of puzzle ``puzzle_index`` of
+    ``engine``'s set.  Thin: every method is one call of the C ABI on the current stream."""
+
+    def __init__(self, engine: "Engine", puzzle_index: int, max_states: int, batch: int, rgd_budget: int):
+        self.engine = engine  # (keeps the engine alive as long as the search)
+        self.handle = None
+        h = c_void_p()
+        check(lib.pw_push_planner_create(engine.handle, int(puzzle_index), int(max_states), int(batch), int(rgd_budget),
+                                         ctypes.byref(h)))
+        self.handle = h
+
+    def begin(self, start) -> None:
+        """``start``: None, or a bytes object of N (x, y) int8 pairs."""
+        check(lib.pw_push_planner_begin(self.handle, start, self.engine._stream()))
+
+    def run(self, max_rounds: int):
+        """The ten info values after at most ``max_rounds`` rounds (<= 0: to the end)."""
+        info = (c_int64 * 10)()
+        check(lib.pw_push_planner_run(self.handle, int(max_rounds), info, self.engine._stream()))
+        return tuple(int(v) for v in info)
+
+    def read_states(self, first, count, pos, canon) -> None:
+        check(lib.pw_push_planner_read_states(self.handle, int(first), int(count), _ptr(pos), _ptr(canon), self.engine._stream()))
+
+    def read_links(self, first, count, parent, frm, action, walk, goal) -> None:
+        check(lib.pw_push_planner_read_links(self.handle, int(first), int(count), _ptr(parent), _ptr(frm), _ptr(action),
+                                             _ptr(walk), _ptr(goal), self.engine._stream()))
+
+    def plan(self):
+        """(actions, pushes) of the way from the start to the goal state."""
+        cap, pushes = 256, c_int32()
+        while True:
+            buf = (ctypes.c_uint8 * cap)()
+            n = check(lib.pw_push_planner_plan(self.handle, buf, cap, ctypes.byref(pushes), self.engine._stream()))
+            if n <= cap:
+                return [int(buf[i]) for i in range(n)], int(pushes.value)
+            cap = n
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.pw_push_planner_destroy(h)
         self.handle = None
 
     __del__ = close

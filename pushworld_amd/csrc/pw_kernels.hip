@@ -422,4 +422,5 @@ struct PageRec {
 #include "pw_plan_replay.inc"
 #include "pw_walk.inc"
 #include "pw_push_search.inc"
+#include "pw_push_planner.inc"
 #include "pw_generate.inc"

@@ -95,6 +95,7 @@ struct PushSearchArgs {
   int64_t max_states, first;
   int32_t rows;     // T
   int32_t parents;  // P
+  const int32_t* plist;  // store index of parent rank i (the best-first search's pop list), or NULL: first + i
   int8_t* pos;
   int8_t* canon;
   int32_t* parent;
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(256) void pw_push_search_publish_kernel(PushSearchA
   uint32_t* dst = reinterpret_cast<uint32_t*>(a.pos + idx * a.npad * 2);
   for (int k = 0; k < a.npad / 2; k++) dst[k] = src[k];
   reinterpret_cast<int16_t*>(a.canon)[idx] = reinterpret_cast<const int16_t*>(a.s_canon)[r];
-  a.parent[idx] = static_cast<int32_t>(a.first + a.row_item[r]);
+  a.parent[idx] = a.plist ? a.plist[a.row_item[r]] : static_cast<int32_t>(a.first + a.row_item[r]);
   reinterpret_cast<int16_t*>(a.from)[idx] = reinterpret_cast<const int16_t*>(a.row_from)[r];
   a.action[idx] = a.row_action[r];
   a.walk[idx] = a.row_walk[r];
@@ -452,6 +453,45 @@ static void push_search_regions(PwPushSearch* s, const int8_t* pos, int32_t n, i
   walk_launch(s->eng, w, st);
 }
 
+// One pass over `a.parents` parents at `fpos` (contiguous rows; their scanned push counts in d_f_offset, a.rows = the total,
+// the row buffers reserved): the two floods, candidate, claim, flags, scan, publish, finish.  Shared by the breadth-first
+// search (a range of the store) and the best-first search (pw_push_planner.inc: a gathered pop list, a.plist).
+static hipError_t push_search_pass(PwPushSearch* s, const PushSearchArgs& a, const int8_t* fpos, hipStream_t st) {
+  const int64_t T = a.rows;
+  WalkArgs w{};
+  w.puzzle_id = s->d_ids;
+  w.pos = fpos;
+  w.n = a.parents;
+  w.npad = s->npad;
+  w.emit = 1;
+  w.offset = s->d_f_offset;
+  w.cap = T;
+  w.row_item = s->d_row_item;
+  w.row_from = s->d_row_from;
+  w.row_action = s->d_row_action;
+  w.row_walk = s->d_row_walk;
+  w.row_goal = s->d_row_goal;
+  w.row_next_pos = s->d_row_next;
+  w.next_item = s->d_counter;
+  walk_launch(s->eng, w, st);
+  push_search_regions(s, s->d_row_next, a.rows, s->d_s_size, s->d_s_canon, s->d_s_offset, nullptr, s->d_ids, st);
+  const dim3 grid(static_cast<unsigned>((T + 255) / 256)), block(256);
+  hipLaunchKernelGGL(pw_push_search_candidate_kernel, grid, block, 0, st, a);
+  hipLaunchKernelGGL(pw_push_search_claim_kernel, grid, block, 0, st, a);
+  hipLaunchKernelGGL(pw_push_search_flag_kernel, grid, block, 0, st, a);
+  size_t tmp = s->r_scan_bytes;
+  const hipError_t err = rocprim::exclusive_scan(s->d_r_scan, tmp, s->d_flag, s->d_rank, 0u, static_cast<size_t>(T) + 1,
+                                                 rocprim::plus<uint32_t>(), st);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(pw_push_search_publish_kernel, grid, block, 0, st, a);
+  hipLaunchKernelGGL(pw_push_search_finish_kernel, dim3(1), dim3(64), 0, st, a);
+  return hipSuccess;
+}
+
+static int push_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int64_t parents, PwPushSearch** out);
+static int push_search_plan(PwPushSearch* s, int64_t index, int64_t chain_cap, uint8_t* actions, int32_t cap, int32_t* pushes,
+                            void* stream);
+
 extern "C" {
 
 void pw_push_search_destroy(PwPushSearch* s) {
@@ -469,6 +509,16 @@ int pw_push_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, PwPus
   if (!out) return pw_fail(PW_EINVAL, "pw_push_search_create: null out");
   if (max_states < 1 || max_states >= (1ll << 31)) return pw_fail(PW_EINVAL, "pw_push_search_create: max_states must be in 1 .. 2^31 - 1");
   if (puzzle < 0 || puzzle >= e->set->count) return pw_fail(PW_EINVAL, "pw_push_search_create: puzzle index out of range");
+  return push_search_create(e, puzzle, max_states, 0, out);
+} catch (...) {
+  return pw_current_exception();  // nothing C++ leaves the C ABI
+}
+
+}  // extern "C"
+
+// (the arguments are checked; parents > 0: that many parents per pass whatever PW_OPT_SEARCH_CHUNK says -- the best-first
+// search's K)
+static int push_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int64_t parents, PwPushSearch** out) {
   PwPushSearch* s = new (std::nothrow) PwPushSearch();
   if (!s) return pw_fail(PW_ENOMEM, "pw_push_search_create: out of memory");
   std::memset(static_cast<void*>(s), 0, sizeof(*s));
@@ -481,7 +531,7 @@ int pw_push_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, PwPus
   s->fp_bits = e->push_search_fp_bits > 0 ? e->push_search_fp_bits : 32;  // PW_OPT_PUSH_SEARCH_FP_BITS
   s->max_states = max_states;
   const int64_t chunk = e->search_chunk > 0 ? e->search_chunk : (1 << 16);  // PW_OPT_SEARCH_CHUNK
-  s->chunk = static_cast<int32_t>(std::min<int64_t>(std::min<int64_t>(chunk, 1 << 24), max_states));
+  s->chunk = static_cast<int32_t>(parents > 0 ? parents : std::min<int64_t>(std::min<int64_t>(chunk, 1 << 24), max_states));
   uint64_t slots = 1024;
   while (slots < 2ull * (static_cast<uint64_t>(max_states) + 1ull)) slots <<= 1;  // load factor below one half
   s->table_slots = slots;
@@ -518,9 +568,9 @@ int pw_push_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, PwPus
   }
   *out = s;
   return PW_OK;
-} catch (...) {
-  return pw_current_exception();  // nothing C++ leaves the C ABI
 }
+
+extern "C" {
 
 int pw_push_search_begin(PwPushSearch* s, const int8_t* start, int32_t stop_at_goal, void* stream) try {
   if (!s) return pw_fail(PW_EINVAL, "pw_push_search_begin: null search");
@@ -611,33 +661,8 @@ int pw_push_search_expand(PwPushSearch* s, int64_t info_out[6], void* stream) tr
     a.first = s->layer_begin + off;
     a.parents = static_cast<int32_t>(std::min<int64_t>(s->chunk, nlayer - off));
     a.rows = static_cast<int32_t>(T);
-    WalkArgs w{};
-    w.puzzle_id = s->d_ids;
-    w.pos = fpos;
-    w.n = a.parents;
-    w.npad = s->npad;
-    w.emit = 1;
-    w.offset = s->d_f_offset;
-    w.cap = T;
-    w.row_item = s->d_row_item;
-    w.row_from = s->d_row_from;
-    w.row_action = s->d_row_action;
-    w.row_walk = s->d_row_walk;
-    w.row_goal = s->d_row_goal;
-    w.row_next_pos = s->d_row_next;
-    w.next_item = s->d_counter;
-    walk_launch(s->eng, w, st);
-    push_search_regions(s, s->d_row_next, a.rows, s->d_s_size, s->d_s_canon, s->d_s_offset, nullptr, s->d_ids, st);
-    const dim3 grid(static_cast<unsigned>((T + 255) / 256)), block(256);
-    hipLaunchKernelGGL(pw_push_search_candidate_kernel, grid, block, 0, st, a);
-    hipLaunchKernelGGL(pw_push_search_claim_kernel, grid, block, 0, st, a);
-    hipLaunchKernelGGL(pw_push_search_flag_kernel, grid, block, 0, st, a);
-    tmp = s->r_scan_bytes;
-    err = rocprim::exclusive_scan(s->d_r_scan, tmp, s->d_flag, s->d_rank, 0u, static_cast<size_t>(T) + 1,
-                                  rocprim::plus<uint32_t>(), st);
+    err = push_search_pass(s, a, fpos, st);
     if (err != hipSuccess) break;
-    hipLaunchKernelGGL(pw_push_search_publish_kernel, grid, block, 0, st, a);
-    hipLaunchKernelGGL(pw_push_search_finish_kernel, dim3(1), dim3(64), 0, st, a);
   }
   if (err == hipSuccess) err = hipGetLastError();
   // the layer's read: what its last pass left
@@ -716,28 +741,35 @@ int pw_push_search_plan(PwPushSearch* s, int64_t index, uint8_t* actions, int32_
   if (cap < 0) return pw_fail(PW_EINVAL, "pw_push_search_plan: cap must be >= 0");
   if (!s->begun) return pw_fail(PW_EINVAL, "pw_push_search_plan: pw_push_search_begin has not been called");
   if (index < 0 || index >= s->layer_end) return pw_fail(PW_EINVAL, "pw_push_search_plan: state index out of bounds");
+  return push_search_plan(s, index, s->depth + 1, actions, cap, pushes, stream);  // (a chain has one state per layer)
+} catch (...) {
+  return pw_current_exception();  // nothing C++ leaves the C ABI
+}
+
+}  // extern "C"
+
+// (the arguments are checked; chain_cap bounds the chain of links: the layers of a breadth-first search, the states of a
+// best-first one)
+static int push_search_plan(PwPushSearch* s, int64_t index, int64_t chain_cap64, uint8_t* actions, int32_t cap, int32_t* pushes,
+                            void* stream) {
   PwDeviceGuard guard(s->eng->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int32_t chain_cap = static_cast<int32_t>(std::min<int64_t>(s->depth + 1, (1ll << 31) - 2));
+  const int32_t chain_cap = static_cast<int32_t>(std::min<int64_t>(chain_cap64, (1ll << 31) - 2));
   const int map_h = s->eng->set->max_h, map_w = s->eng->set->max_w;
   const size_t cells = static_cast<size_t>(map_h) * map_w, row = static_cast<size_t>(s->npad) * 2;
-  // one allocation for the plan's device buffers: chain + length, ids, sizes, offsets, positions, links, maps
+  // two allocations for the plan's device buffers: chain + length, then, sized by the chain found: ids, sizes, offsets,
+  // positions, links, maps
   struct Release {
     void* p = nullptr;
     ~Release() {
       if (p) (void)hipFree(p);
     }
-  } mem;
+  } chain_mem, mem;
   const size_t L0 = static_cast<size_t>(chain_cap);
-  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-  const size_t o_chain = 0, o_ids = o_chain + up((L0 + 1) * 4), o_size = o_ids + up(L0 * 4), o_off = o_size + up(L0 * 4),
-               o_pos = o_off + up((L0 + 1) * 8), o_from = o_pos + up(L0 * row), o_act = o_from + up(L0 * 2),
-               o_walk = o_act + up(L0), o_map = o_walk + up(L0 * 4), bytes = o_map + up(L0 * cells * 2);
-  hipError_t err = hipMalloc(&mem.p, bytes);
+  hipError_t err = hipMalloc(&chain_mem.p, (L0 + 1) * 4);
   if (err != hipSuccess)
     return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_push_search_plan: ") + hipGetErrorString(err));
-  uint8_t* base = static_cast<uint8_t*>(mem.p);
-  int32_t* d_chain = reinterpret_cast<int32_t*>(base + o_chain);
+  int32_t* d_chain = static_cast<int32_t*>(chain_mem.p);
   int32_t* d_len = d_chain + L0;
   hipLaunchKernelGGL(pw_push_search_chain_kernel, dim3(1), dim3(64), 0, st, s->d_parent, index, chain_cap, d_chain, d_len);
   int32_t len = 0;
@@ -748,6 +780,14 @@ int pw_push_search_plan(PwPushSearch* s, int64_t index, uint8_t* actions, int32_
   if (pushes) *pushes = len;
   if (len == 0) return 0;
   const size_t L = static_cast<size_t>(len);
+  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+  const size_t o_ids = 0, o_size = o_ids + up(L * 4), o_off = o_size + up(L * 4), o_pos = o_off + up((L + 1) * 8),
+               o_from = o_pos + up(L * row), o_act = o_from + up(L * 2), o_walk = o_act + up(L), o_map = o_walk + up(L * 4),
+               bytes = o_map + up(L * cells * 2);
+  err = hipMalloc(&mem.p, bytes);
+  if (err != hipSuccess)
+    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_push_search_plan: ") + hipGetErrorString(err));
+  uint8_t* base = static_cast<uint8_t*>(mem.p);
   int32_t* d_ids = reinterpret_cast<int32_t*>(base + o_ids);
   int8_t* d_gpos = reinterpret_cast<int8_t*>(base + o_pos);
   int8_t* d_gfrom = reinterpret_cast<int8_t*>(base + o_from);
@@ -796,8 +836,4 @@ int pw_push_search_plan(PwPushSearch* s, int64_t index, uint8_t* actions, int32_
     }
   }
   return static_cast<int>(total);
-} catch (...) {
-  return pw_current_exception();  // nothing C++ leaves the C ABI
 }
-
-}  // extern "C"

@@ -11,6 +11,7 @@ import sys
 USAGE = """\
 usage: python -m pushworld_amd.run_planner <mode> <puzzle> [--batch K] [--max-states M] [--actions fixed|reference]
        python -m pushworld_amd.run_planner --pushes <puzzle> [--max-states M]
+       python -m pushworld_amd.run_planner --pushes --best-first <puzzle> [--batch K] [--max-states M]
 
 Solves a PushWorld puzzle by best-first search on the GPU and prints the plan as a line of
 (L)eft, (R)ight, (U)p, (D)own actions, or "NO SOLUTION" when the puzzle has none.
@@ -22,6 +23,7 @@ Solves a PushWorld puzzle by best-first search on the GPU and prints the plan as
   --max-states  capacity of the state store (default 2^24); the search gives up when it is reached
   --actions     order of the four actions per expanded state: "reference" (default) or "fixed" (L R U D)
   --pushes      breadth-first search over pushes instead (no <mode>): a plan with the fewest pushes
+  --best-first  with --pushes: best-first search over pushes in RGD order, K states per round (--batch)
 """
 
 
@@ -33,8 +35,12 @@ def main(argv=None) -> int:
     ap.add_argument("--max-states", type=int, default=1 << 24)
     ap.add_argument("--actions", choices=("fixed", "reference"), default="reference")
     ap.add_argument("--pushes", action="store_true")
+    ap.add_argument("--best-first", action="store_true", dest="best_first")
     ap.add_argument("-h", "--help", action="store_true")
     args = ap.parse_args(argv)
+    if args.best_first and not args.pushes:
+        sys.stderr.write("ERROR: --best-first needs --pushes\n")
+        return 1
     if args.pushes and args.puzzle is None:
         args.mode, args.puzzle = "PUSHES", args.mode
     if args.help or args.mode is None or args.puzzle is None:
@@ -44,11 +50,14 @@ def main(argv=None) -> int:
         sys.stderr.write(f"ERROR: Unrecognized mode: {args.mode}\n")
         return 1
     from .puzzle import PushWorldPuzzle
-    from .search import PushBreadthFirstSearch, solve
+    from .search import PushBestFirstSearch, PushBreadthFirstSearch, solve
 
     try:
         pz = PushWorldPuzzle(args.puzzle, order="cpp")
-        if args.pushes:
+        if args.pushes and args.best_first:
+            with PushBestFirstSearch(pz, batch=args.batch, max_states=min(args.max_states, (1 << 31) - 1)) as search:
+                plan = search.solve()
+        elif args.pushes:
             with PushBreadthFirstSearch(pz, max_states=min(args.max_states, (1 << 31) - 1)) as search:
                 plan = search.solve()
         else:

@@ -1746,3 +1746,140 @@ class PushBreadthFirstSearch:
         self.close()
 
     __del__ = close
+
+
+class PushPlannerInfo(tuple):
+    """(status, rounds, expanded, states, open, goal_index, rgd_exceeded, push_rows, largest_region, largest_key) of a
+    ``PushBestFirstSearch``."""
+
+    status = property(lambda self: PLAN_STATUS[self[0]])
+    rounds = property(lambda self: self[1])
+    expanded = property(lambda self: self[2])
+    states = property(lambda self: self[3])
+    open = property(lambda self: self[4])
+    goal_index = property(lambda self: self[5])
+    rgd_exceeded = property(lambda self: self[6])
+    push_rows = property(lambda self: self[7])
+    largest_region = property(lambda self: self[8])
+    largest_key = property(lambda self: self[9])
+
+
+class PushBestFirstSearch:
+    """Best-first search over pushes (``pw_push_planner_*``): ``PushBreadthFirstSearch``'s nodes, store,
+    closed set and links, expanded in the order of the RGD heuristic (fewest tools) of the state as reached, ``batch`` = K
+    states per round.  See ``pw_push_planner_create`` in include/pushworld_amd.h for the exact semantics.
+
+    Args:
+        puzzle: a ``PushWorldPuzzle`` or ``SetPuzzle``.
+        batch: states popped per round, 1 .. 65536.
+        max_states: capacity of the store; a round whose push rows could overflow it is not expanded (status ``limit``).
+        rgd_budget: RGD recursion frames per state (None: the default); states beyond it get NaN keys and pop last.
+
+    After ``run``: ``info`` (``PushPlannerInfo``), ``num_states``, ``goal_index``; after ``plan``: ``pushes``."""
+
+    def __init__(self, puzzle, batch: int = 1, max_states: int = 1 << 20, rgd_budget: Optional[int] = None):
+        self._handle = None
+        self.batch, self.max_states = int(batch), int(max_states)
+        if not 1 <= self.max_states < 1 << 31:  # (before an engine is asked for)
+            raise ValueError("max_states must be in 1 .. 2^31 - 1")
+        if not 1 <= self.batch <= 65536:
+            raise ValueError("batch must be in 1 .. 65536")
+        if rgd_budget is not None and int(rgd_budget) < 1:
+            raise ValueError("rgd_budget must be >= 1 (or None)")
+        self.puzzle = puzzle
+        self._engine = puzzle._engine()
+        self.device = self._engine.device
+        self.num_objects = puzzle.num_movables
+        self.puzzle_index = int(getattr(puzzle, "puzzle_index", 0))
+        self._handle = _capi.PushPlannerHandle(self._engine, self.puzzle_index, self.max_states, self.batch,
+                                               0 if rgd_budget is None else int(rgd_budget))
+        self._reset()
+        self._begun = False
+
+    def _reset(self) -> None:
+        self.info: Optional[PushPlannerInfo] = None
+        self.num_states = 0
+        self.goal_index = -1
+        self.pushes: Optional[int] = None
+
+    def begin(self, start: Optional[Sequence[Tuple[int, int]]] = None) -> None:
+        """Starts a search from ``start`` (a reference-style state, default: the initial state).  ``ValueError`` for a start
+        with a movable outside the grid."""
+        state0 = tuple(tuple(int(v) for v in xy) for xy in (self.puzzle.initial_state if start is None else start))
+        if len(state0) != self.num_objects or any(len(xy) != 2 for xy in state0):
+            raise ValueError("start must hold one (x, y) pair per movable")
+        if self._handle is None:
+            raise ValueError("the search is closed")
+        if any(not -128 <= v <= 127 for xy in state0 for v in xy):
+            raise ValueError("start has a movable outside the grid")
+        self._begun = False
+        self._reset()
+        try:
+            self._handle.begin(None if start is None else bytes(v & 0xFF for xy in state0 for v in xy))
+        except ValueError as exc:
+            raise ValueError(f"start has a movable outside the grid ({exc})") from None
+        self._begun = True
+        self.num_states = 1
+
+    def run(self, max_rounds: Optional[int] = None) -> PushPlannerInfo:
+        """Runs at most ``max_rounds`` rounds (None: until the search is solved, exhausted or at its limit)."""
+        rounds = 0 if max_rounds is None else int(max_rounds)
+        if max_rounds is not None and rounds <= 0:
+            raise ValueError("max_rounds must be positive (or None)")
+        if not self._begun:
+            raise ValueError("begin() has not been called")
+        self.info = PushPlannerInfo(self._handle.run(rounds))
+        self.num_states, self.goal_index = self.info.states, self.info.goal_index
+        return self.info
+
+    def states(self, first: int = 0, count: Optional[int] = None):
+        """(pos int8 [count, NP, 2] the states as reached, canon int8 [count, 2]) of states ``first .. first + count - 1``,
+        on the device."""
+        count = self.num_states - first if count is None else count
+        pos = torch.empty((count, int(self._engine.np), 2), dtype=torch.int8, device=self.device)
+        canon = torch.empty((count, 2), dtype=torch.int8, device=self.device)
+        self._handle.read_states(first, count, pos, canon)
+        return pos, canon
+
+    def links(self, first: int = 0, count: Optional[int] = None):
+        """(parent int32, from int8 [count, 2], action uint8, walk int32, goal uint8) device tensors; the start state has
+        parent -1 and action 0xFF."""
+        count = self.num_states - first if count is None else count
+        parent = torch.empty((count,), dtype=torch.int32, device=self.device)
+        frm = torch.empty((count, 2), dtype=torch.int8, device=self.device)
+        action = torch.empty((count,), dtype=torch.uint8, device=self.device)
+        walk = torch.empty((count,), dtype=torch.int32, device=self.device)
+        goal = torch.empty((count,), dtype=torch.uint8, device=self.device)
+        self._handle.read_links(first, count, parent, frm, action, walk, goal)
+        return parent, frm, action, walk, goal
+
+    def plan(self) -> Optional[List[int]]:
+        """The plan (list of actions 0..3) when the search is solved, else None."""
+        if self.info is None or self.info.status != "solved":
+            return None
+        plan, self.pushes = self._handle.plan()
+        return plan
+
+    def solve(self) -> Optional[List[int]]:
+        """The plan found, ``[]`` for a start that is a goal state, None when the space is exhausted without one.
+        ``RuntimeError`` when ``max_states`` runs out first."""
+        if not self._begun:
+            self.begin()
+        if self.run().status == "limit":
+            raise RuntimeError(f"best-first search over pushes stopped at max_states = {self.max_states} without an answer")
+        return self.plan()
+
+    def close(self) -> None:
+        h = getattr(self, "_handle", None)
+        if h is not None:
+            h.close()
+        self._handle = None
+        self._begun = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
