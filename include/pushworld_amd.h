@@ -1155,6 +1155,74 @@ int  pw_push_search_read_links(PwPushSearch* s, int64_t first, int64_t count, in
    pushes (may be NULL) receives the number of pushes on the chain. */
 int  pw_push_search_plan(PwPushSearch* s, int64_t index, uint8_t* actions, int32_t cap, int32_t* pushes, void* stream);
 
+/* Exact cost-to-go table over pushes (K18), on a PwPushSearch that has been EXHAUSTED: begun with stop_at_goal = 0, its last
+ * pw_push_search_expand reported 0 new states, and the store did not overflow.  Let S be the number of states in the store.
+ * Rows.  State i has npush[i] push rows, in pw_walk_pushes' (y, x, action) order, taken from the state as stored.  row_off
+ * (int64 [S + 1]) is the exclusive scan of npush, R = row_off[S].  For row r of state i:
+ *   succ[r]   int32     the store index of the canonical state of the row's successor; -1 when the successor lies outside its
+ *                       grid (such rows exist from overlapping starts; K16 never appends them)
+ *   from[r]   int8 [2], action[r] uint8: as pw_walk_pushes writes them
+ *   flags[r]  uint8     bit 0 goal (row_goal), bit 1 optimal, bit 2 safe, as defined below
+ *   A successor inside its grid that is missing from the closed set is an internal error: PW_EDEVICE, as in pw_search_solve.
+ * Cost.  Cost is counted in PUSHES and is not a count of moves.  The value of a row is c(r) = 0 when its goal bit is set,
+ * whatever succ[r] is; otherwise c(r) = cost[succ[r]] when succ[r] >= 0; otherwise c(r) is infinite.  cost[i] (int32) is 0 where
+ * the store's goal[i] is 1; elsewhere it is 1 + min_r c(r) over the state's rows; it is -1 where that minimum is infinite: a
+ * dead end, or a state with no rows.
+ * Best row.  best[i] (int32) is the lowest row number k of the state with c(row_off[i] + k) == cost[i] - 1; -1 at goal states
+ * and dead ends.
+ * Row bits.  Row r of state i is optimal iff cost[i] > 0 and c(r) == cost[i] - 1.  It is safe iff c(r) is finite.
+ * info (int64 [5]): states, rows, goal states (cost == 0), dead ends, largest finite cost (-1 when no state has one).
+ * A cost in moves is left out on purpose: the store keeps ONE agent position per canonical state, so a cost in moves is not a
+ * function of the node (as K15's plans over pushes minimise pushes, not moves).  The push set of a state is a function of its
+ * canonical state -- the same region and the same boxes give the same rows in the same order -- so the rows stored for node i
+ * are the rows of any live state that maps to node i; only the walk distances differ.  The query relies on this.
+ *
+ * pw_push_search_solve is synchronous.  PW_EINVAL naming the condition: a null handle or info; a call before
+ * pw_push_search_begin; stop_at_goal set; layers left to expand; an overflowed store.  PW_ELIMIT when R > 2^31 - 1.
+ * pw_push_search_begin and pw_push_search_destroy discard the table.
+ *   successor pass  one pass per PW_OPT_SEARCH_CHUNK parents over the whole store, exactly the front half of a pass of
+ *                   pw_push_search_expand (the counts out of the store, the scan, the rows flood, the regions flood of the
+ *                   successors, the candidates) in the search's own workspace, grown as pw_push_search_expand grows it; the
+ *                   host waits once per pass, for the row count.  A read-only lookup then probes the closed set from the
+ *                   candidate's first slot and accepts a published entry only when the fingerprint matches and the packed
+ *                   canonical state equals the store's words: exact under PW_OPT_PUSH_SEARCH_FP_BITS.  The closed set is never written.
+ *   sweeps          level-synchronous: sweep d gives cost d to every state that is still unset and has a row with c == d - 1,
+ *                   and records the lowest such row.  A sweep after one that changed nothing changes nothing, so 8 sweeps are
+ *                   queued per host read of their changed-counters; the sweeps end at the first that changed nothing and never
+ *                   run more than S times.  A last row pass writes the optimal and safe bits.
+ * Device memory: 16 bytes per state (row_off, cost, best) and 8 bytes per row (succ, from, action, flags) of the table; during
+ * pw_push_search_solve 4 more bytes per row (the row -> state map of the sweeps) and 64 bytes of counters, freed when it returns.
+ * No kernel waits on another workgroup; every loop is bounded by the rows, the slots, S or the 4 095 steps of a walk. */
+int  pw_push_search_solve(PwPushSearch* s, int64_t info[5], void* stream);
+/* states first .. first + count - 1 (row_off: count + 1 values, absolute row numbers) / rows first .. first + count - 1 into device
+   buffers, any of which may be NULL; asynchronous on `stream`.  PW_EINVAL: a null handle, a range outside the table, no table. */
+int  pw_push_search_table_read(PwPushSearch* s, int64_t first_state, int64_t count, int64_t* row_off /* [count + 1] */,
+                               int32_t* cost, int32_t* best, void* stream);
+int  pw_push_search_table_rows(PwPushSearch* s, int64_t first_row, int64_t count, int32_t* succ, int8_t* from, uint8_t* action,
+                               uint8_t* flags, void* stream);
+/* Live states -> table rows and the expert's next action.  puzzle_id / pos / npad / mask and the conventions are
+ * pw_search_table_query's: puzzle_id device int32 [n] or NULL (every item is of the table's puzzle), pos device int8 [n][npad][2],
+ * mask device uint8 [n] or NULL (0 skips an item).  Items of other puzzles and masked items are LEFT UNTOUCHED: several tables fill
+ * one set of outputs for a mixed batch.  For every other item (all outputs are device pointers, any may be NULL):
+ *   index[i]       int32     the store index; -1 when the state is not in the table or a coordinate is outside the grid
+ *   cost[i]        int32     pushes to go; -1 at a dead end; -2 when the state is not in the table
+ *   push_from[i]   int8 [2], push_action[i] uint8: the state's best row, out of the table's rows; (0, 0) and 0xFF when there is none
+ *   walk[i]        int32     dist(push_from) in the LIVE state's walk map; -1 when there is none
+ *   action[i]      int8      the first primitive action of "walk to push_from, then push": push_action when walk == 0, else the
+ *                            parent action of the position at distance 1 on the way back from push_from along the map's parent
+ *                            actions; -1 when there is none (goal, dead end, not in the table)
+ * One small kernel forms the effective mask (mask && id == puzzle), one regions flood runs over the items that take part (the
+ * walk maps are made only when walk or action is asked for), and one kernel with one lane per item applies the lookup of the
+ * successor pass to the live state's own packed canonical state and writes the outputs.
+ * The workspace -- the maps, 2 * map_h * map_w bytes per item at the set's largest dimensions, and 19 bytes of per-item words --
+ * belongs to the handle; it is allocated on first use or growth and synchronises `stream` then.  Otherwise the call is
+ * asynchronous, reads nothing on the host and is capturable.  ONE query at a time per handle.
+ * PW_EINVAL before any launch, pw_last_error naming the function: a null handle, n < 1, a null pos, npad not 4 / 8 / 16 / 32 or
+ * smaller than the set's largest number of movables, no solved table. */
+int  pw_push_search_table_query(PwPushSearch* s, const int32_t* puzzle_id, const int8_t* pos, int32_t npad,
+                                const uint8_t* mask, int32_t n, int32_t* index, int32_t* cost, int8_t* push_from,
+                                uint8_t* push_action, int32_t* walk, int8_t* action, void* stream);
+
 /* Best-first search over pushes (K17): K16's nodes, store, closed set and links, expanded in the order of the reference's RGD
  * heuristic instead of layer by layer.  A node is a canonical state; the store keeps the state as reached and its canon; state 0
  * is the start; the fields per state are K16's (pos, canon, parent, from, action, walk, goal, region size, push count).

@@ -245,6 +245,11 @@ SIGNATURES = {
     "pw_push_search_read_states": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "pw_push_search_read_links": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_search_plan": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pw_push_search_solve": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_table_read": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_table_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_table_query": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_planner_create": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int64, POINTER(c_void_p)]),
     "pw_push_planner_destroy": (None, [c_void_p]),
     "pw_push_planner_begin": (c_int, [c_void_p, c_void_p, c_void_p]),
@@ -1213,6 +1218,25 @@ class PushSearchHandle:
             if n <= cap:
                 return [int(buf[i]) for i in range(n)], int(pushes.value)
             cap = n
+
+    def solve(self):
+        """The five info values of ``pw_push_search_solve``: states, rows, goal states, dead ends, largest finite cost."""
+        info = (c_int64 * 5)()
+        check(lib.pw_push_search_solve(self.handle, info, self.engine._stream()))
+        return tuple(int(v) for v in info)
+
+    def table_read(self, first, count, row_off, cost, best) -> None:
+        check(lib.pw_push_search_table_read(self.handle, int(first), int(count), _ptr(row_off), _ptr(cost), _ptr(best),
+                                            self.engine._stream()))
+
+    def table_rows(self, first, count, succ, frm, action, flags) -> None:
+        check(lib.pw_push_search_table_rows(self.handle, int(first), int(count), _ptr(succ), _ptr(frm), _ptr(action), _ptr(flags),
+                                            self.engine._stream()))
+
+    def table_query(self, puzzle_id, pos, npad, mask, n, index, cost, push_from, push_action, walk, action) -> None:
+        check(lib.pw_push_search_table_query(self.handle, _ptr(puzzle_id), _ptr(pos), int(npad), _ptr(mask), int(n), _ptr(index),
+                                             _ptr(cost), _ptr(push_from), _ptr(push_action), _ptr(walk), _ptr(action),
+                                             self.engine._stream()))
 
     def close(self) -> None:
         h = getattr(self, "handle", None)

@@ -422,5 +422,6 @@ struct PageRec {
 #include "pw_plan_replay.inc"
 #include "pw_walk.inc"
 #include "pw_push_search.inc"
+#include "pw_push_table.inc"
 #include "pw_push_planner.inc"
 #include "pw_generate.inc"

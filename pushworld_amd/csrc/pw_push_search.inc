@@ -86,7 +86,22 @@ struct PwPushSearch {
   int64_t layer_begin, layer_end, depth, goal_index, largest;
   int32_t stop_at_goal;
   bool begun, overflow, ended;
+  // the cost-to-go table of pw_push_search_solve and the query's workspace (pw_push_table.inc)
+  bool t_solved;
+  int64_t t_states, t_rows, t_info[5];
+  int64_t* d_t_row_off;  // [t_states + 1]
+  int32_t* d_t_cost;     // [t_states]
+  int32_t* d_t_best;     // [t_states]
+  int32_t* d_t_succ;     // [t_rows]
+  int8_t* d_t_from;      // [t_rows][2]
+  uint8_t* d_t_action;   // [t_rows]
+  uint8_t* d_t_flags;    // [t_rows]
+  int32_t q_cap;         // items the query's workspace holds
+  bool q_maps;           // ... with their walk maps
+  uint8_t* d_q_mem;      // one allocation: ids, effective mask, region sizes, canon, push counts, maps
 };
+
+static void push_table_discard(PwPushSearch* s);  // (pw_push_table.inc)
 
 struct PushSearchArgs {
   int32_t nw, npad, fp_bits, stop;
@@ -453,10 +468,10 @@ static void push_search_regions(PwPushSearch* s, const int8_t* pos, int32_t n, i
   walk_launch(s->eng, w, st);
 }
 
-// One pass over `a.parents` parents at `fpos` (contiguous rows; their scanned push counts in d_f_offset, a.rows = the total,
-// the row buffers reserved): the two floods, candidate, claim, flags, scan, publish, finish.  Shared by the breadth-first
-// search (a range of the store) and the best-first search (pw_push_planner.inc: a gathered pop list, a.plist).
-static hipError_t push_search_pass(PwPushSearch* s, const PushSearchArgs& a, const int8_t* fpos, hipStream_t st) {
+// The front half of a pass over `a.parents` parents at `fpos` (contiguous rows; their scanned push counts in d_f_offset,
+// a.rows = the total, the row buffers reserved): the two floods and the candidates.  What follows decides what a pass is: claim
+// and publish (push_search_pass), or a read-only lookup (pw_push_table.inc).
+static void push_search_front(PwPushSearch* s, const PushSearchArgs& a, const int8_t* fpos, hipStream_t st) {
   const int64_t T = a.rows;
   WalkArgs w{};
   w.puzzle_id = s->d_ids;
@@ -475,8 +490,15 @@ static hipError_t push_search_pass(PwPushSearch* s, const PushSearchArgs& a, con
   w.next_item = s->d_counter;
   walk_launch(s->eng, w, st);
   push_search_regions(s, s->d_row_next, a.rows, s->d_s_size, s->d_s_canon, s->d_s_offset, nullptr, s->d_ids, st);
+  hipLaunchKernelGGL(pw_push_search_candidate_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, st, a);
+}
+
+// One pass: the front half, then claim, flags, scan, publish, finish.  Shared by the breadth-first search (a range of the
+// store) and the best-first search (pw_push_planner.inc: a gathered pop list, a.plist).
+static hipError_t push_search_pass(PwPushSearch* s, const PushSearchArgs& a, const int8_t* fpos, hipStream_t st) {
+  const int64_t T = a.rows;
+  push_search_front(s, a, fpos, st);
   const dim3 grid(static_cast<unsigned>((T + 255) / 256)), block(256);
-  hipLaunchKernelGGL(pw_push_search_candidate_kernel, grid, block, 0, st, a);
   hipLaunchKernelGGL(pw_push_search_claim_kernel, grid, block, 0, st, a);
   hipLaunchKernelGGL(pw_push_search_flag_kernel, grid, block, 0, st, a);
   size_t tmp = s->r_scan_bytes;
@@ -501,6 +523,8 @@ void pw_push_search_destroy(PwPushSearch* s) {
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   push_search_free_rows(s);
+  push_table_discard(s);
+  if (s->d_q_mem) (void)hipFree(s->d_q_mem);
   delete s;
 }
 
@@ -589,6 +613,7 @@ int pw_push_search_begin(PwPushSearch* s, const int8_t* start, int32_t stop_at_g
   PwDeviceGuard guard(s->eng->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   s->begun = false;
+  push_table_discard(s);
   if (int rc = push_search_reserve_rows(s, 1, st, "pw_push_search_begin")) return rc;  // (the smallest: it grows with the passes)
   const unsigned long long info[PW_PS_I_WORDS] = {1ull, PW_PS_NOGOAL, 0ull, PW_PS_NOGOAL, 0ull, 0ull, 0ull, 0ull};
   hipError_t err = hipMemsetAsync(s->d_table, 0, static_cast<size_t>(s->table_slots) * 8, st);

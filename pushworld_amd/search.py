@@ -9,6 +9,7 @@ shortest plan in that order.
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -1875,6 +1876,186 @@ class PushBestFirstSearch:
             h.close()
         self._handle = None
         self._begun = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+
+# ---- exact cost-to-go tables over pushes (pw_push_search_solve / pw_push_search_table_*) ------------------------
+PUSH_NONE = 0xFF  # ``PushQuery.push_action`` where a state has no best row
+
+
+PushQuery = namedtuple("PushQuery", "index cost action push_from push_action walk")
+PushQuery.__doc__ = """What ``PushSolutionTable.query`` returns: device tensors [n] ([n, 2] for ``push_from``)."""
+
+
+def _push_query_outputs(out, n: int, device) -> PushQuery:
+    """The six tensors a push-table query fills: fresh (-1 / ``COST_UNKNOWN`` / -1 / (0, 0) / ``PUSH_NONE`` / -1) or the
+    checked ``out``."""
+    if out is None:
+        return PushQuery(torch.full((n,), -1, dtype=torch.int32, device=device),
+                         torch.full((n,), COST_UNKNOWN, dtype=torch.int32, device=device),
+                         torch.full((n,), -1, dtype=torch.int8, device=device),
+                         torch.zeros((n, 2), dtype=torch.int8, device=device),
+                         torch.full((n,), PUSH_NONE, dtype=torch.uint8, device=device),
+                         torch.full((n,), -1, dtype=torch.int32, device=device))
+    if not isinstance(out, (tuple, list)) or len(out) != 6:
+        raise ValueError("out must be the PushQuery of an earlier query")
+    for name, t, dtype, shape in zip(PushQuery._fields, out, (torch.int32, torch.int32, torch.int8, torch.int8, torch.uint8,
+                                                              torch.int32), ((n,), (n,), (n,), (n, 2), (n,), (n,))):
+        _dev_tensor(f"out: {name}", t, dtype, shape, device)
+    return PushQuery(*out)
+
+
+class PushSolutionTable:
+    """The exact cost-to-go IN PUSHES of every canonical state reachable in one puzzle: a ``PushBreadthFirstSearch`` with
+    ``stop_at_goal=False`` run to exhaustion, then ``pw_push_search_solve``.  State i of the search has the push rows
+    ``offsets()[i] .. offsets()[i + 1] - 1``, in ``walk_pushes``' (y, x, action) order:
+
+    * ``rows(first, count)``: ``(succ int32, from int8 [count, 2], action uint8, flags uint8)`` -- the store index of the row's
+      successor (-1: it lies outside the grid), the push, and bit 0 goal row, bit 1 optimal, bit 2 safe;
+    * ``costs()`` int32: pushes to go, 0 at goal states, -1 at dead ends (PushWorld is irreversible: a dead end is a property
+      of the boxes alone);
+    * ``best()`` int32: the state's lowest optimal row (relative to its first), -1 at goal states and dead ends.
+
+    A cost in moves is not kept: a node holds one agent position for a whole walk region.
+
+    Args:
+        puzzle: a ``PushWorldPuzzle`` or a ``SetPuzzle``.
+        max_states: capacity of the search; ``ValueError`` ("the state store is full") when the space is larger.
+        start: the state the space is explored from (default: the initial state).
+        chunk: parents per pass, as ``PushBreadthFirstSearch``.
+
+    ``info`` = (states, rows, goal states, dead ends, largest finite cost or -1); ``num_states``, ``num_rows``.
+    Device memory: the search's, plus 16 bytes per state and 8 per row."""
+
+    def __init__(self, puzzle, max_states: int = 1 << 20, start: Optional[Sequence[Tuple[int, int]]] = None,
+                 chunk: Optional[int] = None):
+        self.search = None
+        self.puzzle = puzzle
+        self.search = PushBreadthFirstSearch(puzzle, max_states=max_states, stop_at_goal=False, chunk=chunk)
+        self.puzzle_index = self.search.puzzle_index
+        self.device = self.search.device
+        self.npad = int(self.search._engine.np)
+        try:
+            self.search.begin(start)
+            self.start = tuple(tuple(int(v) for v in xy) for xy in (puzzle.initial_state if start is None else start))
+            while not self.search.exhausted:
+                self.search.expand()
+            self.info = self.search._handle.solve()
+            self.num_states, self.num_rows, self.num_goal_states, self.num_dead_ends, self.max_cost = self.info
+        except Exception:
+            self.search.close()
+            raise
+
+    def _handle(self):
+        if self.search is None or self.search._handle is None:
+            raise ValueError("the table is closed")
+        return self.search._handle
+
+    def states(self, first: int = 0, count: Optional[int] = None):
+        """``PushBreadthFirstSearch.states``: (pos int8 [count, NP, 2] the states as reached, canon int8 [count, 2])."""
+        self._handle()
+        return self.search.states(first, count)
+
+    def offsets(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """int64 [count + 1] on the device: the first row of states ``first .. first + count`` (absolute row numbers)."""
+        h = self._handle()
+        count = self.num_states - first if count is None else count
+        out = torch.empty((max(count, 0) + 1,), dtype=torch.int64, device=self.device)
+        h.table_read(first, count, out, None, None)
+        return out
+
+    def costs(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """int32 [count] on the device: pushes to go, -1 = dead end."""
+        h = self._handle()
+        count = self.num_states - first if count is None else count
+        out = torch.empty((max(count, 0),), dtype=torch.int32, device=self.device)
+        h.table_read(first, count, None, out, None)
+        return out
+
+    def best(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """int32 [count] on the device: the lowest optimal row of each state, -1 where there is none."""
+        h = self._handle()
+        count = self.num_states - first if count is None else count
+        out = torch.empty((max(count, 0),), dtype=torch.int32, device=self.device)
+        h.table_read(first, count, None, None, out)
+        return out
+
+    def rows(self, first: int = 0, count: Optional[int] = None):
+        """(succ int32 [count], from int8 [count, 2], action uint8 [count], flags uint8 [count]) of rows
+        ``first .. first + count - 1``, on the device."""
+        h = self._handle()
+        count = self.num_rows - first if count is None else count
+        n = max(count, 0)
+        succ = torch.empty((n,), dtype=torch.int32, device=self.device)
+        frm = torch.empty((n, 2), dtype=torch.int8, device=self.device)
+        action = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        flags = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        h.table_rows(first, count, succ, frm, action, flags)
+        return succ, frm, action, flags
+
+    def query(self, puzzle_id: Optional[torch.Tensor], pos: torch.Tensor, mask: Optional[torch.Tensor] = None, out=None,
+              actions: bool = True) -> PushQuery:
+        """Looks live states up on the device, on the current stream, no wait once the workspace has its size: ``pos`` int8
+        [n, NP, 2] (the engine's layout, e.g. ``VecPushWorld.pos``), ``puzzle_id`` int32 [n] (None: every item is this
+        table's puzzle), ``mask`` uint8 / bool [n] (0 skips an item).  Returns a ``PushQuery`` of device tensors: the node of
+        each state, its cost in pushes (``COST_DEAD_END`` -1), the first primitive action of "walk to ``push_from``, then
+        push" (-1 where there is none: goal, dead end, not in the table), the best push ``push_from`` / ``push_action``
+        ((0, 0) / ``PUSH_NONE``) and ``walk``, the length of the walk to it in the live state.  A state that is not in the
+        table gives -1 / ``COST_UNKNOWN`` -2 / -1 / (0, 0) / 0xFF / -1.  Items of other puzzles and masked items keep what
+        ``out`` -- the ``PushQuery`` of an earlier call, filled in place -- held.  ``actions=False`` makes no walk maps and
+        leaves ``action`` and ``walk`` as they are.  One query at a time per table."""
+        h = self._handle()
+        n = _pos_inputs(puzzle_id, pos, mask, self.npad, self.device, True)
+        out = _push_query_outputs(out, n, self.device)
+        h.table_query(puzzle_id, pos, self.npad, mask, n, out.index, out.cost, out.push_from, out.push_action,
+                                   out.walk if actions else None, out.action if actions else None)
+        return out
+
+    def optimal_plan(self, start: Optional[Sequence[Tuple[int, int]]] = None) -> Optional[List[int]]:
+        """The primitive actions of a fewest-pushes plan from ``start`` (default: the table's start): at every step the
+        query's action.  [] at a goal state, None at a dead end or from a state that is not in the table."""
+        state = tuple(tuple(int(v) for v in xy) for xy in (self.start if start is None else start))
+        if len(state) != self.search.num_objects or any(len(xy) != 2 for xy in state):
+            raise ValueError("start must hold one (x, y) pair per movable")
+        eng = self.search._engine
+        n2 = 2 * self.search.num_objects
+        pos = torch.zeros((1, self.npad, 2), dtype=torch.int8, device=self.device)
+        host = np.zeros((1, self.npad, 2), np.int8)
+        out = ctypes.create_string_buffer(64)
+        view = memoryview(out).cast("b")
+        plan: List[int] = []
+        limit = None
+        while True:
+            host[0, :len(state)] = np.asarray(state, np.int64).astype(np.int8)
+            pos.copy_(torch.from_numpy(host))
+            q = self.query(None, pos)
+            cost, action = int(q.cost.cpu()[0]), int(q.action.cpu()[0])
+            if cost < 0:
+                return None
+            if cost == 0:
+                return plan
+            if limit is None:
+                limit = cost * 4096
+            if action < 0 or len(plan) >= limit:
+                raise RuntimeError("the table gives no action from a live state (an internal error)")
+            _capi.check(_capi.lib.pw_next_state(eng.handle, self.puzzle_index, bytes(host[0, :len(state)].tobytes()), action,
+                                                out, None))
+            state = tuple(zip(view[0:n2:2], view[1:n2:2]))
+            plan.append(action)
+            if self.puzzle.is_goal_state(state):  # (a goal row may carry a movable out of its grid: no node, and the goal)
+                return plan
+
+    def close(self) -> None:
+        search = getattr(self, "search", None)
+        if search is not None:
+            search.close()
 
     def __enter__(self):
         return self

@@ -456,6 +456,42 @@ class VecPushWorld:
             table.query(self.puzzle_id, self.pos, out=out)
         return out
 
+    def push_table(self, puzzle_index: int, max_states: int = 1 << 20):
+        """A ``search.PushSolutionTable`` -- the exact cost-to-go in pushes, the dead ends and the best push of every canonical
+        state -- of puzzle ``puzzle_index`` of this batch's set, in the set's object order: query it with ``puzzle_id`` /
+        ``pos`` as they are (``push_cost_to_go``).  Explores the puzzle's whole space of canonical states: ``ValueError``
+        beyond ``max_states``."""
+        from .search import PushSolutionTable, SetPuzzle
+
+        if not 0 <= int(puzzle_index) < self.num_puzzles:
+            raise ValueError(f"puzzle_index must be an index into the set (0 .. {self.num_puzzles - 1})")
+        return PushSolutionTable(SetPuzzle(self.pset, int(puzzle_index), engine=self.engine), max_states=max_states)
+
+    def push_cost_to_go(self, tables, mask: Optional[torch.Tensor] = None):
+        """A ``search.PushQuery`` (index, cost, action, push_from, push_action, walk) on the device for every environment's
+        current state, from a list of ``push_table``s (one ``PushSolutionTable.query`` each on the current stream): the cost
+        is in pushes, -1 at a dead end; environments whose puzzle has no table in the list keep -1 / -2 / -1 / (0, 0) /
+        0xFF / -1."""
+        tables = list(tables)
+        for table in tables:
+            if table.search._engine is not self.engine:
+                raise ValueError("the tables must be made on this environment (VecPushWorld.push_table)")
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        from .search import _push_query_outputs
+
+        out = _push_query_outputs(None, self.num_envs, self.device)
+        for table in tables:
+            table.query(self.puzzle_id, self.pos, mask=mask, out=out)
+        return out
+
+    def push_expert_actions(self, tables, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int8 [B] on the device: for every environment the first primitive action of a fewest-pushes plan from its
+        current state ("walk to the best push, then push"), -1 where there is none (a goal state, a dead end, a state or a
+        puzzle without a table, masked out).  One query per table on the current stream after whatever was queued there
+        (e.g. ``step``)."""
+        return self.push_cost_to_go(tables, mask=mask).action
+
     def _own_tables(self, tables) -> list:
         from .search import SolutionTableBatch
 
