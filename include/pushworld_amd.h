@@ -1099,6 +1099,52 @@ int pw_walk_pushes(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int
                    int32_t* row_walk, uint32_t* row_moved, uint8_t* row_goal, int8_t* row_next_pos, int64_t* dropped,
                    void* stream);
 
+/* Stepping by pushes (K19): the push-level action space of K15 acted in.  A choice (from, a) per environment -- an agent
+ * position (x, y) and a uint8 action -- is VALID when a is in 0..3, from lies in the walk region R of the environment's state
+ * and (from, a) is a push move of it.  The macro step of a valid choice is pw_step applied with the actions
+ * L = path(R, from) + [a] in turn (the parent actions of pw_walk_regions from the agent's position to `from`, then the push:
+ * dist(from) + 1 actions), without autoreset inside; it ends after the first step that returns terminated | truncated, or
+ * after the last action.  pw_step_push performs it for a whole batch in one launch and writes
+ *   pos, steps, terminated, truncated   what the last executed pw_step left
+ *   reward  double [batch] or NULL      the sum of the executed steps' rewards, added in execution order ((r1 + r2) + r3) + ...
+ *   dgoals  int8 [batch] or NULL        the sum of the executed steps' dgoals
+ *   moves   int32 [batch] or NULL       the number of primitive steps executed
+ *   status  int8 [batch] or NULL        PW_PUSH_DONE: the push itself was executed; PW_PUSH_CUT: the macro step ended during the
+ *                                       walk -- max_steps was reached (the agent stands on the path where it had got to), or
+ *                                       the state was a goal state already (the first walking step returns terminated)
+ * A choice that is not valid is REFUSED: pos, steps, terminated and truncated stay as they were, reward 0.0, dgoals 0, moves 0,
+ * status PW_PUSH_REFUSED.  That covers a position outside the grid or outside R, a walk move, a move that displaces nothing, an
+ * action outside 0..3 (PUSH_NONE = 0xFF, the best push of a goal state or a dead end, is harmless to feed back in), a puzzle id
+ * outside the set and a movable outside its grid.  There are no 0xFF flags and no bad-action count in this action space.
+ * With PW_STEP_AUTORESET an environment whose terminated | truncated is set on entry is reset exactly as pw_step resets it (the
+ * initial state of puzzle_id[e], steps 0, flags 0, reward 0.0): moves 0, status PW_PUSH_RESET, the choice is not read.
+ * The counters of pw_counters advance as the `moves` executed primitive steps would have advanced them (a reset or a refusal
+ * executes none).  An environment without any push move can never be stepped by this call: that is the caller's business
+ * (status, pw_push_mask, pw_reset with a mask).
+ * pos is in the engine's layout (pw_engine_npad), as for pw_step.  Asynchronous on `stream`, one launch, nothing is read on the
+ * host.  Workspace: none per environment -- the path ancestor a cut needs lives in LDS -- so the call allocates nothing at any
+ * batch size once the engine's replay workspace exists (4 KB of item counters, shared with pw_plan_replay_* and pw_walk_*,
+ * allocated by the first call of any of them; it only ever grows on their demand).
+ * PW_EINVAL before any launch, pw_last_error naming the function and the argument: a null engine, puzzle_id, push_from,
+ * push_action, pos, steps, terminated or truncated; batch < 1; an engine with an open mailbox.
+ *
+ * pw_push_mask writes the dense mask of that action space, inputs and checks as pw_walk_regions (pos NULL: the initial states;
+ * map_h / map_w at least the set's largest dimensions; npad at least its movables): entry [y][x] of item i has bit a set exactly
+ * when ((x, y), a) is a push move of item i, 0 everywhere else and for a skipped item; every entry of every item is written.
+ * num_pushes[i] is the popcount of item i's entries (offset[i + 1] - offset[i] of pw_walk_regions).  One fill and one launch:
+ * the region pass of pw_walk_regions with its push boards written out.  PW_EINVAL as pw_walk_regions, and for a null push_mask. */
+#define PW_PUSH_REFUSED 0
+#define PW_PUSH_DONE 1
+#define PW_PUSH_CUT 2
+#define PW_PUSH_RESET 3
+int pw_step_push(PwEngine* e, const int32_t* puzzle_id, const int8_t* push_from /* [B][2] (x, y) */,
+                 const uint8_t* push_action /* [B] */, int8_t* pos, int32_t* steps, double* reward, int8_t* dgoals,
+                 uint8_t* terminated, uint8_t* truncated, int32_t* moves, int8_t* status,
+                 int32_t batch, uint32_t flags, void* stream);
+int pw_push_mask(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask, int32_t n,
+                 uint8_t* push_mask /* [n][map_h][map_w] */, int32_t* num_pushes /* [n] or NULL */,
+                 int32_t map_h, int32_t map_w, void* stream);
+
 /* Breadth-first search over pushes with its closed set on the device (K16).  A node is a canonical state: the packed positions
  * with the agent's pair replaced by canon(s).  The store keeps, per node, the state as reached (the agent where the push left
  * it) and its canon; state 0 is the start.  Layer d + 1 holds the successors of the push moves of layer d's states: the states

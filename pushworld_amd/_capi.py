@@ -29,6 +29,8 @@ PUZZLE_HEADER_N_OFFSET = 6     # offsetof(PwPuzzleHeader, N): uint32 base, then 
 OBS_U8, OBS_F32 = 0, 1
 PLAN_MAX_ACTIONS = 65536  # PW_PLAN_MAX_ACTIONS of include/pushworld_amd.h: actions per pw_plan_states launch
 STEP_AUTORESET = 1
+# status of an environment after pw_step_push
+PUSH_REFUSED, PUSH_DONE, PUSH_CUT, PUSH_RESET = 0, 1, 2, 3
 
 
 class PwPuzzleInfo(ctypes.Structure):
@@ -238,6 +240,10 @@ SIGNATURES = {
                                 c_void_p, c_int32, c_int32, c_void_p]),
     "pw_walk_pushes": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_step_push": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int32, c_uint32, c_void_p]),
+    "pw_push_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                             c_void_p]),
     "pw_push_search_create": (c_int, [c_void_p, c_int32, c_int64, POINTER(c_void_p)]),
     "pw_push_search_destroy": (None, [c_void_p]),
     "pw_push_search_begin": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
@@ -1165,6 +1171,17 @@ class Engine:
         check(lib.pw_walk_pushes(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(mask), puzzle_id.shape[0],
                                  _ptr(offset), int(cap), _ptr(item), _ptr(frm), _ptr(action), _ptr(walk), _ptr(moved),
                                  _ptr(goal), _ptr(next_pos), _ptr(dropped), self._stream()))
+
+    # stepping by pushes and the dense push mask (pw_step_push / pw_push_mask): device tensors in and out, no wait
+    def step_push(self, puzzle_id, push_from, push_action, pos, steps, reward, dgoals, terminated, truncated, moves=None,
+                  status=None, flags=0):
+        check(lib.pw_step_push(self.handle, _ptr(puzzle_id), _ptr(push_from), _ptr(push_action), _ptr(pos), _ptr(steps),
+                               _ptr(reward), _ptr(dgoals), _ptr(terminated), _ptr(truncated), _ptr(moves), _ptr(status),
+                               pos.shape[0], int(flags), self._stream()))
+
+    def push_mask(self, puzzle_id, pos, mask, push_mask, num_pushes=None):
+        check(lib.pw_push_mask(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(mask), puzzle_id.shape[0],
+                               _ptr(push_mask), _ptr(num_pushes), push_mask.shape[1], push_mask.shape[2], self._stream()))
 
     def expand4(self, puzzle_index, states, succ, moved, goal):
         check(lib.pw_expand4(self.handle, int(puzzle_index), _ptr(states), _ptr(succ), _ptr(moved), _ptr(goal),

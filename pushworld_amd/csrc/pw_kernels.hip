@@ -421,6 +421,7 @@ struct PageRec {
 #include "pw_plan_batch.inc"
 #include "pw_plan_replay.inc"
 #include "pw_walk.inc"
+#include "pw_push_step.inc"
 #include "pw_push_search.inc"
 #include "pw_push_table.inc"
 #include "pw_push_planner.inc"

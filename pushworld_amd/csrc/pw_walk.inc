@@ -19,6 +19,8 @@
 //
 //   regions  pass 1 only: region_size, canon, the walk map (dist | parent << 12, written at discovery) and the number of
 //            push moves into offset[i]; a rocPRIM exclusive scan over n + 1 values turns the counts into row offsets.
+//            With a push_mask (pw_push_mask, pw_push_step.inc) the push boards are written out as one byte per position when an
+//            item's flood ends; region_size / offset may be NULL then and no scan follows.
 //   pushes   pass 1 again (the emitting call recomputes), then pass 2 walks the layers a second time over the walk boards
 //            -- bit operations only -- and calls group_push_set for the push candidates alone: a row's index is its rank in
 //            (y, x, action) order, read off the push boards, its walk distance is the layer.
@@ -44,6 +46,9 @@ struct WalkArgs {
   int64_t* offset;  // regions: written; pushes: read
   uint16_t* walk_map;
   int32_t map_h, map_w;
+  // the push boards written out (pw_push_mask, pw_push_step.inc): region_size / offset may be NULL then
+  uint8_t* push_mask;   // [n][map_h][map_w], zeroed by the caller: bit a of [y][x] = ((x, y), a) is a push move
+  int32_t* num_pushes;  // [n] or NULL
   // pushes
   int64_t cap;
   int32_t* row_item;
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(64) void pw_walk_kernel(WalkArgs a) {
   const int lj = lane & (GS - 1);
   const int gbase = lane & ~(GS - 1);
   const unsigned long long gmask = ((1ull << (GS - 1) << 1) - 1ull) << gbase;
-  if (!a.emit && blockIdx.x == 0 && lane == 0) a.offset[a.n] = 0;  // the scan's last input: offset[n] becomes the total
+  if (!a.emit && a.offset && blockIdx.x == 0 && lane == 0) a.offset[a.n] = 0;  // the scan's last input: offset[n] becomes the total
   uint64_t* const B = pw_walk_lds + static_cast<size_t>(lane / GS) * PW_WALK_BOARDS * a.rows;
   uint64_t* const VIS = B;
   uint64_t* const CUR = B + a.rows;
@@ -158,8 +163,9 @@ __global__ __launch_bounds__(64) void pw_walk_kernel(WalkArgs a) {
           if (skip) {
             if (!a.emit) {
               if (lj == 0) {
-                a.region_size[item] = -1;
-                a.offset[item] = 0;
+                if (a.region_size) a.region_size[item] = -1;
+                if (a.offset) a.offset[item] = 0;
+                if (a.num_pushes) a.num_pushes[item] = 0;
               }
               if (a.canon && lj == 0) reinterpret_cast<int16_t*>(a.canon)[item] = 0;
             }
@@ -250,9 +256,21 @@ __global__ __launch_bounds__(64) void pw_walk_kernel(WalkArgs a) {
       }
       if (!have) {
         if (!a.emit) {
+          if (a.push_mask) {  // (a lane reads the words it wrote itself: every lane of the group wrote all of them)
+            for (int y = lj; y < p.H; y += GS) {
+              const uint64_t r0 = PUSH[y], r1 = PUSH[a.rows + y], r2 = PUSH[2 * a.rows + y], r3 = PUSH[3 * a.rows + y];
+              uint8_t* out = a.push_mask + (static_cast<int64_t>(item) * a.map_h + y) * a.map_w;
+              for (uint64_t m = r0 | r1 | r2 | r3; m != 0ull; m &= m - 1ull) {
+                const int x = __ffsll(static_cast<unsigned long long>(m)) - 1;
+                out[x] = static_cast<uint8_t>(((r0 >> x) & 1ull) | (((r1 >> x) & 1ull) << 1) | (((r2 >> x) & 1ull) << 2) |
+                                              (((r3 >> x) & 1ull) << 3));
+              }
+            }
+          }
           if (lj == 0) {
-            a.region_size[item] = rsize;
-            a.offset[item] = npush;
+            if (a.region_size) a.region_size[item] = rsize;
+            if (a.offset) a.offset[item] = npush;
+            if (a.num_pushes) a.num_pushes[item] = npush;
             if (a.canon) reinterpret_cast<int16_t*>(a.canon)[item] = static_cast<int16_t>((ckey & 63) | ((ckey >> 6) << 8));
           }
           active = false;

@@ -1472,6 +1472,37 @@ def walk_regions(engine_or_vec, puzzle_id: torch.Tensor, pos: Optional[torch.Ten
     return out
 
 
+def push_mask(engine_or_vec, puzzle_id: torch.Tensor, pos: Optional[torch.Tensor] = None,
+              mask: Optional[torch.Tensor] = None):
+    """The dense push mask of every state of a batch (``pw_push_mask``) on the current stream, no wait: ``(push_mask,
+    num_pushes)``, uint8 [n, map_h, map_w] and int32 [n] on the device.  Bit ``a`` of entry ``[y, x]`` is set exactly when
+    ``((x, y), a)`` is a push move of item i -- a row of ``walk_regions(...).pushes()`` -- and ``num_pushes`` counts them;
+    a skipped item (masked out, an id outside the set, a movable outside its grid) holds zeros.  ``map_h`` / ``map_w`` are the
+    set's largest dimensions; inputs as ``walk_regions``."""
+    engine = engine_or_vec if isinstance(engine_or_vec, _capi.Engine) else getattr(engine_or_vec, "engine", None)
+    if not isinstance(engine, _capi.Engine):
+        raise ValueError("engine_or_vec must be a VecPushWorld or an _capi.Engine")
+    dev, npad = engine.device, int(engine.np)
+    n = _walk_inputs(puzzle_id, pos, mask, npad, dev)
+    out = torch.empty((n, engine.pset.max_height, engine.pset.max_width), dtype=torch.uint8, device=dev)
+    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    engine.push_mask(puzzle_id, pos, mask, out, count)
+    return out, count
+
+
+def decode_push_choice(choice: torch.Tensor, map_h: int, map_w: int):
+    """``(push_from int8 [B, 2], push_action uint8 [B])`` of ``choice``, int64 [B] flat indices into ``[4, map_h, map_w]`` (the
+    expanded push mask's shape: ``(a * map_h + y) * map_w + x``), with torch ops on ``choice``'s device.  An index outside
+    the shape decodes to an action outside 0..3, a choice that is no push move."""
+    cells = int(map_h) * int(map_w)
+    inside = (choice >= 0) & (choice < 4 * cells)
+    c = torch.where(inside, choice, torch.zeros_like(choice))
+    action = torch.where(inside, torch.div(c, cells, rounding_mode="floor"), torch.full_like(choice, PUSH_NONE)).to(torch.uint8)
+    cell = c % cells
+    frm = torch.stack((cell % int(map_w), torch.div(cell, int(map_w), rounding_mode="floor")), dim=1).to(torch.int8)
+    return frm.contiguous(), action.contiguous()
+
+
 class PushSearch:
     """Breadth-first search over pushes: the nodes are canonical states (the other movables, and the agent at the smallest
     position of its walk region), the successors of a node are the push moves available anywhere in the region.  One layer

@@ -418,6 +418,76 @@ class VecPushWorld:
         environment) -- the push-level action space.  Waits once, for the number of rows."""
         return self.walk_regions().pushes()
 
+    def push_mask(self, expanded: bool = False):
+        """The push-level action mask of every environment's current state (``pw_push_mask``), on the device, no wait: uint8
+        [B, map_h, map_w] whose entry ``[y, x]`` has bit ``a`` set exactly when ``((x, y), a)`` is a push move (``map_h`` /
+        ``map_w``: the set's largest dimensions); with ``expanded`` bool [B, 4, map_h, map_w], the shape of a policy head's
+        logits over (direction, cell) that ``step_push(choice=...)`` indexes.  ``self.num_pushes`` (int32 [B]) holds the
+        number of push moves of every environment: 0 marks one that ``step_push`` cannot step."""
+        if getattr(self, "_push_mask", None) is None:
+            self._push_mask = torch.empty((self.num_envs, self.pset.max_height, self.pset.max_width), dtype=torch.uint8,
+                                          device=self.device)
+            self.num_pushes = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+            self._push_bits = torch.tensor([1, 2, 4, 8], dtype=torch.uint8, device=self.device).view(1, 4, 1, 1)
+        self.engine.push_mask(self.puzzle_id, self.pos, None, self._push_mask, self.num_pushes)
+        if expanded:
+            return (self._push_mask.unsqueeze(1) & self._push_bits) != 0
+        return self._push_mask
+
+    def step_push(self, push_from: Optional[torch.Tensor] = None, push_action: Optional[torch.Tensor] = None,
+                  choice: Optional[torch.Tensor] = None):
+        """One macro step per environment in the push-level action space (``pw_step_push``): the agent walks to
+        ``push_from`` along the parent actions of its walk region and pushes by ``push_action`` -- bit for bit the loop of
+        ``step`` calls it replaces, ended by the first primitive step that terminates or truncates.
+
+        Args: either ``push_from`` (int8 [B, 2], the agent position (x, y) the push starts from) with ``push_action``
+            (uint8 [B]) -- e.g. ``q.push_from`` / ``q.push_action`` of ``push_cost_to_go``, or a row of ``push_moves`` -- or
+            ``choice``, int64 [B] flat indices into ``[4, map_h, map_w]``, the shape of ``push_mask(expanded=True)``
+            (decoded on the device).
+
+        Returns ``(obs, reward float64[B], terminated uint8[B], truncated uint8[B], moves int32[B], status int8[B])``,
+        views of persistent device buffers (overwritten by the next call).  ``reward`` is the sequential sum of the
+        primitive rewards, ``moves`` the number of primitive steps executed, ``status`` ``PUSH_DONE`` (the push was
+        executed), ``PUSH_CUT`` (the macro step ended during the walk: ``max_steps``, or the state was a goal state
+        already), ``PUSH_REFUSED`` (the choice is no push move of the state -- anything that is not a row of
+        ``push_moves``, ``PUSH_NONE`` included: the environment is left as it was, reward 0, no flag, nothing counted) or
+        ``PUSH_RESET`` (``autoreset``: a finished environment was reset as ``step`` resets it; its choice was not read).
+
+        An environment whose state has no push move at all can never be stepped by this call -- every choice is refused.
+        There is no policy for that here: watch ``status`` or ``push_mask()`` / ``num_pushes`` and ``reset(mask=...)``."""
+        if not self._has_reset:
+            raise RuntimeError("reset() must be called before step_push() can be called.")
+        if choice is not None:
+            if push_from is not None or push_action is not None:
+                raise ValueError("pass either push_from with push_action, or choice")
+            if not isinstance(choice, torch.Tensor) or choice.dtype != torch.int64 or choice.device != self.device \
+                    or choice.shape != self._act_shape:
+                raise ValueError("choice must be an int64 tensor of shape [num_envs] on the engine's device")
+            from .search import decode_push_choice
+
+            push_from, push_action = decode_push_choice(choice, self.pset.max_height, self.pset.max_width)
+        elif push_from is None or push_action is None:
+            raise ValueError("pass either push_from with push_action, or choice")
+        if not isinstance(push_from, torch.Tensor) or push_from.dtype != torch.int8 or push_from.device != self.device \
+                or tuple(push_from.shape) != (self.num_envs, 2) or not push_from.is_contiguous():
+            raise ValueError("push_from must be a contiguous int8 tensor of shape [num_envs, 2] on the engine's device")
+        if not isinstance(push_action, torch.Tensor) or push_action.dtype != torch.uint8 or push_action.device != self.device \
+                or push_action.shape != self._act_shape or not push_action.is_contiguous():
+            raise ValueError("push_action must be a contiguous uint8 tensor of shape [num_envs] on the engine's device")
+        if getattr(self, "push_status", None) is None:
+            self.push_moves_taken = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
+            self.push_status = torch.zeros((self.num_envs,), dtype=torch.int8, device=self.device)
+        if self.resample and self.flags & _capi.STEP_AUTORESET:
+            # finished environments draw the puzzle their autoreset (inside this step) starts from
+            self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
+                                 self.sample_table)
+        self.engine.step_push(self.puzzle_id, push_from, push_action, self.pos, self.steps, self.reward, self.dgoals,
+                              self.terminated, self.truncated, self.push_moves_taken, self.push_status, self.flags)
+        self._obs_current = False
+        if self.obs is not None:
+            self._render()
+        return self.obs, self.reward, self.terminated, self.truncated, self.push_moves_taken, self.push_status
+
     def solution_table(self, puzzle_index: int, max_states: int = 1 << 22):
         """A ``search.SolutionTable`` -- the exact cost-to-go, optimal actions and dead ends of every reachable state -- of
         puzzle ``puzzle_index`` of this batch's set, in the set's object order: query it with ``puzzle_id`` / ``pos`` as they
