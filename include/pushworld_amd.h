@@ -1269,6 +1269,81 @@ int  pw_push_search_table_query(PwPushSearch* s, const int32_t* puzzle_id, const
                                 const uint8_t* mask, int32_t n, int32_t* index, int32_t* cost, int8_t* push_from,
                                 uint8_t* push_action, int32_t* walk, int8_t* action, void* stream);
 
+/* Drawing from a table over pushes (K20): K14's cost index, sample and plans for the table of pw_push_search_solve, and an
+ * emit that turns plans into flat demonstration rows.  All work on a PwPushSearch that holds a solved table; S is its number
+ * of states and mc = info[4] its largest finite cost (-1: none).  The streams are K14's: mix64 is pw_mix64,
+ * PW_TABLE_K_SAMPLE = 0xA0761D6478BD642F, PW_TABLE_K_PLAN = 0xE7037ED1A0B428DB.
+ *
+ * ..._index: builds the cost index over STATES (a state has several rows) unless the handle has it (idempotent):
+ *     states_by_cost  int32 [S]        a permutation of the store indices: all states of cost 0, then cost 1, ... mc, then the
+ *                                      dead ends (cost -1) as the last bucket; INSIDE A BUCKET IN ASCENDING STORE INDEX
+ *     cost_start      uint32 [mc + 3]  bucket c is [cost_start[c], cost_start[c + 1]); the dead ends are bucket mc + 1; the
+ *                                      last entry is S.  mc == -1: the two words [0, S].  A bucket may be empty: a table whose
+ *                                      goal rows all leave the grid has no state of cost 0.
+ *   K16's numbering of the store is deterministic, so with the order inside a bucket fixed a draw is a pure function of
+ *   (puzzle, start, seed, environment, count), whatever the build or the schedule.  One kernel writes (bucket, store index) per
+ *   state and counts the buckets, one stable rocPRIM radix sort by bucket orders the states, one scan makes cost_start.  The
+ *   call allocates (4 bytes per state and per bucket, kept; 12 bytes per state and the sort's workspace, freed on return) and
+ *   synchronises `stream` once.  pw_push_search_begin, a new pw_push_search_solve and pw_push_search_destroy discard the index.
+ * ..._index_read: the two arrays copied into caller device buffers (either may be NULL), asynchronous on `stream`.
+ *
+ * ..._sample: pw_search_table_sample's arguments and semantics, with out_state (the store index drawn) in place of out_row.
+ *   ONE launch, no allocation, no synchronisation (capturable), one thread per environment; the index must exist.  Masked
+ *   environments, and environments of another puzzle when puzzle_id is not NULL, are LEFT ENTIRELY UNTOUCHED, the counter
+ *   included.  The band -- the scalars lo, hi, or lo_n / hi_n per environment with hi < lo read as hi = lo -- is clamped to
+ *   [0, mc]; dead ends are never drawn.  A table with no finite cost, and a band that holds no state (cost 0 in a table without
+ *   goal states in its store), give out_state = out_cost = -1 and nothing else is written.  Else
+ *     counter[i] += 1;  r = mix64(seed ^ PW_TABLE_K_SAMPLE, i, counter[i])
+ *     count = cost_start[hi + 1] - cost_start[lo];  u = floor(r * count / 2^64);  state = states_by_cost[cost_start[lo] + u]
+ *   and the environment is written as pw_reset writes it: pos = the store's state AS REACHED (zeros from the puzzle's N to
+ *   npad - 1), steps = 0, term = trunc = 0 (either may be NULL); out_state = state, out_cost = its cost.  npad is 4 / 8 / 16 /
+ *   32 and at least the puzzle's number of movables.  Every agent position of the node's walk region is the same node; only
+ *   the stored one is drawn.
+ *
+ * ..._plans: ONE launch (capturable, no index needed), one thread per item: the walk from store index index[i] (as the query
+ *   returns it) down to cost 0.
+ *     plan_from    device int8 [n][plan_cap][2]     plan_action  device uint8 [n][plan_cap]
+ *     plan_state   device int32 [n][plan_cap] or NULL: the node the t-th push is made from
+ *     plan_len     device int32 [n]
+ *   At state i with cost > 0, tie 0 takes row row_off[i] + best[i]; tie 1 takes, at step t, the j-th optimal row (flags bit 1)
+ *   of the state in row order, with k the number of its optimal rows and j = floor(mix64(seed ^ PW_TABLE_K_PLAN, item, t) * k
+ *   / 2^64).  A goal row (flags bit 0) ends the plan, whatever its succ is; otherwise the walk goes on to succ (an optimal row
+ *   is safe: never -1).  plan_len is the start's cost when 0 <= cost <= plan_cap; -1 for an index outside [0, S), a dead end
+ *   or an item of another puzzle (the plan arrays untouched); -2 when the cost exceeds plan_cap (nothing is written).  Masked
+ *   items are untouched.
+ *
+ * ..._emit: ONE launch (capturable), one thread per (item, step): push t of the plan of item i becomes row offset[i] + t.
+ *     pos      device int8 [n][npad][2]: the items' live states, or NULL: the stored state of plan_state[i][0]
+ *     offset   device int64 [n + 1]: the exclusive scan of max(plan_len, 0) over the items that take part, made by the caller
+ *     row_item, row_t, row_state, row_cost  device int32 [rows_cap]     row_from  int8 [rows_cap][2]     row_action  uint8 [rows_cap]
+ *     row_pos  device int8 [rows_cap][npad][2]                          dropped   device uint32 [1], added to
+ *   row_state = plan_state[i][t], row_from / row_action the t-th push, row_cost = plan_len[i] - t.  row_pos of t = 0 is the
+ *   live state (or the stored one); for t > 0 it is the movables of the store's state plan_state[i][t] with the agent's pair
+ *   replaced by plan_from[i][t - 1] plus the displacement of plan_action[i][t - 1] (0 left, 1 right, 2 up, 3 down).  No flood
+ *   and no step function: a node's key is its canonical state, so the successor's boxes are the store's, and a push move
+ *   displaces its push set, the agent included, by exactly one cell.  State words go out with 8-byte (npad 4) or 16-byte
+ *   stores.  Rows at or beyond rows_cap (and rows whose plan_state lies outside the store) are dropped and counted into
+ *   `dropped`.  Items of other puzzles, masked items and items with plan_len <= 0 write nothing.
+ *
+ * PW_EINVAL before any launch, pw_last_error naming the function: a null handle or a null required array; n < 1; npad not 4 / 8
+ * / 16 / 32 or smaller than the puzzle's number of movables; band arrays that do not come together, or scalars without
+ * 0 <= lo <= hi; plan_cap < 1; tie not 0 / 1; rows_cap < 0; no solved table; sample without an index.  No kernel waits on
+ * another workgroup; there is no device assert; every loop is bounded by the items, a state's rows, plan_cap or the start's cost. */
+int  pw_push_search_table_index(PwPushSearch* s, void* stream);
+int  pw_push_search_table_index_read(PwPushSearch* s, int32_t* states_by_cost, uint32_t* cost_start, void* stream);
+int  pw_push_search_table_sample(PwPushSearch* s, const int32_t* puzzle_id, const uint8_t* mask, int32_t n, int32_t npad,
+                                 uint64_t seed, uint32_t* counter, int32_t lo, int32_t hi, const int32_t* lo_n,
+                                 const int32_t* hi_n, int8_t* pos, int32_t* steps, uint8_t* term, uint8_t* trunc,
+                                 int32_t* out_state, int32_t* out_cost, void* stream);
+int  pw_push_search_table_plans(PwPushSearch* s, const int32_t* index, const int32_t* puzzle_id, const uint8_t* mask, int32_t n,
+                                int32_t tie, uint64_t seed, int8_t* plan_from, uint8_t* plan_action, int32_t* plan_state,
+                                int32_t plan_cap, int32_t* plan_len, void* stream);
+int  pw_push_search_table_emit(PwPushSearch* s, const int32_t* puzzle_id, const uint8_t* mask, int32_t n, int32_t npad,
+                               const int8_t* plan_from, const uint8_t* plan_action, const int32_t* plan_state, int32_t plan_cap,
+                               const int32_t* plan_len, const int8_t* pos, const int64_t* offset, int64_t rows_cap,
+                               int32_t* row_item, int32_t* row_t, int32_t* row_state, int8_t* row_from, uint8_t* row_action,
+                               int32_t* row_cost, int8_t* row_pos, uint32_t* dropped, void* stream);
+
 /* Best-first search over pushes (K17): K16's nodes, store, closed set and links, expanded in the order of the reference's RGD
  * heuristic instead of layer by layer.  A node is a canonical state; the store keeps the state as reached and its canon; state 0
  * is the start; the fields per state are K16's (pos, canon, parent, from, action, walk, goal, region size, push count).

@@ -256,6 +256,16 @@ SIGNATURES = {
     "pw_push_search_table_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_search_table_query": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_table_index": (c_int, [c_void_p, c_void_p]),
+    "pw_push_search_table_index_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_search_table_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_int32,
+                                            c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "pw_push_search_table_plans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p,
+                                           c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pw_push_search_table_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                          c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_planner_create": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int64, POINTER(c_void_p)]),
     "pw_push_planner_destroy": (None, [c_void_p]),
     "pw_push_planner_begin": (c_int, [c_void_p, c_void_p, c_void_p]),
@@ -1254,6 +1264,33 @@ class PushSearchHandle:
         check(lib.pw_push_search_table_query(self.handle, _ptr(puzzle_id), _ptr(pos), int(npad), _ptr(mask), int(n), _ptr(index),
                                              _ptr(cost), _ptr(push_from), _ptr(push_action), _ptr(walk), _ptr(action),
                                              self.engine._stream()))
+
+    # drawing from the table (pw_push_search_table_index / _sample / _plans / _emit): device tensors in and out
+    def table_index(self) -> None:
+        check(lib.pw_push_search_table_index(self.handle, self.engine._stream()))
+
+    def table_index_read(self, states_by_cost, cost_start) -> None:
+        check(lib.pw_push_search_table_index_read(self.handle, _ptr(states_by_cost), _ptr(cost_start), self.engine._stream()))
+
+    def table_sample(self, puzzle_id, mask, n, npad, seed, counter, lo, hi, lo_n, hi_n, pos, steps, term, trunc, out_state,
+                     out_cost) -> None:
+        check(lib.pw_push_search_table_sample(self.handle, _ptr(puzzle_id), _ptr(mask), int(n), int(npad),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter), int(lo), int(hi), _ptr(lo_n),
+                                              _ptr(hi_n), _ptr(pos), _ptr(steps), _ptr(term), _ptr(trunc), _ptr(out_state),
+                                              _ptr(out_cost), self.engine._stream()))
+
+    def table_plans(self, index, puzzle_id, mask, n, tie, seed, plan_from, plan_action, plan_state, plan_cap, plan_len) -> None:
+        check(lib.pw_push_search_table_plans(self.handle, _ptr(index), _ptr(puzzle_id), _ptr(mask), int(n), int(tie),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(plan_from), _ptr(plan_action), _ptr(plan_state),
+                                             int(plan_cap), _ptr(plan_len), self.engine._stream()))
+
+    def table_emit(self, puzzle_id, mask, n, npad, plan_from, plan_action, plan_state, plan_cap, plan_len, pos, offset, rows_cap,
+                   row_item, row_t, row_state, row_from, row_action, row_cost, row_pos, dropped) -> None:
+        check(lib.pw_push_search_table_emit(self.handle, _ptr(puzzle_id), _ptr(mask), int(n), int(npad), _ptr(plan_from),
+                                            _ptr(plan_action), _ptr(plan_state), int(plan_cap), _ptr(plan_len), _ptr(pos),
+                                            _ptr(offset), int(rows_cap), _ptr(row_item), _ptr(row_t), _ptr(row_state),
+                                            _ptr(row_from), _ptr(row_action), _ptr(row_cost), _ptr(row_pos), _ptr(dropped),
+                                            self.engine._stream()))
 
     def close(self) -> None:
         h = getattr(self, "handle", None)

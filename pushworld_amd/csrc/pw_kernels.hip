@@ -424,5 +424,6 @@ struct PageRec {
 #include "pw_push_step.inc"
 #include "pw_push_search.inc"
 #include "pw_push_table.inc"
+#include "pw_push_table_sample.inc"
 #include "pw_push_planner.inc"
 #include "pw_generate.inc"

@@ -99,6 +99,10 @@ struct PwPushSearch {
   int32_t q_cap;         // items the query's workspace holds
   bool q_maps;           // ... with their walk maps
   uint8_t* d_q_mem;      // one allocation: ids, effective mask, region sizes, canon, push counts, maps
+  // the cost index over the table (pw_push_table_sample.inc); discarded with the table
+  bool t_index_valid;
+  int32_t* d_t_states_by_cost;  // [t_states]
+  uint32_t* d_t_cost_start;     // [t_info[4] + 3]
 };
 
 static void push_table_discard(PwPushSearch* s);  // (pw_push_table.inc)

@@ -235,7 +235,17 @@ __global__ __launch_bounds__(256) void pw_push_table_query_kernel(PushSearchArgs
   if (q.action) q.action[i] = static_cast<int8_t>(act);
 }
 
+// the cost index over the table (pw_push_table_sample.inc)
+static void push_table_index_discard(PwPushSearch* s) {
+  if (s->d_t_states_by_cost) (void)hipFree(s->d_t_states_by_cost);
+  if (s->d_t_cost_start) (void)hipFree(s->d_t_cost_start);
+  s->d_t_states_by_cost = nullptr;
+  s->d_t_cost_start = nullptr;
+  s->t_index_valid = false;
+}
+
 static void push_table_discard(PwPushSearch* s) {
+  push_table_index_discard(s);
   void* bufs[] = {s->d_t_row_off, s->d_t_cost, s->d_t_best, s->d_t_succ, s->d_t_from, s->d_t_action, s->d_t_flags};
   for (void* b : bufs)
     if (b) (void)hipFree(b);

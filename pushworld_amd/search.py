@@ -1943,6 +1943,39 @@ def _push_query_outputs(out, n: int, device) -> PushQuery:
     return PushQuery(*out)
 
 
+PushPlans = namedtuple("PushPlans", "push_from push_action state length")
+PushPlans.__doc__ = """What ``PushSolutionTable.plans`` returns: device tensors ``push_from`` int8 [n, plan_cap, 2], ``push_action``
+uint8 [n, plan_cap], ``state`` int32 [n, plan_cap] (the node the t-th push is made from) and ``length`` int32 [n]."""
+
+PushRows = namedtuple("PushRows", "item t state push_from push_action cost pos dropped num_rows")
+PushRows.__doc__ = """What ``PushSolutionTable.demonstration_rows`` returns: one row per push of every plan -- device tensors
+``item`` / ``t`` / ``state`` / ``cost`` int32 [T], ``push_from`` int8 [T, 2], ``push_action`` uint8 [T], ``pos`` int8 [T, NP, 2]
+(the state the push is made from), ``dropped`` uint32 [1] (rows beyond the capacity) and ``num_rows``, T as an int."""
+
+
+def _push_plans_outputs(out, n: int, plan_cap: int, device) -> PushPlans:
+    """The four tensors a plans launch fills: fresh (zeros / zeros / -1 / ``PLANS_NONE``) or the checked ``out``."""
+    if out is None:
+        return PushPlans(torch.zeros((n, plan_cap, 2), dtype=torch.int8, device=device),
+                         torch.zeros((n, plan_cap), dtype=torch.uint8, device=device),
+                         torch.full((n, plan_cap), -1, dtype=torch.int32, device=device),
+                         torch.full((n,), PLANS_NONE, dtype=torch.int32, device=device))
+    if not isinstance(out, (tuple, list)) or len(out) != 4:
+        raise ValueError("out must be the PushPlans of an earlier call")
+    for name, t, dtype, shape in zip(PushPlans._fields, out, (torch.int8, torch.uint8, torch.int32, torch.int32),
+                                     ((n, plan_cap, 2), (n, plan_cap), (n, plan_cap), (n,))):
+        _dev_tensor(f"out: {name}", t, dtype, shape, device)
+    return PushPlans(*out)
+
+
+def encode_push_choice(push_from: torch.Tensor, push_action: torch.Tensor, map_h: int, map_w: int) -> torch.Tensor:
+    """int64 [B] flat indices into ``[4, map_h, map_w]`` of the pushes ``push_from`` (int8 [B, 2]) / ``push_action`` (uint8 [B]):
+    ``(a * map_h + y) * map_w + x``, the exact inverse of ``decode_push_choice``; -1 for a push outside the shape."""
+    x, y, a = push_from[:, 0].to(torch.int64), push_from[:, 1].to(torch.int64), push_action.to(torch.int64)
+    inside = (x >= 0) & (x < int(map_w)) & (y >= 0) & (y < int(map_h)) & (a < 4)
+    return torch.where(inside, (a * int(map_h) + y) * int(map_w) + x, torch.full_like(a, -1))
+
+
 class PushSolutionTable:
     """The exact cost-to-go IN PUSHES of every canonical state reachable in one puzzle: a ``PushBreadthFirstSearch`` with
     ``stop_at_goal=False`` run to exhaustion, then ``pw_push_search_solve``.  State i of the search has the push rows
@@ -1955,6 +1988,9 @@ class PushSolutionTable:
     * ``best()`` int32: the state's lowest optimal row (relative to its first), -1 at goal states and dead ends.
 
     A cost in moves is not kept: a node holds one agent position for a whole walk region.
+
+    The table is a data source too: ``cost_index`` groups the states by cost, ``sample`` draws start states k
+    pushes from the goal for a batch, ``plans`` walks fewest-pushes plans and ``demonstration_rows`` turns them into flat rows.
 
     Args:
         puzzle: a ``PushWorldPuzzle`` or a ``SetPuzzle``.
@@ -2082,6 +2118,135 @@ class PushSolutionTable:
             plan.append(action)
             if self.puzzle.is_goal_state(state):  # (a goal row may carry a movable out of its grid: no node, and the goal)
                 return plan
+
+    # ---- drawing from the table (pw_push_search_table_index / _sample / _plans / _emit) --------------------------
+    def _entry(self, what: str):
+        """(function, handle, stream) of ``_sample_call``'s launch; the first sample builds the cost index (the call is
+        idempotent: with the index in place it launches nothing)."""
+        h = self._handle()
+        h.table_index()
+        return _capi.lib.pw_push_search_table_sample, h.handle, h.engine._stream()
+
+    def cost_index(self):
+        """``(states_by_cost int32 [num_states], cost_start uint32 [max_cost + 3])`` on the device: the STATES grouped by
+        cost-to-go, the dead ends last, in ascending store index inside a bucket; bucket c is
+        ``states_by_cost[cost_start[c] : cost_start[c + 1]]``, the dead ends are bucket ``max_cost + 1``.  Built by the first
+        call (it allocates and waits once), kept until the search is restarted."""
+        h = self._handle()
+        h.table_index()
+        states = torch.empty((self.num_states,), dtype=torch.int32, device=self.device)
+        start = torch.empty((self.max_cost + 3,), dtype=torch.uint32, device=self.device)
+        h.table_index_read(states, start)
+        return states, start
+
+    def sample(self, puzzle_id: Optional[torch.Tensor], pos: torch.Tensor, steps: torch.Tensor,
+               terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None, cost=(1, None),
+               mask: Optional[torch.Tensor] = None, seed: int = 0, counter: Optional[torch.Tensor] = None, out=None):
+        """``SolutionTable.sample`` over this table's canonical states: one start state per environment, drawn uniformly from
+        the states whose cost IN PUSHES lies in ``cost`` (``(lo, hi)`` ints, ``hi`` None: up to ``max_cost``, or two int32
+        tensors [n]) and written as a reset would -- ``pos`` gets the state as the search reached it (the agent where the
+        push left it), ``steps`` = 0, ``terminated`` = ``truncated`` = 0.  One launch on the current stream, no wait, no
+        allocation when ``counter`` and ``out`` are given and the index exists (capturable).  The band is clamped to
+        ``0 .. max_cost``; dead ends are never drawn.  Returns ``(state, cost)`` int32 [n] (``out``, filled in place): the
+        store index drawn and its cost; -1 / -1 where the table has no solvable state or the band holds no state.  A draw
+        is a function of (``seed``, environment, ``counter``) alone: the order inside a cost bucket is the store's.  Masked
+        environments and environments of other puzzles keep everything they held, the counter included."""
+        return _sample_call(self, True, puzzle_id, pos, steps, terminated, truncated, cost, mask, seed, counter, out)
+
+    def plans(self, index: torch.Tensor, puzzle_id: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+              tie: str = "lowest", seed: int = 0, plan_cap: int = 256, out=None) -> PushPlans:
+        """A fewest-pushes plan from every state of ``index`` (int32 [n] store indices, as ``query`` returns them) in one launch
+        on the current stream, no wait: a ``PushPlans``.  ``tie`` "lowest" takes each state's ``best`` row, "uniform" draws
+        among its optimal rows (f(``seed``, item, step)).  ``length`` is the state's cost; ``PLANS_NONE`` -1 for an index
+        outside the table, a dead end or an item of another puzzle, ``PLANS_CUT`` -2 for a plan longer than ``plan_cap``
+        (nothing else written in both cases).  Masked items keep what ``out`` -- the ``PushPlans`` of an earlier call -- held."""
+        device = self.device
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1:
+            raise ValueError("index must be an int32 tensor [n] (store indices, as query returns them)")
+        n = int(index.shape[0])
+        if n < 1 or n >= 1 << 31:
+            raise ValueError("index must hold 1 .. 2^31 - 1 items")
+        _dev_tensor("index", index, torch.int32, (n,), device)
+        _dev_tensor("puzzle_id", puzzle_id, torch.int32, (n,), device, optional=True)
+        _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
+        if tie not in TABLE_TIES:
+            raise ValueError("tie must be 'lowest' or 'uniform'")
+        plan_cap = int(plan_cap)
+        if not 1 <= plan_cap <= _capi.PLAN_MAX_ACTIONS:
+            raise ValueError(f"plan_cap must be in 1 .. {_capi.PLAN_MAX_ACTIONS}")
+        out = _push_plans_outputs(out, n, plan_cap, device)
+        self._handle().table_plans(index, puzzle_id, mask, n, TABLE_TIES[tie], seed, out.push_from, out.push_action, out.state,
+                                   plan_cap, out.length)
+        return out
+
+    def demonstration_rows(self, plans: PushPlans, pos: Optional[torch.Tensor] = None, puzzle_id: Optional[torch.Tensor] = None,
+                           mask: Optional[torch.Tensor] = None, rows_cap: Optional[int] = None,
+                           offset: Optional[torch.Tensor] = None, out: Optional[PushRows] = None) -> PushRows:
+        """Every push of every plan of ``plans`` as one flat row (``pw_push_search_table_emit``, one launch, no flood and no
+        step): a ``PushRows``.  Row ``offset[i] + t`` holds push t of item i, the node it is made from, the cost to go
+        ``length[i] - t`` and the state the push is made from -- for t = 0 ``pos[i]`` (int8 [n, NP, 2] live states; None: the
+        node's stored state), later the store's state of the node with the agent where the push before left it.  ``offset``
+        (int64 [n + 1]) defaults to the exclusive scan of the lengths of the items that take part (not masked, of this
+        table's puzzle, length > 0).  ``rows_cap`` None sizes the rows from ``offset[n]`` -- the one host wait; rows at or
+        beyond a given ``rows_cap`` are dropped and counted in ``dropped``.  ``out``: the ``PushRows`` of an earlier call or
+        of another table of the same batch, filled in place (``rows_cap`` defaults to its rows and must not exceed them)."""
+        device = self.device
+        if not isinstance(plans, (tuple, list)) or len(plans) != 4 or not isinstance(plans[3], torch.Tensor) \
+                or plans[3].dim() != 1 or not isinstance(plans[1], torch.Tensor) or plans[1].dim() != 2:
+            raise ValueError("plans must be the PushPlans of a plans call")
+        n, plan_cap = int(plans[3].shape[0]), int(plans[1].shape[1])
+        if n < 1 or plan_cap < 1:
+            raise ValueError("plans must hold at least one item and one step")
+        plans = _push_plans_outputs(plans, n, plan_cap, device)
+        _dev_tensor("pos", pos, torch.int8, (n, self.npad, 2), device, optional=True)
+        _dev_tensor("puzzle_id", puzzle_id, torch.int32, (n,), device, optional=True)
+        _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
+        if offset is None:
+            lens = plans.length.clamp(min=0).to(torch.int64)
+            if mask is not None:
+                lens = lens * (mask != 0)
+            if puzzle_id is not None:
+                lens = lens * (puzzle_id == self.puzzle_index)
+            offset = torch.zeros((n + 1,), dtype=torch.int64, device=device)
+            torch.cumsum(lens, 0, out=offset[1:])
+        _dev_tensor("offset", offset, torch.int64, (n + 1,), device)
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 9 or not isinstance(out[0], torch.Tensor) or out[0].dim() != 1:
+                raise ValueError("out must be the PushRows of an earlier call")
+            cap = int(out[0].shape[0])
+            rows_cap = cap if rows_cap is None else int(rows_cap)
+            if rows_cap > cap:
+                raise ValueError("rows_cap must not exceed the rows of out")
+        elif rows_cap is None:
+            self._handle()
+            rows_cap = int(offset[n].cpu())  # the one wait: the number of rows
+        rows_cap = int(rows_cap)
+        if rows_cap < 0:
+            raise ValueError("rows_cap must be >= 0")
+        if out is None:
+            cap = rows_cap
+            out = PushRows(torch.full((cap,), -1, dtype=torch.int32, device=device),
+                           torch.full((cap,), -1, dtype=torch.int32, device=device),
+                           torch.full((cap,), -1, dtype=torch.int32, device=device),
+                           torch.zeros((cap, 2), dtype=torch.int8, device=device),
+                           torch.full((cap,), PUSH_NONE, dtype=torch.uint8, device=device),
+                           torch.full((cap,), -1, dtype=torch.int32, device=device),
+                           torch.zeros((cap, self.npad, 2), dtype=torch.int8, device=device),
+                           torch.zeros((1,), dtype=torch.int32, device=device).view(torch.uint32), cap)
+        for name, t, dtype, shape in zip(PushRows._fields[:8], out,
+                                         (torch.int32, torch.int32, torch.int32, torch.int8, torch.uint8, torch.int32, torch.int8,
+                                          (torch.uint32, torch.int32)),
+                                         ((cap,), (cap,), (cap,), (cap, 2), (cap,), (cap,), (cap, self.npad, 2), (1,))):
+            _dev_tensor(f"out: {name}", t, dtype, shape, device)
+        out = PushRows(*out)
+        self._handle().table_emit(puzzle_id, mask, n, self.npad, plans.push_from, plans.push_action, plans.state, plan_cap,
+                                  plans.length, pos, offset, rows_cap, out.item, out.t, out.state, out.push_from, out.push_action,
+                                  out.cost, out.pos, out.dropped)
+        return out
+
+    def covers(self, puzzle_id: torch.Tensor) -> torch.Tensor:
+        """bool [n] on the device: the items of ``puzzle_id`` this table answers for."""
+        return puzzle_id == self.puzzle_index
 
     def close(self) -> None:
         search = getattr(self, "search", None)

@@ -663,6 +663,125 @@ class VecPushWorld:
                 self.engine.render(out.puzzle_id, out.pos, storage)
         return out
 
+    def _own_push_tables(self, tables) -> list:
+        tables = list(tables)
+        for table in tables:
+            if table.search._engine is not self.engine:
+                raise ValueError("the tables must be made on this environment (VecPushWorld.push_table)")
+        return tables
+
+    def reset_from_push_tables(self, tables, cost=(1, None), mask: Optional[torch.Tensor] = None, seed: Optional[int] = None):
+        """``reset_from_tables`` with a list of ``push_table``s: every (masked) environment whose puzzle has a table in
+        ``tables`` starts from a canonical state drawn uniformly among the states of its puzzle with a cost-to-go IN PUSHES
+        in ``cost`` = ``(lo, hi)`` (``hi`` None: up to each table's own largest cost; two int32 tensors [B]: a band per
+        environment), the agent where the search's push left it.  The band is clamped to each table's costs and dead ends
+        are never drawn; environments without a table (or whose table has no solvable state in the band) start from the
+        initial state.  One ``pw_reset`` launch, one sample launch per table, one render; no wait once every table has its
+        cost index.  Returns the observation tensor.
+
+        ``self.start_row`` (here the store index of the node drawn) / ``self.start_cost`` (int32 [B]) and
+        ``self.table_draws`` are ``reset_from_tables``' own: a draw is a function of (seed, environment, count)."""
+        tables = self._own_push_tables(tables)
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        if getattr(self, "table_draws", None) is None:
+            self.table_seed = self.seed
+            # (uint32 counter bits over an int32 allocation, like `episode`)
+            self.table_draws = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device).view(torch.uint32)
+            self.start_row = torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device)
+            self.start_cost = torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device)
+        if seed is not None:
+            self.table_seed = int(seed)
+            self.table_draws.view(torch.int32).zero_()
+        self._reset_states(mask)
+        if mask is None:
+            self.start_row.fill_(-1), self.start_cost.fill_(-1)
+        else:
+            self.start_row.masked_fill_(mask.bool(), -1), self.start_cost.masked_fill_(mask.bool(), -1)
+        for table in tables:
+            table.sample(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, cost=cost, mask=mask,
+                         seed=self.table_seed, counter=self.table_draws, out=(self.start_row, self.start_cost))
+        self._obs_current = False
+        if self.obs is not None:
+            self._render()
+        return self.obs
+
+    def optimal_push_demonstrations(self, tables, tie: str = "lowest", seed: int = 0, observation: Optional[str] = "own",
+                                    mask: Optional[torch.Tensor] = None, plan_cap: int = 256, masks: bool = False):
+        """Fewest-pushes demonstrations in the push-level action space, read off ``push_table``s: from every (unmasked)
+        environment's current state one ``push_cost_to_go`` over ``tables``, one plans launch per table (``tie`` "lowest":
+        each node's best row, "uniform": drawn among its optimal rows with ``seed``), a ``cumsum``, ONE host wait for the
+        number of rows T, one emit launch per table -- every push of every plan becomes one row, without a flood or a step
+        -- and one render launch.  Environments at a goal state or a dead end, outside every table or with a plan longer
+        than ``plan_cap`` contribute no rows.
+
+        Returns a ``types.SimpleNamespace`` of device tensors over the T rows: ``puzzle_id`` int32, ``pos`` int8 [T, NP, 2]
+        (the state the push is made from: row 0 of an environment is its live state), ``item`` (the environment) and ``t``
+        int32, ``push_from`` int8 [T, 2] / ``push_action`` uint8, ``cost`` int32 (pushes to go, falling by 1 per row to 1),
+        ``choice`` int64 -- the push as a flat index into ``[4, map_h, map_w]``, the exact inverse of
+        ``search.decode_push_choice``, what ``step_push(choice=...)`` takes -- ``obs`` (``observation`` as in
+        ``optimal_demonstrations``; None: no render), ``num_rows`` and, with ``masks``, ``push_mask`` uint8 [T, map_h, map_w]
+        (``search.push_mask`` over the rows)."""
+        from types import SimpleNamespace
+
+        from .search import PLANS_NONE, PushRows, _push_plans_outputs, encode_push_choice, push_mask
+
+        tables = self._own_push_tables(tables)
+        if observation == "own":
+            observation = self.observation
+        if observation not in ("uint8", "float32", "cells", None):
+            raise ValueError("observation must be 'uint8', 'float32', 'cells' or None")
+        own_rgb = "uint8" if self.engine.obs_dtype == torch.uint8 else "float32"
+        if observation in ("uint8", "float32") and observation != own_rgb:
+            raise ValueError(f"this environment's engine renders {own_rgb} pixels: observation must be '{own_rgb}', 'cells' or None")
+        if tie not in ("lowest", "uniform"):
+            raise ValueError("tie must be 'lowest' or 'uniform'")
+        if int(plan_cap) < 1:
+            raise ValueError("plan_cap must be >= 1")
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        B, dev = self.num_envs, self.device
+        q = self.push_cost_to_go(tables, mask=mask)
+        # (no plan is longer than a table's largest cost: the buffers need no more columns; a cost beyond plan_cap is cut as ever)
+        width = max(1, min(int(plan_cap), max([int(t.max_cost) for t in tables] + [1])))
+        plans = _push_plans_outputs(None, B, width, dev)
+        owns = []
+        for table in tables:  # (a table answers for its own puzzles only: the others keep what another table wrote)
+            own = table.covers(self.puzzle_id)
+            if mask is not None:
+                own &= mask.bool()
+            owns.append(own)
+            table.plans(q.index, self.puzzle_id, mask=own, tie=tie, seed=seed, plan_cap=width, out=plans)
+        offset = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(plans.length.clamp(min=0), 0, out=offset[1:])
+        T = int(offset[B].cpu())  # the one wait: the number of rows
+        rows = None
+        for table, own in zip(tables, owns):
+            rows = table.demonstration_rows(plans, pos=self.pos, puzzle_id=self.puzzle_id, mask=own, rows_cap=T, offset=offset,
+                                            out=rows)
+        if rows is None:
+            rows = PushRows(*(torch.zeros((0,) + s, dtype=d, device=dev) for s, d in
+                              (((), torch.int32), ((), torch.int32), ((), torch.int32), ((2,), torch.int8), ((), torch.uint8),
+                               ((), torch.int32), ((self.num_objects_padded, 2), torch.int8))),
+                            torch.zeros((1,), dtype=torch.int32, device=dev).view(torch.uint32), 0)
+        out = SimpleNamespace(num_rows=T, item=rows.item, t=rows.t, state=rows.state, push_from=rows.push_from,
+                              push_action=rows.push_action, cost=rows.cost, pos=rows.pos, obs=None)
+        out.puzzle_id = self.puzzle_id[rows.item.to(torch.int64)].contiguous() if T > 0 else \
+            torch.zeros((0,), dtype=torch.int32, device=dev)
+        out.choice = encode_push_choice(rows.push_from, rows.push_action, self.pset.max_height, self.pset.max_width)
+        if observation == "cells":
+            out.obs = torch.empty((T,) + self.engine.cells_shape(), dtype=torch.uint8, device=dev)
+            if T > 0:
+                self.engine.render_cells(out.puzzle_id, out.pos, out.obs)
+        elif observation is not None:
+            storage, out.obs = self.engine.alloc_obs(T)
+            if T > 0:
+                self.engine.render(out.puzzle_id, out.pos, storage)
+        if masks:
+            out.push_mask = push_mask(self.engine, out.puzzle_id, out.pos)[0] if T > 0 else \
+                torch.zeros((0, self.pset.max_height, self.pset.max_width), dtype=torch.uint8, device=dev)
+        return out
+
     def set_states(self, pos: np.ndarray) -> None:
         self.pos.copy_(torch.as_tensor(np.asarray(pos), dtype=torch.int8))
         self._has_reset = True
