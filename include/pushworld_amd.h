@@ -1145,6 +1145,48 @@ int pw_push_mask(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32
                  uint8_t* push_mask /* [n][map_h][map_w] */, int32_t* num_pushes /* [n] or NULL */,
                  int32_t map_h, int32_t map_w, void* stream);
 
+/* Pushes unrolled into primitive actions (K21): the bridge from the push level back to the move level.  Item i is a state s
+ * (puzzle_id[i], pos[i]; pos NULL: the initial states, as pw_walk_regions) and a choice (from, a) = (push_from[i],
+ * push_action[i]).  The choice is VALID by pw_step_push's rule, unchanged: a in 0..3, from in the walk region R(s), (from, a) a
+ * push move.  Its unrolled sequence is
+ *   L = path(R, from) + [a]
+ * where path(R, from) is the parent actions of pw_walk_regions' map from the agent's position to `from`: the L of the
+ * pw_step_push comment, so len(L) = dist(from) + 1 is in 1 .. 4096.  An item is REFUSED -- length -1, no byte written -- when
+ * it is masked out (mask[i] == 0), its id is outside the set, a movable lies outside its grid, or its choice is not valid
+ * (PUSH_NONE = 0xFF counts as not valid).
+ * pw_push_unroll_count writes
+ *   length  int32 [n]      len(L), or -1 for a refused item
+ *   offset  int64 [n + 1]  the exclusive prefix sum of max(length, 0); offset[n] = the total number of actions
+ * pw_push_unroll_write takes the same inputs and the offset of the first call, recomputes, and writes
+ *   actions uint8 [cap]    actions[offset[i] + k] = L[k].  Bytes at or beyond `cap` are not written; *dropped (device int64, or
+ *                          NULL) receives how many were left out.  actions may be NULL when cap is 0.
+ * pw_push_unroll_plans gathers unrolled rows into plan arrays in exactly the format pw_plan_replay_check takes.  The rows
+ * item_offset[j] .. item_offset[j + 1] - 1 (item_offset int64 [m + 1], ascending, within 0 .. rows) are the consecutive pushes
+ * of plan j -- the layout of pw_push_search_table_emit -- and length int32 [rows], offset int64 [rows + 1], actions uint8 [cap]
+ * are what count and write left for those rows:
+ *   plan_len int32 [m]           the sum of the rows' lengths (offset[last + 1] - offset[first]: the spans of consecutive rows are
+ *                                contiguous in `actions`); 0 for a plan without rows; -1 (PW_REPLAY_NONE) for a plan with a
+ *                                refused row, with rows outside 0 .. rows, or with bytes at or beyond cap
+ *   plans    uint8 [m][plan_cap] the first min(plan_len, plan_cap) actions of the plan; a plan longer than plan_cap keeps its
+ *                                true plan_len (PW_REPLAY_CUT downstream).  Bytes beyond that are left as they were.
+ * All three are asynchronous on `stream` and read nothing on the host; count and write are one launch each (count adds
+ * rocPRIM's scan), the gather is one launch.  They use the engine's shared replay workspace only (the item counters, and the
+ * scan's temporary storage, which the first call of a size allocates).  pos and push_from are read as 2-byte (x, y) pairs.
+ * PW_EINVAL before any launch, pw_last_error naming the function and the argument: a null engine, puzzle_id, push_from,
+ * push_action, length, offset, item_offset, plans or plan_len; null actions with cap > 0; n or m < 1; npad not 4 / 8 / 16 / 32 or
+ * below the set's largest number of movables; cap or rows < 0; plan_cap outside 1 .. PW_PLAN_MAX_ACTIONS.
+ * No kernel waits on another workgroup; there is no device assert; every loop is bounded by the items, the cells of a board
+ * times four actions, or 4 095 layers. */
+int pw_push_unroll_count(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32_t npad,
+                         const int8_t* push_from /* [n][2] (x, y) */, const uint8_t* push_action /* [n] */,
+                         const uint8_t* mask, int32_t n, int32_t* length, int64_t* offset, void* stream);
+int pw_push_unroll_write(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const int8_t* push_from,
+                         const uint8_t* push_action, const uint8_t* mask, int32_t n, const int64_t* offset, int64_t cap,
+                         uint8_t* actions, int64_t* dropped, void* stream);
+int pw_push_unroll_plans(PwEngine* e, const int64_t* item_offset, const int32_t* length, const int64_t* offset,
+                         const uint8_t* actions, int64_t rows, int64_t cap, int32_t m, int32_t plan_cap, uint8_t* plans,
+                         int32_t* plan_len, void* stream);
+
 /* Breadth-first search over pushes with its closed set on the device (K16).  A node is a canonical state: the packed positions
  * with the agent's pair replaced by canon(s).  The store keeps, per node, the state as reached (the agent where the push left
  * it) and its canon; state 0 is the start.  Layer d + 1 holds the successors of the push moves of layer d's states: the states

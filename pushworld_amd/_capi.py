@@ -244,6 +244,12 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_int32, c_uint32, c_void_p]),
     "pw_push_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                              c_void_p]),
+    "pw_push_unroll_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                     c_void_p, c_void_p]),
+    "pw_push_unroll_write": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                     c_int64, c_void_p, c_void_p, c_void_p]),
+    "pw_push_unroll_plans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                     c_void_p, c_void_p, c_void_p]),
     "pw_push_search_create": (c_int, [c_void_p, c_int32, c_int64, POINTER(c_void_p)]),
     "pw_push_search_destroy": (None, [c_void_p]),
     "pw_push_search_begin": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
@@ -1192,6 +1198,20 @@ class Engine:
     def push_mask(self, puzzle_id, pos, mask, push_mask, num_pushes=None):
         check(lib.pw_push_mask(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(mask), puzzle_id.shape[0],
                                _ptr(push_mask), _ptr(num_pushes), push_mask.shape[1], push_mask.shape[2], self._stream()))
+
+    # pushes unrolled into primitive actions (pw_push_unroll_count / _write / _plans): device tensors in and out, no wait
+    def push_unroll_count(self, puzzle_id, pos, push_from, push_action, mask, length, offset):
+        check(lib.pw_push_unroll_count(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(push_from), _ptr(push_action),
+                                       _ptr(mask), puzzle_id.shape[0], _ptr(length), _ptr(offset), self._stream()))
+
+    def push_unroll_write(self, puzzle_id, pos, push_from, push_action, mask, offset, cap, actions, dropped=None):
+        check(lib.pw_push_unroll_write(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(push_from), _ptr(push_action),
+                                       _ptr(mask), puzzle_id.shape[0], _ptr(offset), int(cap), _ptr(actions), _ptr(dropped),
+                                       self._stream()))
+
+    def push_unroll_plans(self, item_offset, length, offset, actions, rows, cap, plans, plan_len):
+        check(lib.pw_push_unroll_plans(self.handle, _ptr(item_offset), _ptr(length), _ptr(offset), _ptr(actions), int(rows),
+                                       int(cap), plan_len.shape[0], plans.shape[1], _ptr(plans), _ptr(plan_len), self._stream()))
 
     def expand4(self, puzzle_index, states, succ, moved, goal):
         check(lib.pw_expand4(self.handle, int(puzzle_index), _ptr(states), _ptr(succ), _ptr(moved), _ptr(goal),

@@ -2244,6 +2244,29 @@ class PushSolutionTable:
                                   out.cost, out.pos, out.dropped)
         return out
 
+    def primitive_plans(self, pos: torch.Tensor, puzzle_id: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                        tie: str = "lowest", seed: int = 0, plan_cap: int = 1024, push_cap: int = 256):
+        """A fewest-pushes plan IN PRIMITIVE ACTIONS from every live state of ``pos`` (int8 [n, NP, 2]; ``puzzle_id`` / ``mask``
+        as ``query``): ``query``, ``plans`` (at most ``push_cap`` pushes), ``demonstration_rows`` and ``push_rows_to_plans``,
+        all on the device with two host waits (the number of rows, the number of actions).  Returns ``(plans uint8 [n,
+        plan_cap], plan_len int32 [n], pushes int32 [n])`` as ``replay_plans`` takes them: ``plan_len`` 0 at a goal state, -1
+        at a dead end, for a state outside the table, an item of another puzzle, a masked item or a plan of more than
+        ``push_cap`` pushes.  Unlike ``optimal_plan`` the walk to every push follows the parent actions of the walk region
+        of the state the push is made from (``walk_regions``' maps)."""
+        q = self.query(puzzle_id, pos, mask=mask, actions=False)
+        n = int(q.index.shape[0])
+        own = mask
+        if puzzle_id is not None:
+            own = self.covers(puzzle_id) if mask is None else self.covers(puzzle_id) & (mask != 0)
+        plans = self.plans(q.index, puzzle_id, mask=own, tie=tie, seed=seed, plan_cap=push_cap)
+        offset = torch.zeros((n + 1,), dtype=torch.int64, device=self.device)
+        torch.cumsum(plans.length.clamp(min=0), 0, out=offset[1:])
+        rows = self.demonstration_rows(plans, pos=pos, puzzle_id=puzzle_id, mask=own, offset=offset,
+                                       rows_cap=int(offset[n].cpu()))
+        ids = torch.full((rows.num_rows,), self.puzzle_index, dtype=torch.int32, device=self.device)
+        out, plan_len, pushes = push_rows_to_plans(self.search._engine, ids, rows, offset, plan_cap=plan_cap)
+        return out, torch.where(plans.length < 0, torch.full_like(plan_len, -1), plan_len), pushes
+
     def covers(self, puzzle_id: torch.Tensor) -> torch.Tensor:
         """bool [n] on the device: the items of ``puzzle_id`` this table answers for."""
         return puzzle_id == self.puzzle_index
@@ -2260,3 +2283,87 @@ class PushSolutionTable:
         self.close()
 
     __del__ = close
+
+
+# ---- pushes unrolled into primitive actions (pw_push_unroll_count / _write / _plans) ----------------------------
+PushUnroll = namedtuple("PushUnroll", "length offset actions num_actions")
+PushUnroll.__doc__ = """What ``unroll_pushes`` returns: device tensors ``length`` int32 [n] (the primitive actions of item i's push,
+-1 for a refused item), ``offset`` int64 [n + 1] (the actions of item i: ``actions[offset[i] : offset[i + 1]]``), ``actions``
+uint8 [num_actions], and ``num_actions`` as an int."""
+
+
+def _unroll_inputs(puzzle_id, push_from, push_action, pos, mask, npad: int, device) -> int:
+    """The checks of ``unroll_pushes`` on its device arrays; returns n."""
+    n = _walk_inputs(puzzle_id, pos, mask, npad, device)
+    if not isinstance(push_from, torch.Tensor) or push_from.dtype != torch.int8 or tuple(push_from.shape) != (n, 2):
+        raise ValueError("push_from must be an int8 tensor [n, 2]")
+    if not isinstance(push_action, torch.Tensor) or push_action.dtype != torch.uint8 or tuple(push_action.shape) != (n,):
+        raise ValueError("push_action must be a uint8 tensor [n]")
+    for name, t in (("push_from", push_from), ("push_action", push_action)):
+        if t.device != device:
+            raise ValueError(f"{name} must live on {device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return n
+
+
+def unroll_pushes(engine_or_vec, puzzle_id: torch.Tensor, push_from: torch.Tensor, push_action: torch.Tensor,
+                  pos: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> PushUnroll:
+    """Every push of a batch as the primitive actions that perform it (``pw_push_unroll_count`` / ``pw_push_unroll_write``) on
+    the current stream: item i is the state ``puzzle_id[i]`` / ``pos[i]`` (int8 [n, NP, 2]; None: the initial states) and the
+    choice ``push_from[i]`` (int8 [n, 2]) / ``push_action[i]`` (uint8 [n]); its actions are the walk from the agent's position
+    to ``push_from`` along the parent actions of its walk region, then the push -- what ``step_push`` executes.  A choice that
+    ``step_push`` would refuse (``PUSH_NONE`` included), a masked item, an id outside the set and a movable outside its grid
+    give length -1 and no actions.  Count, ONE host wait for the total, then write.  Returns a ``PushUnroll``."""
+    engine = engine_or_vec if isinstance(engine_or_vec, _capi.Engine) else getattr(engine_or_vec, "engine", None)
+    if not isinstance(engine, _capi.Engine):
+        raise ValueError("engine_or_vec must be a VecPushWorld or an _capi.Engine")
+    dev, npad = engine.device, int(engine.np)
+    n = _unroll_inputs(puzzle_id, push_from, push_action, pos, mask, npad, dev)
+    length = torch.empty((n,), dtype=torch.int32, device=dev)
+    offset = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    engine.push_unroll_count(puzzle_id, pos, push_from, push_action, mask, length, offset)
+    total = int(offset[n].item())  # the one wait: the number of actions
+    actions = torch.empty((total,), dtype=torch.uint8, device=dev)
+    if total > 0:
+        engine.push_unroll_write(puzzle_id, pos, push_from, push_action, mask, offset, total, actions)
+    return PushUnroll(length, offset, actions, total)
+
+
+def push_rows_to_plans(engine_or_vec, puzzle_id_rows: torch.Tensor, rows, item_offset: torch.Tensor, plan_cap: int = 1024):
+    """Plans over pushes as plans over primitive actions: ``rows`` is a ``PushRows`` (one row per push, with the state it is
+    made from: ``PushSolutionTable.demonstration_rows``), ``puzzle_id_rows`` int32 [T] the puzzle of every row, and the rows
+    ``item_offset[j] : item_offset[j + 1]`` (int64 [m + 1]) are the consecutive pushes of plan j.  One ``unroll_pushes`` over the
+    rows (its one wait) and one gather launch (``pw_push_unroll_plans``).  Returns ``(plans uint8 [m, plan_cap], plan_len int32
+    [m], pushes int32 [m])`` on the device, in exactly the format ``replay_plans`` takes: ``plan_len`` is the number of
+    primitive actions (0 for a plan without rows, ``REPLAY_NONE`` -1 for a plan with a row that is no push move of its state;
+    a plan longer than ``plan_cap`` keeps its length and its first ``plan_cap`` actions: ``REPLAY_CUT`` downstream);
+    ``pushes`` is the number of rows of every plan."""
+    engine = engine_or_vec if isinstance(engine_or_vec, _capi.Engine) else getattr(engine_or_vec, "engine", None)
+    if not isinstance(engine, _capi.Engine):
+        raise ValueError("engine_or_vec must be a VecPushWorld or an _capi.Engine")
+    dev, npad = engine.device, int(engine.np)
+    if not isinstance(rows, (tuple, list)) or len(rows) != 9 or not isinstance(rows[0], torch.Tensor) or rows[0].dim() != 1:
+        raise ValueError("rows must be a PushRows (PushSolutionTable.demonstration_rows)")
+    rows = PushRows(*rows)
+    T = int(rows.item.shape[0])
+    plan_cap = int(plan_cap)
+    if not 1 <= plan_cap <= _capi.PLAN_MAX_ACTIONS:
+        raise ValueError(f"plan_cap must be in 1 .. {_capi.PLAN_MAX_ACTIONS}")
+    if not isinstance(item_offset, torch.Tensor) or item_offset.dtype != torch.int64 or item_offset.dim() != 1 \
+            or not 2 <= int(item_offset.shape[0]) <= 1 << 31:
+        raise ValueError("item_offset must be an int64 tensor [m + 1], m >= 1")
+    _dev_tensor("item_offset", item_offset, torch.int64, tuple(item_offset.shape), dev)
+    m = int(item_offset.shape[0]) - 1
+    plans = torch.zeros((m, plan_cap), dtype=torch.uint8, device=dev)
+    plan_len = torch.zeros((m,), dtype=torch.int32, device=dev)
+    pushes = (item_offset[1:] - item_offset[:-1]).to(torch.int32)
+    if T == 0:
+        if not isinstance(puzzle_id_rows, torch.Tensor) or tuple(puzzle_id_rows.shape) != (0,):
+            raise ValueError("puzzle_id_rows must be an int32 tensor [T], one id per row")
+        return plans, plan_len, pushes
+    if not isinstance(puzzle_id_rows, torch.Tensor) or tuple(puzzle_id_rows.shape) != (T,):
+        raise ValueError("puzzle_id_rows must be an int32 tensor [T], one id per row")
+    u = unroll_pushes(engine, puzzle_id_rows, rows.push_from, rows.push_action, pos=rows.pos)
+    engine.push_unroll_plans(item_offset, u.length, u.offset, u.actions, T, u.num_actions, plans, plan_len)
+    return plans, plan_len, pushes

@@ -724,7 +724,7 @@ class VecPushWorld:
         (``search.push_mask`` over the rows)."""
         from types import SimpleNamespace
 
-        from .search import PLANS_NONE, PushRows, _push_plans_outputs, encode_push_choice, push_mask
+        from .search import encode_push_choice, push_mask
 
         tables = self._own_push_tables(tables)
         if observation == "own":
@@ -740,6 +740,32 @@ class VecPushWorld:
             raise ValueError("plan_cap must be >= 1")
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8)
+        dev = self.device
+        T, rows, _, _ = self._push_plan_rows(tables, tie, seed, mask, plan_cap)
+        out = SimpleNamespace(num_rows=T, item=rows.item, t=rows.t, state=rows.state, push_from=rows.push_from,
+                              push_action=rows.push_action, cost=rows.cost, pos=rows.pos, obs=None)
+        out.puzzle_id = self.puzzle_id[rows.item.to(torch.int64)].contiguous() if T > 0 else \
+            torch.zeros((0,), dtype=torch.int32, device=dev)
+        out.choice = encode_push_choice(rows.push_from, rows.push_action, self.pset.max_height, self.pset.max_width)
+        if observation == "cells":
+            out.obs = torch.empty((T,) + self.engine.cells_shape(), dtype=torch.uint8, device=dev)
+            if T > 0:
+                self.engine.render_cells(out.puzzle_id, out.pos, out.obs)
+        elif observation is not None:
+            storage, out.obs = self.engine.alloc_obs(T)
+            if T > 0:
+                self.engine.render(out.puzzle_id, out.pos, storage)
+        if masks:
+            out.push_mask = push_mask(self.engine, out.puzzle_id, out.pos)[0] if T > 0 else \
+                torch.zeros((0, self.pset.max_height, self.pset.max_width), dtype=torch.uint8, device=dev)
+        return out
+
+    def _push_plan_rows(self, tables, tie: str, seed: int, mask: Optional[torch.Tensor], plan_cap: int):
+        """The front half of ``optimal_push_demonstrations``: ``(T, rows, plans, offset)`` -- the query, one plans launch per
+        table, the ``cumsum``, the one wait for the number of rows T and one emit launch per table.  ``tables`` are this
+        environment's own, ``mask`` uint8 on the device or None."""
+        from .search import PushRows, _push_plans_outputs
+
         B, dev = self.num_envs, self.device
         q = self.push_cost_to_go(tables, mask=mask)
         # (no plan is longer than a table's largest cost: the buffers need no more columns; a cost beyond plan_cap is cut as ever)
@@ -764,23 +790,40 @@ class VecPushWorld:
                               (((), torch.int32), ((), torch.int32), ((), torch.int32), ((2,), torch.int8), ((), torch.uint8),
                                ((), torch.int32), ((self.num_objects_padded, 2), torch.int8))),
                             torch.zeros((1,), dtype=torch.int32, device=dev).view(torch.uint32), 0)
-        out = SimpleNamespace(num_rows=T, item=rows.item, t=rows.t, state=rows.state, push_from=rows.push_from,
-                              push_action=rows.push_action, cost=rows.cost, pos=rows.pos, obs=None)
-        out.puzzle_id = self.puzzle_id[rows.item.to(torch.int64)].contiguous() if T > 0 else \
-            torch.zeros((0,), dtype=torch.int32, device=dev)
-        out.choice = encode_push_choice(rows.push_from, rows.push_action, self.pset.max_height, self.pset.max_width)
-        if observation == "cells":
-            out.obs = torch.empty((T,) + self.engine.cells_shape(), dtype=torch.uint8, device=dev)
-            if T > 0:
-                self.engine.render_cells(out.puzzle_id, out.pos, out.obs)
-        elif observation is not None:
-            storage, out.obs = self.engine.alloc_obs(T)
-            if T > 0:
-                self.engine.render(out.puzzle_id, out.pos, storage)
-        if masks:
-            out.push_mask = push_mask(self.engine, out.puzzle_id, out.pos)[0] if T > 0 else \
-                torch.zeros((0, self.pset.max_height, self.pset.max_width), dtype=torch.uint8, device=dev)
-        return out
+        return T, rows, plans, offset
+
+    def fewest_push_plans(self, tables, tie: str = "lowest", seed: int = 0, mask: Optional[torch.Tensor] = None,
+                          plan_cap: int = 1024, push_cap: int = 256):
+        """Fewest-pushes plans IN PRIMITIVE ACTIONS from every (unmasked) environment's current state, read off
+        ``push_table``s: ``optimal_push_demonstrations``' pipeline up to its rows (without a render; plans of at most
+        ``push_cap`` pushes), then ``search.push_rows_to_plans`` -- one count launch, one write launch and one gather over the
+        rows.  Two host waits: the number of rows and the number of actions.
+
+        Returns a ``types.SimpleNamespace`` of device tensors: ``plans`` uint8 [B, plan_cap], ``plan_len`` int32 [B] and
+        ``pushes`` int32 [B] (the pushes of every plan).  ``plan_len`` is 0 for a goal state and -1 for a dead end, a state
+        outside every table, a masked environment or a push plan beyond ``push_cap``; a plan of more than ``plan_cap`` actions
+        keeps its length and its first ``plan_cap`` actions.  The walk to every push follows the parent actions of the walk
+        region, as ``step_push`` walks.  ``search.replay_plans(vec, vec.puzzle_id, r.plans, r.plan_len, pos=vec.pos)`` turns
+        the plans into primitive demonstration rows (rewards, dones, and observations through ``demonstrations``' renders)."""
+        from types import SimpleNamespace
+
+        from .search import push_rows_to_plans
+
+        tables = self._own_push_tables(tables)
+        if tie not in ("lowest", "uniform"):
+            raise ValueError("tie must be 'lowest' or 'uniform'")
+        if not 1 <= int(plan_cap) <= _capi.PLAN_MAX_ACTIONS:
+            raise ValueError(f"plan_cap must be in 1 .. {_capi.PLAN_MAX_ACTIONS}")
+        if int(push_cap) < 1:
+            raise ValueError("push_cap must be >= 1")
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        T, rows, push_plans, offset = self._push_plan_rows(tables, tie, seed, mask, push_cap)
+        ids = self.puzzle_id[rows.item.to(torch.int64)].contiguous() if T > 0 else \
+            torch.zeros((0,), dtype=torch.int32, device=self.device)
+        plans, plan_len, pushes = push_rows_to_plans(self.engine, ids, rows, offset, plan_cap=int(plan_cap))
+        plan_len = torch.where(push_plans.length < 0, torch.full_like(plan_len, -1), plan_len)
+        return SimpleNamespace(plans=plans, plan_len=plan_len, pushes=pushes)
 
     def set_states(self, pos: np.ndarray) -> None:
         self.pos.copy_(torch.as_tensor(np.asarray(pos), dtype=torch.int8))
