@@ -353,6 +353,30 @@ int64_t pw_engine_obs_stride(const PwEngine* e);       /* recommended env stride
                                       further candidate is allocated once it is spent (the best so far is kept and tuned) -- bounds the
                                       constructor when several ranks of a node screen at the same time */
 #define PW_OPT_OBS_SCREEN_MS 41      /* read-only: milliseconds the last pw_obs_alloc_tuned spent allocating, screening and releasing candidates */
+/* The frame padding of a RETAINED observation buffer is written once.  A puzzle is centred in the frame, so every pixel row above and
+ * below it is zero whatever the state -- on the Level-1 pool two thirds of the 4 KiB pages of a uint8 ppc-3 buffer hold nothing else.
+ * With PW_OPT_OBS_PADDING_ONCE the engine keeps ONE retained observation: a buffer of pw_obs_alloc / pw_obs_alloc_tuned (at its own
+ * stride, pw_engine_obs_stride rounded up to 512) whose padding was last written by a full render, by this engine, of the puzzle_id
+ * buffer and batch of the current pw_batch_bind.  While that holds, pw_step_render of that batch into that buffer launches the
+ * ppc-3 page kernel over the LIVE pages only -- the pages in which the full kernel stores at least one 16-byte chunk of a puzzle's
+ * own pixel rows (a whole page of one environment, or the tail of one and the head of the next); it stays one timed render launch.
+ *   - pw_render always writes every byte and, on such a buffer, establishes the retained observation: it is the repair path.  So do
+ *     the renders of pw_engine_tune_render / pw_obs_alloc_tuned, and a pw_step_render that found nothing retained.
+ *   - It ends with pw_batch_bind, pw_batch_unbind, the re-bind that pw_reset / pw_resample on the bound puzzle_id buffer do behind
+ *     themselves, pw_obs_free, a render of other ids or another batch into the buffer, and with PW_OPT_PAGE_SLICE_ENVS, PW_OPT_RENDER_KERNEL
+ *     or PW_OPT_FUSED_STEP_RENDER being set (none of them applies while one is set; neither does a batch that needs slices).
+ *   - The contents of a retained buffer are the library's: bytes a caller writes into its padding stay there until the next pw_render.
+ *   - A captured pw_step_render launch replays the form it was captured in (live pages or full), like the launches of a bound batch.
+ * Buffers of the caller's own, pw_step_render_delta, the row-page kernel (ppc > 3) and the per-environment kernels are not affected.
+ * The list of live pages is built on the device from the ids (pw_batch_bind reads its length back with the segment count; after a
+ * re-bind in-stream the launch takes the upper bound and the surplus workgroups return); a step allocates nothing and never waits
+ * for the host.  pw_engine_tune_render measures the launch configuration of the live launch in a second pass and keeps it apart from
+ * PW_OPT_PAGE_* (which, set by hand afterwards, hold for both launches again). */
+#define PW_OPT_OBS_PADDING_ONCE 53   /* 0 (default) every pw_step_render writes every byte; 1 as described above.  A/B runs: 2 = 1 with the grid of
+                                      the full render, the workgroups of padding pages returning at once; 3 = 1 with the list of live pages
+                                      (1 takes whichever the tuner measured faster, the list when it never ran) */
+#define PW_OPT_OBS_LIVE_PAGES 54     /* read-only: length of the live-page list of the retained observation, 0 when nothing is retained (synchronises
+                                      the device when the list was last rebuilt in-stream) */
 int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value);
 int64_t pw_engine_get_option(const PwEngine* e, int32_t option);
 /* Durations (milliseconds) of the render launches recorded since the last call, in launch order

@@ -340,6 +340,9 @@ OPTIONS = {
     "bind_lanes": 42,          # lanes per environment of the segments: 0 automatic, 1 / 2 / 3 / 4 = at most 1 / 2 / 4 / 8
     "bind_puzzles": 38,        # read-only: puzzles of the set that can be bound (table block within 16 KB of LDS)
     "bind_mismatches": 39,     # read-only: environments found with another puzzle id than the one they were bound to
+    "obs_padding_once": 53,    # pw_step_render into a retained library-owned buffer of the bound batch renders the live pages only: 0 off, 1 on
+                               # (2 / 3: on, with the early-exit / the list form -- A/B runs)
+    "obs_live_pages": 54,      # read-only: length of the live-page list of the retained observation (0: nothing retained)
 }
 _OPTION_VALUES = {"group": 0, "wave": 1, "lane": 2, "auto": 0, "page": 0, "lds": 1, "big": 3, "all": 1, "none": 2,
                   "forward": 0, "reverse": 1, "never": 2**31}

@@ -725,6 +725,8 @@ int pw_engine_create(const PwPuzzleSet* s, const PwEngineConfig* cfg, PwEngine**
   e->tuned_ns = 0;
   e->d_rec = nullptr;
   e->rec_cap = 0;
+  e->ret = PwRetained{};  // (option 0, nothing retained, no list)
+  e->ret.form = 1;
   e->prof_used = 0;
   // Static zone-colour tables (walls, agent walls, background, goal outlines) of every puzzle in
   // the layout the render kernel of this engine streams from: row stride pad_w with the puzzle
@@ -929,6 +931,7 @@ void pw_engine_destroy(PwEngine* e) {
   if (e->d_boards) (void)hipFree(e->d_boards);
   if (e->d_qdesc) (void)hipFree(e->d_qdesc);
   if (e->d_rec) (void)hipFree(e->d_rec);
+  if (e->ret.d_live) (void)hipFree(e->ret.d_live);
   if (e->d_ovl) (void)hipFree(e->d_ovl);
   if (e->d_ovl_dir) (void)hipFree(e->d_ovl_dir);
   if (e->d_push_dir) (void)hipFree(e->d_push_dir);
@@ -994,6 +997,7 @@ int64_t pw_engine_obs_stride(const PwEngine* e) try {
 }
 
 static void rebind_async(PwEngine* e, const int32_t* puzzle_id, int32_t batch, hipStream_t st);
+static bool live_build(PwEngine* e, const int32_t* puzzle_id, int32_t batch, hipStream_t st, bool may_alloc);
 
 int pw_reset(PwEngine* e, const int32_t* puzzle_id, const uint8_t* mask, int8_t* pos, int32_t* steps,
              uint8_t* terminated, uint8_t* truncated, int32_t batch, void* stream) try {
@@ -1086,6 +1090,8 @@ static void bind_launch(PwEngine* e, hipStream_t st) {
 static void rebind_async(PwEngine* e, const int32_t* puzzle_id, int32_t batch, hipStream_t st) {
   PwBind* b = e->bind;
   if (!b || b->puzzle_id != puzzle_id || b->batch != batch) return;
+  e->ret.valid = false;  // other puzzles, other padding: the next render is a full one
+  if (e->ret.list_pid == puzzle_id && e->ret.list_batch == batch) (void)live_build(e, puzzle_id, batch, st, false);
   bind_launch(e, st);
   b->seg_grid = b->seg_cap;
   b->lds_bytes = e->seg_max_bytes;
@@ -1133,14 +1139,111 @@ static bool ensure_rec(PwEngine* e, int32_t batch) {
   return true;
 }
 
-// grid of a page-ordered launch: orders 1 and 2 permute a rounded-up index range; the surplus workgroups exit
-static unsigned page_grid(uint32_t n_pages, uint32_t order, uint32_t run_log2) {
-  if (order == 1u) return (n_pages + 7u) & ~7u;
-  if (order == 2u) {
-    const unsigned span = 8u << run_log2;
-    return (n_pages + span - 1u) / span * span;
+// ---- the retained observation (PW_OPT_OBS_PADDING_ONCE, PwRetained) ---------------------------------------------------
+static int64_t owned_obs_stride(const PwEngine* e) { return (e->obs_bytes + 511) & ~int64_t(511); }
+
+// the ppc-3 page kernel renders such a batch in ONE launch, into a buffer with the stride of the library's own
+static bool live_applies(const PwEngine* e, int64_t env_stride, int32_t batch) {
+  if (!page_path(e, env_stride) || e->rowpage || e->force_fused || e->page_slice_envs > 0) return false;
+  if (env_stride != owned_obs_stride(e)) return false;
+  const uint64_t cpe = static_cast<uint64_t>(env_stride / 16);
+  return static_cast<uint64_t>(batch) <= std::max<uint64_t>(1, ((1ull << 31) - 512) / cpe);
+}
+
+// Builds the live-page list of (puzzle_id, batch) on `st` (device guard held by the caller).  The length stays on the device
+// (n_live = -1) until a caller that synchronises anyway copies it from d_count.  may_alloc: the caller is no steady-state
+// path (hipFree of a smaller list synchronises the device, so nothing in flight still reads it).
+static bool live_build(PwEngine* e, const int32_t* puzzle_id, int32_t batch, hipStream_t st, bool may_alloc) {
+  PwRetained& r = e->ret;
+  r.list_pid = nullptr;
+  r.n_live = -1;
+  const int64_t stride = owned_obs_stride(e);
+  if (!live_applies(e, stride, batch)) return false;
+  const uint32_t cpe = static_cast<uint32_t>(stride / 16);
+  const uint32_t n_pages = static_cast<uint32_t>((static_cast<uint64_t>(batch) * cpe + 255) / 256);
+  if (r.list_cap < static_cast<int64_t>(n_pages)) {
+    if (!may_alloc) return false;
+    if (r.d_live) (void)hipFree(r.d_live);
+    r.d_live = nullptr;
+    r.list_cap = 0;
+    const size_t blk_cap = (static_cast<size_t>(n_pages) + 1023) / 1024;
+    if (hipMalloc(reinterpret_cast<void**>(&r.d_live), (static_cast<size_t>(n_pages) + blk_cap + 4) * 4) != hipSuccess) {
+      (void)hipGetLastError();  // no list: pw_step_render keeps rendering in full
+      return false;
+    }
+    r.d_blk = r.d_live + n_pages;
+    r.d_count = r.d_blk + blk_cap;
+    r.list_cap = n_pages;
   }
-  return n_pages;
+  LiveArgs a;
+  a.hdrs = e->set->d_headers;
+  a.puzzle_id = puzzle_id;
+  a.num_puzzles = e->set->count;
+  a.batch = batch;
+  a.pad_h = e->pad_h;
+  a.pad_w = e->pad_w;
+  a.chunks_per_env = cpe;
+  a.n_chunks = static_cast<uint32_t>((e->obs_bytes + 15) / 16);
+  a.n_pages = n_pages;
+  a.n_blk = (n_pages + 1023u) / 1024u;
+  a.blk = r.d_blk;
+  a.live = r.d_live;
+  a.count = r.d_count;
+  if (e->page_f32) {
+    hipLaunchKernelGGL(pw_live_count_kernel<4>, dim3(a.n_blk), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pw_live_scan_kernel, dim3(1), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(pw_live_fill_kernel<4>, dim3(a.n_blk), dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(pw_live_count_kernel<1>, dim3(a.n_blk), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pw_live_scan_kernel, dim3(1), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(pw_live_fill_kernel<1>, dim3(a.n_blk), dim3(256), 0, st, a);
+  }
+  r.list_pid = puzzle_id;
+  r.list_batch = batch;
+  r.n_pages = n_pages;
+  return true;
+}
+
+static bool bound_to(const PwEngine* e, const int32_t* puzzle_id, int32_t batch) {
+  return e->bind && e->bind->puzzle_id == puzzle_id && e->bind->batch == batch;
+}
+
+// something other than a render of the retained (puzzle_id, batch) wrote into [ra.obs, + batch * stride): where that meets the
+// retained buffer, its padding is no longer known
+static void retained_overwritten(PwEngine* e, const RenderArgs& ra, int32_t batch) {
+  PwRetained& r = e->ret;
+  if (!r.valid) return;
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(ra.obs), hi = lo + static_cast<uint64_t>(batch) * static_cast<uint64_t>(ra.env_stride);
+  const uintptr_t rlo = reinterpret_cast<uintptr_t>(r.obs), rhi = rlo + static_cast<uint64_t>(r.batch) * static_cast<uint64_t>(r.stride);
+  if (lo < rhi && rlo < hi) r.valid = false;
+}
+
+// A full render of (ra.puzzle_id, batch) into ra.obs has been launched: it establishes the retained observation where the
+// rule allows one (header, PW_OPT_OBS_PADDING_ONCE), and ends the validity of a retained buffer it wrote other bytes into.
+static void retained_after_full_render(PwEngine* e, const RenderArgs& ra, int32_t batch) {
+  PwRetained& r = e->ret;
+  bool owned = false;
+  for (const PwObsBuf& b : e->obs_bufs)
+    owned = owned || (b.ptr == ra.obs && static_cast<uint64_t>(batch) * static_cast<uint64_t>(ra.env_stride) <= b.bytes);
+  if (r.option && owned && live_applies(e, ra.env_stride, batch) && bound_to(e, ra.puzzle_id, batch) &&
+      r.list_pid == ra.puzzle_id && r.list_batch == batch) {
+    r.valid = true;
+    r.obs = ra.obs;
+    r.stride = ra.env_stride;
+    r.batch = batch;
+    r.puzzle_id = ra.puzzle_id;
+    return;
+  }
+  retained_overwritten(e, ra, batch);
+}
+
+// pw_step_render may launch the live pages only: 0 no, 1 the list form, 2 the early-exit form
+static int retained_live_form(const PwEngine* e, const RenderArgs& ra, int32_t batch) {
+  const PwRetained& r = e->ret;
+  if (!r.valid || !r.option || r.obs != ra.obs || r.stride != ra.env_stride || r.batch != batch || r.puzzle_id != ra.puzzle_id ||
+      !bound_to(e, ra.puzzle_id, batch) || r.list_pid != ra.puzzle_id || r.list_batch != batch || !live_applies(e, ra.env_stride, batch))
+    return 0;
+  return r.option == 2 ? 2 : (r.option == 3 ? 1 : r.form);
 }
 
 static void launch_rowpage(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st) {
@@ -1189,7 +1292,8 @@ static void launch_rowpage(PwEngine* e, const RenderArgs& ra, int32_t batch, hip
 }
 
 // rec_ready: the group step kernel of this call already left the page records of (puzzle_id, pos) in e->d_rec
-static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready) {
+// live_form: the caller checked (retained_live_form) that only the live pages need rendering: 1 the list, 2 the early exits
+static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready, int live_form) {
   const bool paged = page_path(e, ra.env_stride) && !ra.do_step && !ra.skip_movables && ensure_rec(e, batch);
   if (paged && !rec_ready) {
     PageRecArgs pa{ra.hdrs, ra.puzzle_id, ra.pos, static_cast<PageRec*>(e->d_rec), batch, ra.np, e->set->count};
@@ -1228,23 +1332,32 @@ static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipS
       ca.magic_cellrow = static_cast<uint32_t>(((1ull << 32) + d - 1) / d);
       const uint64_t total = static_cast<uint64_t>(nb) * cpe;
       ca.n_pages = static_cast<uint32_t>((total + 255) / 256);
-      ca.order = static_cast<uint32_t>(e->page_order);
-      ca.run_log2 = static_cast<uint32_t>(ca.order == 1u ? std::min(e->page_run_log2, 3) : e->page_run_log2);
+      // the live launch has a configuration of its own once the tuner has measured one (its trial launches set the engine's)
+      const PwRetained& rt = e->ret;
+      const bool own_cfg = live_form && rt.tuned && !e->tuning;
+      const int order = own_cfg ? rt.order : e->page_order, run_log2 = own_cfg ? rt.run_log2 : e->page_run_log2;
+      const int load_all = own_cfg ? rt.load_all : e->page_load_all;
+      ca.order = static_cast<uint32_t>(order);
+      ca.run_log2 = static_cast<uint32_t>(ca.order == 1u ? std::min(run_log2, 3) : run_log2);
       ca.zero_page = reinterpret_cast<const uint8_t*>(e->d_scratch) + 4096;
-      const unsigned grid = page_grid(ca.n_pages, ca.order, ca.run_log2);
-      const size_t lds_pad = static_cast<size_t>(e->page_lds_pad_kb) * 1024;
+      ca.live = nullptr;
+      ca.live_n = nullptr;
+      ca.n_live = 0;
+      unsigned grid = page_grid(ca.n_pages, ca.order, ca.run_log2);
+      if (live_form == 1) {
+        ca.live = rt.d_live;
+        ca.live_n = rt.n_live < 0 ? rt.d_count : nullptr;  // list rebuilt in-stream: the upper bound, the surplus workgroups return
+        ca.n_live = rt.n_live < 0 ? ca.n_pages : static_cast<uint32_t>(rt.n_live);
+        grid = page_grid(ca.n_live, ca.order, ca.run_log2);
+        if (grid == 0) continue;
+      }
+      const size_t lds_pad = static_cast<size_t>(own_cfg ? rt.lds_pad_kb : e->page_lds_pad_kb) * 1024;
       if (e->page_f32) {
         rp.estat = e->d_estat_page;  // the page kernels index the frame-layout zone table
         rp.estat_off = e->d_estat_page_off;
-        if (e->tuning && e->page_load_all) hipLaunchKernelGGL((pw_render_page_kernel<float, 1, true>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
-        else if (e->tuning) hipLaunchKernelGGL((pw_render_page_kernel<float, 1, false>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
-        else if (e->page_load_all) hipLaunchKernelGGL((pw_render_page_kernel<float, 0, true>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
-        else hipLaunchKernelGGL((pw_render_page_kernel<float, 0, false>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
+        launch_page<float>(e->tuning, load_all != 0, live_form, grid, lds_pad, st, rp, ca);
       } else {
-        if (e->tuning && e->page_load_all) hipLaunchKernelGGL((pw_render_page_kernel<uint8_t, 1, true>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
-        else if (e->tuning) hipLaunchKernelGGL((pw_render_page_kernel<uint8_t, 1, false>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
-        else if (e->page_load_all) hipLaunchKernelGGL((pw_render_page_kernel<uint8_t, 0, true>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
-        else hipLaunchKernelGGL((pw_render_page_kernel<uint8_t, 0, false>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
+        launch_page<uint8_t>(e->tuning, load_all != 0, live_form, grid, lds_pad, st, rp, ca);
       }
     }
     return;
@@ -1597,6 +1710,7 @@ int pw_batch_bind(PwEngine* e, const int32_t* puzzle_id, int32_t batch, int64_t*
   if (batch <= 0 || !puzzle_id) return pw_fail(PW_EINVAL, "pw_batch_bind: puzzle_id must be a device buffer of batch > 0 ids");
   PwDeviceGuard guard(e->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  e->ret.valid = false;  // (established again by the next full render of the new binding into a buffer of pw_obs_alloc)
   if (!e->d_seg_dir || e->seg_puzzles == 0) {  // nothing to bind to (PW_OPT_STEP_TABLES never): every call stays unbound
     if (hipStreamSynchronize(st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_batch_bind: stream synchronisation failed");
     release_bind(e);
@@ -1644,13 +1758,19 @@ int pw_batch_bind(PwEngine* e, const int32_t* puzzle_id, int32_t batch, int64_t*
   PwBind* b = e->bind;
   b->puzzle_id = puzzle_id;
   bind_launch(e, st);
+  // the live pages of this assignment in a library-owned observation buffer; their number comes back with the segment count
+  const bool have_live = live_build(e, puzzle_id, batch, st, true);
+  uint32_t n_live = 0;
   int32_t meta[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipError_t err = hipMemcpyAsync(meta, b->meta, sizeof(meta), hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess && have_live) err = hipMemcpyAsync(&n_live, e->ret.d_count, 4, hipMemcpyDeviceToHost, st);
   if (err == hipSuccess) err = hipStreamSynchronize(st);
   if (err != hipSuccess) {
+    e->ret.list_pid = nullptr;
     release_bind(e);
     return pw_fail(PW_EDEVICE, std::string("pw_batch_bind: ") + hipGetErrorString(err));
   }
+  if (have_live) e->ret.n_live = n_live;
   for (int i = 0; i < 4; i++) b->info[i] = meta[i];
   b->seg_grid = std::max(meta[0], 1);  // (a grid of at least one workgroup: a batch without any segment launches one that leaves)
   b->lds_bytes = static_cast<uint32_t>(meta[4]);
@@ -1669,6 +1789,7 @@ int pw_batch_bind(PwEngine* e, const int32_t* puzzle_id, int32_t batch, int64_t*
 
 int pw_batch_unbind(PwEngine* e) try {
   if (!e) return pw_fail(PW_EINVAL, "null engine");
+  e->ret.valid = false;
   if (!e->bind) return PW_OK;
   // (its resident kernel may be running the binding's segments -- and the synchronisation below would wait for its idle limit)
   if (e->mailbox) return pw_fail(PW_EINVAL, "pw_batch_unbind: this engine has an open mailbox (pw_mailbox_close first)");
@@ -1689,6 +1810,7 @@ int pw_render(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* ob
   int rc = fill_render_args(e, puzzle_id, pos, obs, env_stride_bytes, batch, &ra);
   if (rc != PW_OK) return rc;
   launch_render(e, ra, batch, static_cast<hipStream_t>(stream));
+  retained_after_full_render(e, ra, batch);  // (every byte is written: the repair path of a retained buffer)
   return check_launch("pw_render");
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
@@ -1721,12 +1843,16 @@ int pw_step_render(PwEngine* e, const int32_t* puzzle_id, const uint8_t* actions
     attach_binding(e, &s1);
     if (page_path(e, env_stride_bytes) && ensure_rec(e, batch)) s1.rec = static_cast<PageRec*>(e->d_rec);
     const bool rec_ready = launch_one_step(e, s1, batch, st);
-    launch_render(e, ra, batch, st, rec_ready);
+    // a retained buffer (PW_OPT_OBS_PADDING_ONCE) holds its frame padding already: the pages with anything else only
+    const int live_form = retained_live_form(e, ra, batch);
+    launch_render(e, ra, batch, st, rec_ready, live_form);
+    if (!live_form) retained_after_full_render(e, ra, batch);
     return check_launch("pw_step_render");
   }
   ra.step = sa;
   ra.do_step = 1;
   launch_render(e, ra, batch, st);
+  retained_after_full_render(e, ra, batch);
   return check_launch("pw_step_render");
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
@@ -1771,6 +1897,8 @@ int pw_step_render_delta(PwEngine* e, const int32_t* puzzle_id, const uint8_t* a
   StepArgs sa = ra.step;
   rc = fill_render_args(e, puzzle_id, pos, obs, env_stride_bytes, batch, &ra);
   if (rc != PW_OK) return rc;
+  // (the redraw of the retained batch stays inside its puzzles' own rows; that of other ids or another layout need not)
+  if (!(e->ret.obs == obs && e->ret.stride == env_stride_bytes && e->ret.batch == batch && e->ret.puzzle_id == puzzle_id)) retained_overwritten(e, ra, batch);
   if (e->dirty_cap < batch) {
     if (e->d_dirty) (void)hipFree(e->d_dirty);
     e->d_dirty = nullptr;
@@ -2079,14 +2207,17 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
       return PW_OK;
     case PW_OPT_FUSED_STEP_RENDER:
       e->force_fused = value != 0;
+      e->ret.valid = false;
       return PW_OK;
     case PW_OPT_RENDER_KERNEL:
       if (value < 0 || value > 1) return pw_fail(PW_EINVAL, "PW_OPT_RENDER_KERNEL: 0 automatic, 1 per-environment LDS kernel");
       e->force_lds_render = value != 0;
+      e->ret.valid = false;
       return PW_OK;
     case PW_OPT_PAGE_SLICE_ENVS:
       if (value < 0) return pw_fail(PW_EINVAL, "PW_OPT_PAGE_SLICE_ENVS must be >= 0");
       e->page_slice_envs = value;
+      e->ret.valid = false;
       return PW_OK;
     case PW_OPT_SEARCH_CHUNK:
       if (value < 0) return pw_fail(PW_EINVAL, "PW_OPT_SEARCH_CHUNK must be >= 0");
@@ -2206,20 +2337,24 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
     case PW_OPT_PAGE_ORDER:
       if (value < 0 || value > 2) return pw_fail(PW_EINVAL, "PW_OPT_PAGE_ORDER: 0 address order, 1 eighth per XCD, 2 runs per XCD");
       e->page_order = static_cast<int>(value);
+      e->ret.tuned = false;  // (a launch configuration set by hand holds for the live launch too)
       return PW_OK;
     case PW_OPT_PAGE_RUN_LOG2:
       if (value < 0 || value > 20) return pw_fail(PW_EINVAL, "PW_OPT_PAGE_RUN_LOG2: 0 .. 20 (0 .. 2 with page order 1)");
       e->page_run_log2 = static_cast<int>(value);
+      e->ret.tuned = false;
       return PW_OK;
     case PW_OPT_PAGE_LDS_PAD_KB:
       if (value < 0 || value > 48) return pw_fail(PW_EINVAL, "PW_OPT_PAGE_LDS_PAD_KB: 0 .. 48");
       e->page_lds_pad_kb = static_cast<int>(value);
+      e->ret.tuned = false;
       return PW_OK;
     case PW_OPT_TUNED_NS:
     case PW_OPT_STEP_TABLE_BYTES:
     case PW_OPT_STEP_TABLE_PUZZLES:
     case PW_OPT_EXPAND_FORM:
     case PW_OPT_CELLS_BASE_BYTES:
+    case PW_OPT_OBS_LIVE_PAGES:
       return pw_fail(PW_EINVAL, "read-only option");
     case PW_OPT_STEP_TABLES: {
       if (value < 0 || value > 3)
@@ -2232,6 +2367,13 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
     case PW_OPT_PAGE_LOAD_ALL:
       if (value < 0 || value > 1) return pw_fail(PW_EINVAL, "PW_OPT_PAGE_LOAD_ALL: 0 or 1");
       e->page_load_all = static_cast<int>(value);
+      e->ret.tuned = false;
+      return PW_OK;
+    case PW_OPT_OBS_PADDING_ONCE:
+      if (value < 0 || value > 3)
+        return pw_fail(PW_EINVAL, "PW_OPT_OBS_PADDING_ONCE: 0 off, 1 on (2 / 3: on, with the early-exit / the list form of the live launch)");
+      e->ret.option = static_cast<int>(value);
+      e->ret.valid = false;  // (established by the next full render)
       return PW_OK;
     case PW_OPT_OBS_CHUNK_MB:
       if (value < 0 || value > 4096) return pw_fail(PW_EINVAL, "PW_OPT_OBS_CHUNK_MB: 0 (the default, 32 MiB) .. 4096");
@@ -2316,6 +2458,15 @@ int64_t pw_engine_get_option(const PwEngine* e, int32_t option) try {
     case PW_OPT_PAGE_LDS_PAD_KB: return e->page_lds_pad_kb;
     case PW_OPT_TUNED_NS: return e->tuned_ns;
     case PW_OPT_PAGE_LOAD_ALL: return e->page_load_all;
+    case PW_OPT_OBS_PADDING_ONCE: return e->ret.option;
+    case PW_OPT_OBS_LIVE_PAGES: {
+      if (!e->ret.valid) return 0;
+      if (e->ret.n_live >= 0) return e->ret.n_live;
+      uint32_t n = 0;  // (list rebuilt in-stream: its length is on the device)
+      PwDeviceGuard guard(e->set->device);
+      if (hipMemcpy(&n, e->ret.d_count, 4, hipMemcpyDeviceToHost) != hipSuccess) return pw_fail(PW_EDEVICE, "PW_OPT_OBS_LIVE_PAGES: copy failed");
+      return n;
+    }
     case PW_OPT_STEP_TABLES: return e->step_tables;
     case PW_OPT_STEP_TABLE_BYTES: return e->ovl_bytes;
     case PW_OPT_STEP_TABLE_PUZZLES: return e->ovl_puzzles;
@@ -2420,6 +2571,64 @@ static int tune_render_impl(PwEngine* e, const RenderArgs& ra, int32_t batch, hi
       }
     }
   }
+  // Second pass (PW_OPT_OBS_PADDING_ONCE): the same candidates for the launch of the live pages only -- a third of the pages in
+  // a sparser write front need not like the order and the occupancy cap of the full sweep -- and, in the configuration that
+  // wins, the early-exit form against the list.  `obs` is fully rendered here, so these launches write the same bytes again.
+  PwRetained& rt = e->ret;
+  if (rt.option && err == hipSuccess && live_applies(e, ra.env_stride, batch) && live_build(e, ra.puzzle_id, batch, st, true)) {
+    uint32_t n_live = 0;
+    err = hipMemcpyAsync(&n_live, rt.d_count, 4, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err == hipSuccess) {
+      rt.n_live = n_live;
+      TuneScope scope(e);
+      const int n_cand = kNumTuneCand;  // (live_applies: the ppc-3 page kernel)
+      auto measure_live = [&](int c, int reps, int form) {
+        apply_tune_cand(e, c);
+        launch_render(e, ra, batch, st, true, form);
+        if (err == hipSuccess) err = hipEventRecord(ev0, st);
+        for (int k = 0; k < reps; k++) launch_render(e, ra, batch, st, true, form);
+        if (err == hipSuccess) err = hipEventRecord(ev1, st);
+        if (err == hipSuccess) err = hipEventSynchronize(ev1);
+        float ms = 0.0f;
+        if (err == hipSuccess) err = hipEventElapsedTime(&ms, ev0, ev1);
+        return ms / static_cast<float>(reps);
+      };
+      std::vector<std::pair<float, int>> first;
+      for (int c = 0; c < n_cand && err == hipSuccess; c++) first.push_back({measure_live(c, 5, 1), c});
+      std::sort(first.begin(), first.end());
+      int lbest = first.empty() ? 0 : first[0].second;
+      float lbest_ms = 0.0f;
+      for (int k = 0; k < 3 && k < static_cast<int>(first.size()) && err == hipSuccess; k++) {
+        const float ms = measure_live(first[k].second, 12, 1);
+        if (k == 0 || ms < lbest_ms) {
+          lbest = first[k].second;
+          lbest_ms = ms;
+        }
+      }
+      // the early exits keep the grid of the full render: in the list's configuration and in the full render's
+      int ebest = lbest;
+      float exit_ms = err == hipSuccess ? measure_live(lbest, 12, 2) : 0.0f;
+      if (err == hipSuccess && best != lbest) {
+        const float ms = measure_live(best, 12, 2);
+        if (ms < exit_ms) {
+          ebest = best;
+          exit_ms = ms;
+        }
+      }
+      if (err == hipSuccess) {
+        rt.form = exit_ms < lbest_ms ? 2 : 1;
+        const int keep = rt.form == 2 ? ebest : lbest;
+        rt.tuned = true;
+        rt.order = kTuneCand[keep][0];
+        rt.run_log2 = kTuneCand[keep][1];
+        rt.lds_pad_kb = kTuneCand[keep][2];
+        rt.load_all = kTuneCand[keep][3];
+        rt.list_ns = static_cast<int64_t>(lbest_ms * 1.0e6f);
+        rt.exit_ns = static_cast<int64_t>(exit_ms * 1.0e6f);
+      }
+    }
+  }
   (void)hipEventDestroy(ev0);
   (void)hipEventDestroy(ev1);
   apply_tune_cand(e, best);
@@ -2440,6 +2649,7 @@ int pw_engine_tune_render(PwEngine* e, const int32_t* puzzle_id, const int8_t* p
   PwDeviceGuard guard(e->set->device);
   int best = 0;
   rc = tune_render_impl(e, ra, batch, static_cast<hipStream_t>(stream), &best);
+  if (rc == PW_OK) retained_after_full_render(e, ra, batch);
   return rc != PW_OK ? rc : best;
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
@@ -2597,6 +2807,10 @@ int pw_obs_free(PwEngine* e, void* obs) try {
     if (e->obs_bufs[i].ptr != obs) continue;
     PwDeviceGuard guard(e->set->device);
     (void)hipDeviceSynchronize();  // nothing in flight may still write the buffer
+    if (e->ret.obs == obs) {
+      e->ret.valid = false;
+      e->ret.obs = nullptr;
+    }
     release_obs_buf(e->obs_bufs[i]);
     e->obs_bufs.erase(e->obs_bufs.begin() + static_cast<std::ptrdiff_t>(i));
     return PW_OK;
@@ -2732,8 +2946,13 @@ int pw_obs_alloc_tuned(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos,
     }
   }
   *obs = cands[best].buf.ptr;
+  const int tuned_index = cands[best].idx;
   e->obs_bufs.push_back(std::move(cands[best].buf));
-  return cands[best].idx;
+  {  // the tuner left the buffer fully rendered: a bound batch may retain it from here on
+    RenderArgs ra;
+    if (fill_render_args(e, puzzle_id, pos, *obs, stride, batch, &ra) == PW_OK) retained_after_full_render(e, ra, batch);
+  }
+  return tuned_index;
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
 }

@@ -119,7 +119,34 @@ struct PwBind {
   uint32_t lds_bytes;        // dynamic LDS of the launches: the largest block among the bound puzzles (after an asynchronous re-bind:
                              // the largest block of the set)
 };
+// The retained observation of an engine (PW_OPT_OBS_PADDING_ONCE): ONE library-owned buffer whose frame padding was last written
+// by a full render of the bound batch, so that pw_step_render may leave it alone -- and the list of the pages that hold
+// anything else.  The list is a function of the puzzle ids, the batch size and the frame (the stride of library-owned buffers);
+// it is built wherever the ids are looked at anyway (pw_batch_bind, the re-bind behind pw_reset / pw_resample, the tuner).
+struct PwRetained {
+  int option;                // PW_OPT_OBS_PADDING_ONCE: 0 off, 1 on, 2 on with the early-exit form, 3 on with the list form
+  bool valid;                // the padding of `obs` is written and nothing but this engine's renders of (puzzle_id, batch) touched it since
+  void* obs;
+  int64_t stride;
+  int32_t batch;
+  const int32_t* puzzle_id;
+  // the live-page list
+  uint32_t* d_live;          // one allocation: live [list_cap], blk [ceil(list_cap / 1024)], count
+  uint32_t *d_blk, *d_count;
+  int64_t list_cap;          // pages the allocation holds
+  const int32_t* list_pid;   // what the list was built from (NULL: no list)
+  int32_t list_batch;
+  uint32_t n_pages;          // pages of the buffer
+  int64_t n_live;            // length of the list, -1 = known to the device only (rebuilt in-stream)
+  // launch configuration of the live launch: what the tuner's second pass measured; without one, the engine's page options
+  bool tuned;
+  int order, run_log2, lds_pad_kb, load_all;
+  int form;                  // 1 list, 2 early exit: the faster one in the tuner's measurement (1 when never measured)
+  int64_t list_ns, exit_ns;  // nanoseconds per launch of the two forms in that configuration (0: never measured)
+};
+
 struct PwEngine {
+  PwRetained ret;
   const PwPuzzleSet* set;
   PwEngineConfig cfg;
   int np;            // padded object count of the pos layout

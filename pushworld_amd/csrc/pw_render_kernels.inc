@@ -32,7 +32,7 @@ struct RenderArgs {
   StepArgs step;
 };
 
-static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready = false);
+static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready = false, int live_form = 0);
 
 // LDS layout of the render kernels (dynamic):
 //   [0, 16)        8 zero guard entries in front of E
@@ -223,7 +223,22 @@ struct CopyArgs {
   uint32_t order;
   uint32_t run_log2;
   const uint8_t* zero_page;  // 4 KiB of zeros: what the every-page-loads instance loads for pages of the frame padding
+  // live-page launch of a retained observation buffer (kLive = 1, PW_OPT_OBS_PADDING_ONCE): workgroup i renders page live[i]
+  const uint32_t* live;      // pages with a chunk outside the frame padding, ascending
+  const uint32_t* live_n;    // device-side length of `live` when the host does not know it (list rebuilt in-stream: the grid is
+                             // the upper bound n_pages and the workgroups beyond the count return), else NULL
+  uint32_t n_live;           // length of `live` as the host knows it (ignored with live_n)
 };
+
+// grid of a page-ordered launch over n indices: orders 1 and 2 permute a rounded-up index range; the surplus workgroups exit
+__host__ __device__ inline unsigned page_grid(uint32_t n, uint32_t order, uint32_t run_log2) {
+  if (order == 1u) return (n + 7u) & ~7u;
+  if (order == 2u) {
+    const unsigned span = 8u << run_log2;
+    return (n + span - 1u) / span * span;
+  }
+  return n;
+}
 
 struct PageRecArgs {
   const PwPuzzleHeader* hdrs;
@@ -449,16 +464,32 @@ struct PageGeom {
 };
 
 template <int ES>
-__device__ __forceinline__ PageGeom page_geom(const RenderArgs& a, const PageRec& r) {
+__device__ __forceinline__ PageGeom page_geom_hw(int pad_h, int pad_w, int H, int W) {
   PageGeom g;
-  const int H = r.H, W = r.W;
-  const int pady = (a.pad_h - H) * 3 / 2, padx = (a.pad_w - W) * 3 / 2;
+  const int pady = (pad_h - H) * 3 / 2, padx = (pad_w - W) * 3 / 2;
   const int c0 = (padx + 2) / 3;
-  g.shift = 3 * (pady * a.pad_w * 3 + padx - 3 * c0);
-  const int row_b = 9 * a.pad_w * ES;  // one pixel row of the frame in bytes
+  g.shift = 3 * (pady * pad_w * 3 + padx - 3 * c0);
+  const int row_b = 9 * pad_w * ES;  // one pixel row of the frame in bytes
   g.nz_lo = (pady * row_b) >> 4;
   g.nz_hi = ((pady + 3 * H) * row_b + 15) >> 4;
   return g;
+}
+
+template <int ES>
+__device__ __forceinline__ PageGeom page_geom(const RenderArgs& a, const PageRec& r) {
+  return page_geom_hw<ES>(a.pad_h, a.pad_w, r.H, r.W);
+}
+
+// chunks [lo, hi) of an environment's image all lie in its frame padding (or there are none)
+__device__ __forceinline__ bool page_chunks_padding(const PageGeom& g, int lo, int hi) {
+  return lo >= hi || hi <= g.nz_lo || lo >= g.nz_hi;
+}
+
+// A page that holds the tail of one environment (its chunks from c_first on) and, with has_second, the head of the next
+// (whose image starts at local chunk `split`): every chunk the page kernel stores there is frame padding
+__device__ __forceinline__ bool page_tail_head_padding(const PageGeom& g0, const PageGeom& g1, int c_first, int split,
+                                                       int n_chunks, bool has_second) {
+  return page_chunks_padding(g0, c_first, n_chunks) && (!has_second || page_chunks_padding(g1, 0, min(256 - split, n_chunks)));
 }
 
 // The observation stores are NON-TEMPORAL: the written lines are not kept in L2, which keeps the static images
@@ -476,7 +507,11 @@ __device__ __forceinline__ PageGeom page_geom(const RenderArgs& a, const PageRec
 // page_loadall), and the instance the tuner picks on most fast-class buffers too.  Padding pages load from ONE 4 KiB page
 // of zeros (always cache resident: no HBM traffic, also for pools whose static images are not), the others their
 // static-image chunks (zeros where the frame padding begins): the bytes are the same.
-template <typename T, int kTag = 0, bool kLoadAll = false>
+// kLive (PW_OPT_OBS_PADDING_ONCE, pw_step_render into a retained buffer whose frame padding is known to be written): 1 = the
+// page order is applied to the index into the list of live pages, and the workgroup renders page live[i]; 2 = the grid of the
+// full render, and the workgroups of padding pages return before they load or store anything (the comparison variant).  The
+// pages that are rendered run the same code either way.
+template <typename T, int kTag = 0, bool kLoadAll = false, int kLive = 0>
 __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyArgs ca) {
   typedef pw_u32x4 u32x4;
   constexpr int ES = static_cast<int>(sizeof(T));
@@ -490,16 +525,25 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
 
   // ---- workgroup-uniform bookkeeping -------------------------------------------------------------
   uint32_t page = blockIdx.x;
+  uint32_t n_sweep = ca.n_pages;  // indices the page order permutes
+  if (kLive == 1) {
+    n_sweep = ca.n_live;
+    if (ca.live_n) {
+      n_sweep = *ca.live_n;
+      if (page >= page_grid(n_sweep, ca.order, ca.run_log2)) return;  // (beyond the range the order permutes onto itself)
+    }
+  }
   if (ca.order == 1u) {
     // 8 >> run_log2 contiguous parts: XCD k writes in part k mod parts, the XCDs sharing a part interleave its pages
     const uint32_t pl = 3u - ca.run_log2, parts = 1u << pl, k = page & 7u, j = page >> 3;
-    const uint32_t per = ((ca.n_pages + 7u) >> 3) << ca.run_log2;  // pages per part
+    const uint32_t per = ((n_sweep + 7u) >> 3) << ca.run_log2;  // pages per part
     page = (k & (parts - 1u)) * per + ((j << ca.run_log2) | (k >> pl));
   } else if (ca.order == 2u) {
     const uint32_t sb = ca.run_log2, j = page >> 3, k = page & 7u;
     page = ((((j >> sb) << 3) + k) << sb) | (j & ((1u << sb) - 1u));
   }
-  if (page >= ca.n_pages) return;
+  if (page >= n_sweep) return;
+  if (kLive == 1) page = ca.live[page];
   const uint32_t g0 = page * 256u;  // first 16-byte chunk of the page
   const uint32_t cpe = ca.chunks_per_env;
   // g0 / cpe without an integer division: float estimate (exact to +-1 for g0 < 2^31) + correction
@@ -520,6 +564,7 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
     // ---- 13 of 14 pages: the whole page lies inside one environment's image ----------------------
     const u32x4 zero = u32x4{0u, 0u, 0u, 0u};
     u32x4 v0 = zero, v1 = zero, v2 = zero, v3 = zero;
+    if (kLive == 2 && page_chunks_padding(g, c_first, c_first + 256)) return;
     if (!kLoadAll && (c_first + 256 <= g.nz_lo || c_first >= g.nz_hi)) {  // frame padding above / below the puzzle: no loads at all
       PAGE_STORE(v0, dst);
       PAGE_STORE(v1, dst + 1024);
@@ -574,6 +619,7 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
   const uint32_t env1 = min(env0 + 1u, last);
   const PageRec r1 = ca.rec[env1];
   const PageGeom g1 = page_geom<ES>(a, r1);
+  if (kLive == 2 && page_tail_head_padding(g, g1, c_first, split, static_cast<int>(ca.n_chunks), has_second)) return;
   const int valid0 = static_cast<int>(ca.n_chunks) - c_first;  // local chunks [0, valid0) of env0 carry image bytes
   const uint8_t* src0 = ca.simg + static_cast<int64_t>(r0.pid) * ca.simg_stride + static_cast<int64_t>(c_first) * 16;
   const uint8_t* src1 = ca.simg + static_cast<int64_t>(r1.pid) * ca.simg_stride - static_cast<int64_t>(split) * 16;
@@ -623,6 +669,130 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
     if (ok[k]) PAGE_STORE(v[k], dst + k * 1024);
 }
 #undef PAGE_STORE
+
+// host side: the instance of the page kernel for (dtype, trial launch, every page loads, live form)
+template <typename T, int kTag, bool kLoadAll>
+static void launch_page_form(int live_form, unsigned grid, size_t lds_pad, hipStream_t st, const RenderArgs& rp, const CopyArgs& ca) {
+  if (live_form == 1) hipLaunchKernelGGL((pw_render_page_kernel<T, kTag, kLoadAll, 1>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
+  else if (live_form == 2) hipLaunchKernelGGL((pw_render_page_kernel<T, kTag, kLoadAll, 2>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
+  else hipLaunchKernelGGL((pw_render_page_kernel<T, kTag, kLoadAll, 0>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
+}
+
+template <typename T>
+static void launch_page(bool tuning, bool load_all, int live_form, unsigned grid, size_t lds_pad, hipStream_t st, const RenderArgs& rp,
+                        const CopyArgs& ca) {
+  if (tuning && load_all) launch_page_form<T, 1, true>(live_form, grid, lds_pad, st, rp, ca);
+  else if (tuning) launch_page_form<T, 1, false>(live_form, grid, lds_pad, st, rp, ca);
+  else if (load_all) launch_page_form<T, 0, true>(live_form, grid, lds_pad, st, rp, ca);
+  else launch_page_form<T, 0, false>(live_form, grid, lds_pad, st, rp, ca);
+}
+
+
+// ------------------------------------------------------------------------------------
+// Live pages of a batch (PW_OPT_OBS_PADDING_ONCE): the pages of an observation buffer in which the page kernel stores at
+// least one chunk that is not frame padding -- the kernel's own conditions, from the puzzle ids alone.  Count per 1 024
+// pages, scan of the counts, scatter: `live` comes out in ascending page order, its length in *count.
+// ------------------------------------------------------------------------------------
+struct LiveArgs {
+  const PwPuzzleHeader* hdrs;
+  const int32_t* puzzle_id;
+  int32_t num_puzzles;
+  int32_t batch;
+  int32_t pad_h, pad_w;
+  uint32_t chunks_per_env;
+  uint32_t n_chunks;
+  uint32_t n_pages;
+  uint32_t n_blk;     // ceil(n_pages / 1024)
+  uint32_t* blk;      // [n_blk] live pages per 1 024 pages, then their exclusive prefix sums
+  uint32_t* live;     // [n_pages]
+  uint32_t* count;
+};
+
+template <int ES>
+__device__ __forceinline__ bool page_is_live(const LiveArgs& a, uint32_t page) {
+  const uint32_t g0 = page * 256u, cpe = a.chunks_per_env;
+  const uint32_t env0 = g0 / cpe;  // (< batch: g0 < batch * cpe)
+  const int c_first = static_cast<int>(g0 - env0 * cpe);
+  const PwPuzzleHeader& h0 = a.hdrs[pw_clamp_pid(a.puzzle_id[env0], a.num_puzzles)];
+  const PageGeom g = page_geom_hw<ES>(a.pad_h, a.pad_w, h0.H, h0.W);
+  if (c_first + 256 <= static_cast<int>(a.n_chunks)) return !page_chunks_padding(g, c_first, c_first + 256);
+  const int split = static_cast<int>(cpe) - c_first;
+  const uint32_t last = static_cast<uint32_t>(a.batch) - 1u;
+  const bool has_second = split < 256 && env0 + 1u <= last;
+  const PwPuzzleHeader& h1 = a.hdrs[pw_clamp_pid(a.puzzle_id[min(env0 + 1u, last)], a.num_puzzles)];
+  const PageGeom g1 = page_geom_hw<ES>(a.pad_h, a.pad_w, h1.H, h1.W);
+  return !page_tail_head_padding(g, g1, c_first, split, static_cast<int>(a.n_chunks), has_second);
+}
+
+// thread t of workgroup b looks at pages 1024 b + 4 t .. + 3: bit k of the result = page k is live
+template <int ES>
+__device__ __forceinline__ uint32_t live_flags4(const LiveArgs& a) {
+  const uint32_t p0 = blockIdx.x * 1024u + threadIdx.x * 4u;
+  uint32_t f = 0u;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; k++)
+    if (p0 + k < a.n_pages && page_is_live<ES>(a, p0 + k)) f |= 1u << k;
+  return f;
+}
+
+template <int ES>
+__global__ __launch_bounds__(256) void pw_live_count_kernel(LiveArgs a) {
+  __shared__ uint32_t total;
+  if (threadIdx.x == 0) total = 0u;
+  __syncthreads();
+  const uint32_t n = __popc(live_flags4<ES>(a));
+  if (n) atomicAdd(&total, n);
+  __syncthreads();
+  if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
+}
+
+// one workgroup: blk[] -> exclusive prefix sums, *count = the sum
+__global__ __launch_bounds__(1024) void pw_live_scan_kernel(LiveArgs a) {
+  __shared__ uint32_t buf[1024];
+  __shared__ uint32_t carry;
+  const uint32_t t = threadIdx.x;
+  if (t == 0) carry = 0u;
+  __syncthreads();
+  for (uint32_t base = 0; base < a.n_blk; base += 1024u) {
+    const uint32_t i = base + t;
+    const uint32_t v = i < a.n_blk ? a.blk[i] : 0u;
+    buf[t] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {
+      const uint32_t add = t >= d ? buf[t - d] : 0u;
+      __syncthreads();
+      buf[t] += add;
+      __syncthreads();
+    }
+    const uint32_t c = carry;
+    if (i < a.n_blk) a.blk[i] = c + buf[t] - v;
+    __syncthreads();
+    if (t == 1023u) carry = c + buf[1023];
+    __syncthreads();
+  }
+  if (t == 0) *a.count = carry;
+}
+
+template <int ES>
+__global__ __launch_bounds__(256) void pw_live_fill_kernel(LiveArgs a) {
+  __shared__ uint32_t buf[256];
+  const uint32_t t = threadIdx.x;
+  const uint32_t f = live_flags4<ES>(a);
+  const uint32_t n = __popc(f);
+  buf[t] = n;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256u; d <<= 1) {
+    const uint32_t add = t >= d ? buf[t - d] : 0u;
+    __syncthreads();
+    buf[t] += add;
+    __syncthreads();
+  }
+  uint32_t at = a.blk[blockIdx.x] + buf[t] - n;  // (< the sum of all counts <= n_pages)
+  const uint32_t p0 = blockIdx.x * 1024u + t * 4u;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; k++)
+    if ((f >> k) & 1u) a.live[at++] = p0 + k;
+}
 
 // ------------------------------------------------------------------------------------
 // Row-page render: the page-ordered kernel for every other frame whose pixel rows are at least 512 bytes

@@ -166,7 +166,11 @@ class VecPushWorld:
                 budget = min(total // 3, free // 2) if free > 0 else 4 * nbytes
                 tune_allocations = min(32, max(1, int(budget // nbytes)))
             owned = False
+            # a library-owned buffer of a bound batch with a fixed assignment keeps its frame padding: steps render the live pages only
+            padding_once = self._bind and not resample and "obs_padding_once" not in (engine_options or {})
             if tune and tune_allocations:
+                if padding_once:
+                    self.engine.set_option("obs_padding_once", 1)  # (before the tuner: it measures the live launch too)
                 # library-owned buffer: candidates are tuned on the initial states (reset() draws them again)
                 self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, None)
                 try:
@@ -181,6 +185,8 @@ class VecPushWorld:
                     warnings.warn(f"pw_obs_alloc_tuned failed ({exc}); using a torch-owned observation buffer", RuntimeWarning)
             self.obs_owned_by_library = owned
             if not owned:
+                if padding_once:
+                    self.engine.set_option("obs_padding_once", 0)
                 self._obs_storage, self.obs = self.engine.alloc_obs(self.num_envs)
                 if tune:
                     self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, None)
