@@ -1,5 +1,7 @@
 """The random-shape puzzles of tests/test_gpu_shapes.py and seeded lists of their states -- overlapping ones above all -- for
 the walk-region and push-search tests (tests/test_walk_shapes_host.py, test_gpu_walk_shapes.py, test_gpu_push_search_shapes.py).
+The runs of the best-first search over pushes (``PLANNER_*``, tests/test_push_planner_shapes_host.py and
+test_gpu_push_planner_shapes.py) and the push-step tests (test_gpu_push_step_shapes.py) use the same puzzles and lists.
 A helper, not a test.  Everything is in Python object order (``oracle.c_oracle.COraclePuzzle(text)``).
 
 Per case (n_movables, size, seed) the puzzle is the first draw of ``random_puzzle(np.random.default_rng(1000 + seed), n, size)``
@@ -69,6 +71,52 @@ MANY_START_18 = 15  # index into states(CASES[4]): 112 push rows, 6 of them out 
 MANY_START_32 = ((52, 13), (9, 51), (14, 27), (49, 37), (32, 1), (54, 10), (18, 49), (49, 4), (6, 7), (59, 25), (39, 6),
                  (3, 37), (19, 8), (49, 50), (45, 10), (54, 45), (43, 18), (50, 48), (1, 18), (5, 55), (53, 0), (43, 0),
                  (15, 30), (33, 21), (55, 19), (9, 42), (44, 13), (53, 49), (3, 60), (47, 31), (7, 33), (44, 30))
+
+# Runs of the best-first search over pushes (pw_push_planner_*, K17), chosen on the CPU: tests/test_push_planner_shapes_host.py
+# asserts what each group was chosen for and pins the ten info words of every run, tests/test_gpu_push_planner_shapes.py sends
+# every run through the device.  ``case``: one of CASES, or the name of a Level-1 puzzle; ``start``: None (the initial state),
+# an index into states(case), or a state; ``budget`` / ``max_states``: None for the defaults; ``rounds``: None runs to the end.
+PlannerRun = namedtuple("PlannerRun", "case start k budget max_states rounds")
+# NaN-only queues: a movable of the start is off its movement graph, so every key is NaN and every pop is newest-first out of
+# one bucket (733 states from listed 28 of (8, 16, 2)).  All starts overlap.  Six rounds unless the search ends sooner: from
+# SEARCH_STARTS[(3, 12, 9)][2] it is exhausted in round 5, from the DEEP_GOAL_STARTS it is solved.
+PLANNER_NAN_ROUNDS = 6
+PLANNER_NAN = [PlannerRun(case, start, k, None, None, PLANNER_NAN_ROUNDS) for case, start, k in (
+    (CASES[0], SEARCH_STARTS[CASES[0]][3], 4), (CASES[0], SEARCH_STARTS[CASES[0]][1], 64), (CASES[0], SEARCH_STARTS[CASES[0]][2], 64),
+    (CASES[0], DEEP_GOAL_STARTS[CASES[0]][0], 1),
+    (CASES[1], 18, 4), (CASES[1], 19, 64), (CASES[1], DEEP_GOAL_STARTS[CASES[1]][0], 4),
+    (CASES[2], 14, 4), (CASES[2], 18, 1), (CASES[2], 28, 64), (CASES[2], DEEP_GOAL_STARTS[CASES[2]][1], 1))]
+# finite and +inf keys in one queue: the initial state and three near states of (8, 16, 2); listed 3, 4 and 9 overlap
+PLANNER_MIXED_LISTED = [0, 3, 4, 9]
+PLANNER_MIXED = [PlannerRun(CASES[2], s, k, None, None, 5) for s in PLANNER_MIXED_LISTED for k in (4, 64)]
+# finite, +inf and NaN keys in one queue: 32 RGD frames per state overrun on a few states of (8, 16, 2).  The round counts are
+# the first at which a NaN entry is popped at K = 4, i.e. after the finite and the +inf buckets have drained (8 rounds pop
+# finite keys only; the first +inf entry pops in round 25 from the initial state, in round 34 from listed 9).
+PLANNER_BUDGET = 32
+PLANNER_BUDGET_RUNS = [PlannerRun(CASES[2], 0, 4, PLANNER_BUDGET, None, 64), PlannerRun(CASES[2], 9, 4, PLANNER_BUDGET, None, 87)]
+# searches of (8, 16, 2) that end at a goal row whose successor lies outside the grid: in round 3 (K = 64) or 6 (K = 1) from
+# GOAL_OUTSIDE_STARTS, in round 1 from the listed states
+PLANNER_GOAL_OUTSIDE = [PlannerRun(CASES[2], GOAL_OUTSIDE_STARTS[0], 64, None, None, None),
+                        PlannerRun(CASES[2], GOAL_OUTSIDE_STARTS[1], 1, None, None, None),
+                        PlannerRun(CASES[2], GOAL_OUTSIDE_STARTS[1], 64, None, None, None),
+                        PlannerRun(CASES[2], GOAL_OUTSIDE_LISTED[0], 1, None, None, None),
+                        PlannerRun(CASES[2], GOAL_OUTSIDE_LISTED[1], 4, None, None, None)]
+# the 30 x 30 board with 8-padded rows from its initial state: three states, all keys +inf, exhausted after three rounds
+PLANNER_EXHAUSTED = [PlannerRun(CASES[1], None, k, None, None, None) for k in (4, 64)]
+# rounds that pop more than 256 states (pw_push_planner_pop_kernel strides K over 256 threads): `Simple Tool` pops 300 of 401
+# and of 623 open entries over 15 buckets in rounds 6 and 7 at K = 300, and the whole open list (401, 600) at K = 1000.  Seven
+# rounds keep a restatement under 15 s of CPU (`Walk Past` needs over 20 s for five rounds and is left out).
+PLANNER_WIDE = [PlannerRun("Simple Tool", None, 300, None, None, 7), PlannerRun("Simple Tool", None, 1000, None, None, 7)]
+# 18 movables (32-padded rows, RGD with N > 16): the initial state and listed 3 (which overlaps) of (18, 30, 6)
+PLANNER_18 = [PlannerRun(CASES[4], s, 4, None, None, 5) for s in (0, 3)]
+# 16-padded rows: the initial state and listed 10 (which overlaps) of (12, 30, 4), regions of about 740 positions
+PLANNER_16_ROUNDS = 2  # 143 and 137 states in 18 s and 15 s of CPU; a third round restates about 110 more such regions per start
+PLANNER_16 = [PlannerRun(CASES[3], s, 4, None, None, PLANNER_16_ROUNDS) for s in (0, 10)]
+# `limit` from an overlapping start: listed 9 of (8, 16, 2) at K = 64 holds 54 states after three rounds and the fourth pops
+# 165 push rows, so a store of 150 (rounds 1 .. 3 need at most 106) refuses round 4
+PLANNER_LIMIT = PlannerRun(CASES[2], 9, 64, None, 150, None)
+PLANNER_RUNS = (PLANNER_NAN + PLANNER_MIXED + PLANNER_BUDGET_RUNS + PLANNER_GOAL_OUTSIDE + PLANNER_EXHAUSTED + PLANNER_WIDE +
+                PLANNER_18 + PLANNER_16 + [PLANNER_LIMIT])
 
 Listed = namedtuple("Listed", "kind state")
 _TEXT, _PUZZLE, _STATES, _STORES, _REGIONS = {}, {}, {}, {}, {}
@@ -163,6 +211,15 @@ def search_starts(case):
 def goal_starts(case):
     """The starts of the searches that stop at a goal: the goal_near states of the list, then DEEP_GOAL_STARTS."""
     return [s.state for s in states(case) if s.kind == "goal_near"] + DEEP_GOAL_STARTS[case]
+
+
+def planner_start(run):
+    """The start state of a ``PlannerRun``; None for the initial state of a Level-1 puzzle."""
+    if isinstance(run.case, str):
+        return None
+    if run.start is None:
+        return puzzle(run.case).initial_state
+    return states(run.case)[run.start].state if isinstance(run.start, int) else run.start
 
 
 def _cells(cp, state, k):
