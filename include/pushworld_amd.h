@@ -1464,6 +1464,74 @@ int  pw_push_planner_read_links(PwPushPlanner* p, int64_t first, int64_t count, 
 /* The plan to the goal state, as pw_push_search_plan (host buffer; returns the length, nothing written if > cap). */
 int  pw_push_planner_plan(PwPushPlanner* p, uint8_t* actions, int32_t cap, int32_t* pushes, void* stream);
 
+/* Exact cost-to-go tables OVER PUSHES (pw_push_search_solve's definitions: canonical states, push rows in (y, x, action) order,
+ * succ / cost / best / flags) of MANY small puzzles in ONE launch (csrc/pw_push_solution_batch.inc), in the form of
+ * pw_solve_batch: persistent workgroups take items off a device counter and do the search over canonical states, the rows, the
+ * sweeps (a barrier each) and the row bits of an item inside the kernel.  The walk regions are flooded on the packed state word
+ * with the step pw_solve_batch_run takes, the agent's byte replaced, so the definitions are those of pw_walk_regions / pw_walk_pushes:
+ * (q, a) is a walk move when stepping the state with the agent at q moves the agent and nothing else, a push move when it moves
+ * the agent and at least one other movable; a position at which the agent's bounding box leaves the grid is not in the region;
+ * canon is the region's smallest position in (y, x) order.  A node's key is the packed word (movable j at bits 8 j, x in the low
+ * nibble, y in the high one) with the agent at canon and zeros beyond the puzzle's N.
+ * Limits: 16 x 16 cells with the border, at most 8 movables, overlap tables present; anything else gets status 3.
+ *
+ * pw_push_solve_batch_create: states_cap, rows_cap >= 0: the pools for the tables of all items together (0 / 0: summaries only).
+ *   A stored item takes its states + 1 entries of the state pool and its rows of the row pool.
+ * pw_push_solve_batch_run: `puzzles` device int32 [n] set indices or NULL = 0 .. n - 1; `starts` device int8 [n][npad][2] (npad
+ *   4 / 8 / 16 / 32, at least the set's movables; only the first N movables of a row are read) or NULL = each puzzle's initial
+ *   state; a start outside its grid gives status 3.  Asynchronous on `stream` except when the engine's slabs or the handle's
+ *   per-item arrays have to grow.
+ * Per item, in device arrays owned by the handle (pw_push_solve_batch_results; valid until the next run or the destroy):
+ *   status     uint8      0 built and stored   2 more than max_states_each states (or more than 32 x max_states_each rows)
+ *                         3 not searched   4 built, but a pool was full: the summary is valid, nothing is stored
+ *                         5 a finite cost reached 65 535   6 a successor was missing from the exhausted closed set (internal)
+ *   summary    int32 [6]  states, rows, goal states, dead ends, largest finite cost (-1: none), cost of the start (-1: a dead
+ *                         end); valid for status 0 and 4 (else: states and rows found so far, then 0 0 -1 -1)
+ *   state_off / row_off   int64: the item's first entry in the state pool / the row pool, -1 when it is not stored
+ * State 0 is the start, and the order of a state's rows, best, the costs and the bits are fixed.  State numbers inside a layer,
+ * hence succ, and the pool offsets depend on the schedule and may differ from run to run: everything is found by state.
+ * pw_push_solve_batch_totals (synchronises `stream`): [0] the state-pool entries and [1] the rows that store every built table
+ *   of the run (size a second handle with them), [2] lookup slots in use, [3] missing successors (0).
+ * pw_push_solve_batch_read_states: states first .. first + count - 1 of a stored item into device buffers (any may be NULL):
+ *   key uint64, row_off int64 [count + 1] (first row of each state, relative to the item's first row), cost int32 (-1: a dead
+ *   end), best int32 (the lowest row of the least value, relative to the state's first; -1 at goal states and dead ends).
+ * pw_push_solve_batch_read_rows: rows first .. first + count - 1 of a stored item: succ int32 (state within the item, -1: the
+ *   successor lies outside the grid), from int8 [2], action uint8, flags uint8 (bit 0 goal row, 1 optimal, 2 safe).
+ *   The first read after a run fetches the item offsets (synchronises `stream` once); asynchronous afterwards.
+ * pw_push_solve_batch_query: live states of a MIXED batch, ONE launch, no allocation, no synchronisation (capturable): per item
+ *   the lookup of its puzzle's item, the range check and packing of the first N movables, the flood of the live region (a
+ *   layered breadth-first search that keeps a 2-bit parent action per cell when walk or action is asked for), the probe of the
+ *   canonical key confirmed against the stored key, and the way back from push_from along the parents.  Outputs and conventions
+ *   are exactly pw_push_search_table_query's (index, cost -1 dead end / -2 not in the table, push_from, push_action 0xFF, walk,
+ *   action; any may be NULL).  Masked items and items whose puzzle has no STORED table in this handle are LEFT UNTOUCHED.
+ *   A puzzle listed twice is answered from its higher item.
+ * Every argument check returns PW_EINVAL before any launch and names the function (null handle, n < 1, null puzzle_id / pos,
+ * npad not 4 / 8 / 16 / 32 or below the set's movables, negative caps, no run yet).
+ * Memory: 24 bytes per entry of the state pool (8 key + 8 row_off + 4 cost + 4 best), 8 bytes per row (4 succ + 2 from +
+ * 1 action + 1 flags), 4 bytes per lookup slot -- a power of two >= 2 x states (at least 16) slots per stored item, reserved as
+ * 4 slots per state + 16 per item; 50 bytes per item; 4 bytes per puzzle of the set.  The engine's slabs (shared with
+ * pw_search_batch, PW_OPT_SEARCH_BATCH_GROUPS_PER_CU applies): per persistent workgroup 400 bytes per state of max_states_each
+ * (16 per state + 32 rows of 12 bytes) + 12 bytes per slot of the 2^16 / 2^20 / ... closed-set levels. */
+typedef struct PwPushSolveBatch PwPushSolveBatch;
+int pw_push_solve_batch_create(PwEngine* e, int64_t states_cap, int64_t rows_cap, PwPushSolveBatch** out);
+void pw_push_solve_batch_destroy(PwPushSolveBatch* b);
+int pw_push_solve_batch_run(PwPushSolveBatch* b, const int32_t* puzzles, const int8_t* starts, int32_t npad, int32_t n,
+                            int64_t max_states_each, void* stream);
+/* device pointers (any may be NULL); returns the number of items of the last run */
+int pw_push_solve_batch_results(PwPushSolveBatch* b, const uint8_t** status, const int32_t** summary, const int64_t** state_off,
+                                const int64_t** row_off);
+/* the same arrays copied into the caller's device buffers [n], [n][6], [n], [n] (any may be NULL), asynchronous on `stream` */
+int pw_push_solve_batch_copy_results(PwPushSolveBatch* b, uint8_t* status, int32_t* summary, int64_t* state_off, int64_t* row_off,
+                                     void* stream);
+int pw_push_solve_batch_totals(PwPushSolveBatch* b, int64_t totals[4], void* stream);
+int pw_push_solve_batch_read_states(PwPushSolveBatch* b, int32_t item, int64_t first, int64_t count, uint64_t* key,
+                                    int64_t* row_off, int32_t* cost, int32_t* best, void* stream);
+int pw_push_solve_batch_read_rows(PwPushSolveBatch* b, int32_t item, int64_t first, int64_t count, int32_t* succ, int8_t* from,
+                                  uint8_t* action, uint8_t* flags, void* stream);
+int pw_push_solve_batch_query(PwPushSolveBatch* b, const int32_t* puzzle_id, const int8_t* pos, int32_t npad, const uint8_t* mask,
+                              int32_t n, int32_t* index, int32_t* cost, int8_t* push_from, uint8_t* push_action, int32_t* walk,
+                              int8_t* action, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -272,6 +272,18 @@ SIGNATURES = {
     "pw_push_search_table_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                           c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_solve_batch_create": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_void_p)]),
+    "pw_push_solve_batch_destroy": (None, [c_void_p]),
+    "pw_push_solve_batch_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
+    "pw_push_solve_batch_results": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
+    "pw_push_solve_batch_copy_results": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_solve_batch_totals": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
+    "pw_push_solve_batch_read_states": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p]),
+    "pw_push_solve_batch_read_rows": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "pw_push_solve_batch_query": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_planner_create": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int64, POINTER(c_void_p)]),
     "pw_push_planner_destroy": (None, [c_void_p]),
     "pw_push_planner_begin": (c_int, [c_void_p, c_void_p, c_void_p]),

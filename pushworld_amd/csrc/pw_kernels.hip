@@ -453,5 +453,6 @@ struct PageRec {
 #include "pw_push_search.inc"
 #include "pw_push_table.inc"
 #include "pw_push_table_sample.inc"
+#include "pw_push_solution_batch.inc"
 #include "pw_push_planner.inc"
 #include "pw_generate.inc"

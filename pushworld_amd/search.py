@@ -2285,6 +2285,224 @@ class PushSolutionTable:
     __del__ = close
 
 
+# ---- cost-to-go tables over pushes of many small puzzles in one launch (pw_push_solve_batch_*) -------------------
+def pack_push_key(canon, state) -> int:
+    """The key of a canonical state as ``PushSolutionTableBatch.keys`` holds it: movable j at bits 8 j (x in the low nibble, y in
+    the high one), the agent at ``canon``; ``state`` lists the puzzle's movables only, so nothing lies beyond them."""
+    key = 0
+    for j, (x, y) in enumerate([tuple(canon)] + [tuple(xy) for xy in list(state)[1:]]):
+        if j >= 8 or not (0 <= int(x) < 16 and 0 <= int(y) < 16):
+            raise ValueError("a key holds at most 8 movables with coordinates in 0 .. 15")
+        key |= (int(x) | (int(y) << 4)) << (8 * j)
+    return key
+
+
+class PushSolutionTableBatch:
+    """``PushSolutionTable``'s states and rows for MANY small puzzles of one set, built by ONE launch (``pw_push_solve_batch_run``:
+    persistent workgroups, the search over canonical states, the rows and the sweeps of an item inside the kernel) and queried
+    for a mixed batch by one launch.  The kernel's limits are ``SolutionTableBatch``'s: 16 x 16 cells with the border, 8
+    movables; bigger puzzles (status 3) and bigger spaces (status 2) are ``PushSolutionTable``'s.
+
+    Args:
+        source: a ``VecPushWorld`` or an ``_capi.Engine``: the tables are of its puzzle set, in its object order.
+        puzzles: set indices (item i is puzzle ``puzzles[i]``); None: every puzzle of the set.
+        starts: one entry per item, a state (a sequence of (x, y), the agent first) or None for the puzzle's initial state; None:
+            every item starts from its initial state.  A start outside its grid gives status 3.
+        max_states_each: cap on the canonical states per item (an item also holds at most 32 rows per state of the cap).
+        states, rows: entries of the two pools that hold the tables of all items together.  Both None: one summary-only pass
+            sizes them, a second pass stores (nothing is left out); 0 / 0: summaries only.
+
+    Device tensors, one entry per item: ``status`` uint8 (0 stored, 2 beyond the cap, 3 not searched, 4 built but a pool was
+    full -- summary only, 5 a cost beyond 65 534, 6 internal error), ``summary`` int32 [n, 6] and its columns ``num_states``,
+    ``num_rows``, ``num_goals``, ``dead_ends``, ``max_cost`` (-1: no finite cost), ``start_cost`` (-1: the start is a dead end)
+    -- valid for status 0 and 4 --, ``state_offset`` / ``row_offset`` int64 (-1: not stored).  ``states_needed`` /
+    ``rows_needed``: the pools that store every built table.
+
+    State 0 is the start; the order of a state's rows ((y, x, action) of the push), ``best``, the costs and the row bits are
+    fixed.  State numbers inside a layer (hence ``succ``) and the pool offsets depend on the schedule of the launch: everything
+    is found by state (``keys(i)`` / ``states(i)`` / ``query``), never by a number across runs.
+    Device memory: 24 bytes per entry of the state pool, 8 per row, see ``pw_push_solve_batch_create``."""
+
+    def __init__(self, source, puzzles: Optional[Sequence[int]] = None, starts=None, max_states_each: int = 1 << 16,
+                 states: Optional[int] = None, rows: Optional[int] = None):
+        engine = source if isinstance(source, _capi.Engine) else getattr(source, "engine", None)
+        if not isinstance(engine, _capi.Engine):
+            raise ValueError("source must be a VecPushWorld or an _capi.Engine")
+        self.engine, self.device, self.npad = engine, engine.device, int(engine.np)
+        count = len(engine.pset)
+        self.puzzles = list(range(count)) if puzzles is None else [int(p) for p in puzzles]
+        if not self.puzzles:
+            raise ValueError("puzzles must not be empty")
+        if min(self.puzzles) < 0 or max(self.puzzles) >= count:
+            raise ValueError(f"puzzles must be indices into the set (0 .. {count - 1})")
+        if (states is None) != (rows is None):
+            raise ValueError("states and rows must both be given or both be None")
+        if states is not None and (int(states) < 0 or int(rows) < 0):
+            raise ValueError("states and rows must be >= 0 (or None)")
+        if int(max_states_each) < 1:
+            raise ValueError("max_states_each must be >= 1")
+        self.max_states_each = int(max_states_each)
+        self.handle = None
+        self._ids = None if puzzles is None else torch.as_tensor(np.asarray(self.puzzles, dtype=np.int32)).to(self.device)
+        self._starts = None
+        if starts is not None:
+            starts = list(starts)
+            if len(starts) != len(self.puzzles):
+                raise ValueError("starts must hold one entry (a state or None) per item")
+            headers = np.frombuffer(engine.pset.headers(), dtype=np.uint8).reshape(count, 320)
+            host = np.zeros((len(starts), self.npad, 2), dtype=np.int8)
+            for i, (pid, start) in enumerate(zip(self.puzzles, starts)):
+                n_mov = int(headers[pid, 6])
+                if start is None:
+                    init = headers[pid, 256:320].view(np.int8).reshape(32, 2)
+                    host[i, :min(n_mov, self.npad)] = init[:min(n_mov, self.npad)]
+                    continue
+                xy = np.asarray(start, dtype=np.int64)
+                if xy.shape != (n_mov, 2):
+                    raise ValueError(f"starts[{i}] must list the {n_mov} movables of puzzle {pid} as (x, y)")
+                if xy.min() < -128 or xy.max() > 127:
+                    raise ValueError(f"starts[{i}] holds a coordinate outside -128 .. 127")
+                host[i, :n_mov] = xy
+            self._starts = torch.as_tensor(host).to(self.device)
+        if states is None:
+            self._run(0, 0)
+            states, rows = self.states_needed, self.rows_needed
+            self.close()
+        self._run(int(states), int(rows))
+
+    def _stream(self):
+        return self.engine._stream()
+
+    def _run(self, states: int, rows: int) -> None:
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib.pw_push_solve_batch_create(self.engine.handle, int(states), int(rows), ctypes.byref(h)))
+        self.handle = h
+        n = len(self.puzzles)
+        try:
+            _capi.check(_capi.lib.pw_push_solve_batch_run(h, _capi._ptr(self._ids), _capi._ptr(self._starts), self.npad, n,
+                                                          self.max_states_each, self._stream()))
+            self.status = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            self.summary = torch.empty((n, 6), dtype=torch.int32, device=self.device)
+            self.state_offset = torch.empty((n,), dtype=torch.int64, device=self.device)
+            self.row_offset = torch.empty((n,), dtype=torch.int64, device=self.device)
+            _capi.check(_capi.lib.pw_push_solve_batch_copy_results(h, _capi._ptr(self.status), _capi._ptr(self.summary),
+                                                                   _capi._ptr(self.state_offset), _capi._ptr(self.row_offset),
+                                                                   self._stream()))
+            totals = (ctypes.c_int64 * 4)()
+            _capi.check(_capi.lib.pw_push_solve_batch_totals(h, totals, self._stream()))
+        except Exception:
+            self.close()
+            raise
+        self.pool_states, self.pool_rows = int(states), int(rows)
+        self.states_needed, self.rows_needed, self.slots_used, self.missing = (int(t) for t in totals)
+        self.num_states, self.num_rows, self.num_goals, self.dead_ends, self.max_cost, self.start_cost = self.summary.unbind(1)
+        self._counts, self._covered = None, None
+
+    def __len__(self) -> int:
+        return len(self.puzzles)
+
+    def _item(self, item: int) -> Tuple[int, int, int]:
+        """(item, its states, its rows); ``ValueError`` for an item without a stored table."""
+        if self.handle is None:
+            raise ValueError("the batch is closed")
+        if not 0 <= int(item) < len(self.puzzles):
+            raise ValueError("item out of bounds")
+        if self._counts is None:
+            self._counts = (self.status.cpu().numpy(), self.summary[:, :2].cpu().numpy())
+        if self._counts[0][int(item)] != TABLE_BUILT:
+            raise ValueError(f"item {int(item)} has no stored table (status {int(self._counts[0][int(item)])})")
+        return int(item), int(self._counts[1][int(item), 0]), int(self._counts[1][int(item), 1])
+
+    def _read_states(self, which: int, item: int) -> torch.Tensor:
+        item, count, _ = self._item(item)
+        shape, dtype = (((count,), torch.int64), ((count + 1,), torch.int64), ((count,), torch.int32),
+                        ((count,), torch.int32))[which]
+        out = torch.empty(shape, dtype=dtype, device=self.device)
+        ptrs = [None, None, None, None]
+        ptrs[which] = _capi._ptr(out)
+        _capi.check(_capi.lib.pw_push_solve_batch_read_states(self.handle, item, 0, count, *ptrs, self._stream()))
+        return out
+
+    def keys(self, item: int) -> torch.Tensor:
+        """int64 [count] on the device: the key of every canonical state (movable j at bits 8 j: x | y << 4, the agent at the
+        canon of its walk region; ``pack_push_key``)."""
+        return self._read_states(0, item)
+
+    def states(self, item: int) -> np.ndarray:
+        """int array [count, N, 2] of (x, y) positions, state by state, the agent at ``canon``."""
+        keys = self.keys(item).cpu().numpy().astype(np.uint64)
+        n_mov = self.engine.pset.headers()[320 * self.puzzles[int(item)] + 6]
+        shifts = (np.arange(n_mov, dtype=np.uint64) * np.uint64(8))[None, :]
+        byte = (keys[:, None] >> shifts) & np.uint64(0xFF)
+        return np.stack([byte & np.uint64(15), byte >> np.uint64(4)], axis=-1).astype(np.int64)
+
+    def offsets(self, item: int) -> torch.Tensor:
+        """int64 [count + 1] on the device: the first row of every state, relative to the item's first row."""
+        return self._read_states(1, item)
+
+    def costs(self, item: int) -> torch.Tensor:
+        """int32 [count] on the device: pushes to go, -1 = dead end."""
+        return self._read_states(2, item)
+
+    def best(self, item: int) -> torch.Tensor:
+        """int32 [count] on the device: the lowest optimal row of each state (relative to its first), -1 where there is none."""
+        return self._read_states(3, item)
+
+    def rows(self, item: int):
+        """(succ int32 [R], from int8 [R, 2], action uint8 [R], flags uint8 [R]) of the item's rows, on the device: the state
+        (within the item) a row leads to (-1: outside the grid), the push, and bit 0 goal row, bit 1 optimal, bit 2 safe."""
+        item, _, n = self._item(item)
+        succ = torch.empty((n,), dtype=torch.int32, device=self.device)
+        frm = torch.empty((n, 2), dtype=torch.int8, device=self.device)
+        action = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        flags = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        _capi.check(_capi.lib.pw_push_solve_batch_read_rows(self.handle, item, 0, n, _capi._ptr(succ), _capi._ptr(frm),
+                                                            _capi._ptr(action), _capi._ptr(flags), self._stream()))
+        return succ, frm, action, flags
+
+    def query(self, puzzle_id: torch.Tensor, pos: torch.Tensor, mask: Optional[torch.Tensor] = None, out=None,
+              actions: bool = True) -> PushQuery:
+        """``PushSolutionTable.query`` for a mixed batch: ONE launch on the current stream, no allocation besides fresh outputs,
+        no wait (it can be captured in a graph with ``out`` given).  ``puzzle_id`` int32 [n], ``pos`` int8 [n, NP, 2], ``mask``
+        uint8 / bool [n].  Returns a ``PushQuery``; ``index`` is the state within the puzzle's item.  Items whose puzzle has no
+        stored table here and masked items keep what ``out`` held.  ``actions=False`` leaves ``action`` and ``walk`` as they are."""
+        n = _state_inputs(puzzle_id, pos, mask, self.npad, self.device)
+        out = _push_query_outputs(out, n, self.device)
+        if self.handle is None:
+            raise ValueError("the batch is closed")
+        _capi.check(_capi.lib.pw_push_solve_batch_query(self.handle, _capi._ptr(puzzle_id), _capi._ptr(pos), self.npad,
+                                                        _capi._ptr(mask), n, _capi._ptr(out.index), _capi._ptr(out.cost),
+                                                        _capi._ptr(out.push_from), _capi._ptr(out.push_action),
+                                                        _capi._ptr(out.walk) if actions else None,
+                                                        _capi._ptr(out.action) if actions else None, self._stream()))
+        return out
+
+    def covers(self, puzzle_id: torch.Tensor) -> torch.Tensor:
+        """bool [n] on the device: the items of ``puzzle_id`` whose puzzle has a stored table here."""
+        if self._covered is None:
+            has = torch.zeros((len(self.engine.pset),), dtype=torch.bool, device=self.device)
+            ids = self._ids if self._ids is not None else torch.arange(len(self.puzzles), device=self.device)
+            has[ids[self.status == TABLE_BUILT].long()] = True
+            self._covered = has
+        pid = puzzle_id.long()
+        inside = (pid >= 0) & (pid < self._covered.shape[0])
+        return inside & self._covered[pid.clamp(0, self._covered.shape[0] - 1)]
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h is not None and _capi.lib is not None:
+            _capi.lib.pw_push_solve_batch_destroy(h)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+
 # ---- pushes unrolled into primitive actions (pw_push_unroll_count / _write / _plans, DESIGN.md K21) ----------------------------
 PushUnroll = namedtuple("PushUnroll", "length offset actions num_actions")
 PushUnroll.__doc__ = """What ``unroll_pushes`` returns: device tensors ``length`` int32 [n] (the primitive actions of item i's push,

@@ -543,14 +543,28 @@ class VecPushWorld:
             raise ValueError(f"puzzle_index must be an index into the set (0 .. {self.num_puzzles - 1})")
         return PushSolutionTable(SetPuzzle(self.pset, int(puzzle_index), engine=self.engine), max_states=max_states)
 
+    def push_tables(self, puzzles=None, **kw):
+        """A ``search.PushSolutionTableBatch``: the cost-to-go tables in pushes of the small puzzles of this batch's set
+        (``puzzles``: set indices, None = all), built in one launch and queried in one (``push_cost_to_go``).  ``kw``: ``starts``,
+        ``max_states_each``, ``states``, ``rows``."""
+        from .search import PushSolutionTableBatch
+
+        return PushSolutionTableBatch(self, puzzles, **kw)
+
     def push_cost_to_go(self, tables, mask: Optional[torch.Tensor] = None):
         """A ``search.PushQuery`` (index, cost, action, push_from, push_action, walk) on the device for every environment's
-        current state, from a list of ``push_table``s (one ``PushSolutionTable.query`` each on the current stream): the cost
-        is in pushes, -1 at a dead end; environments whose puzzle has no table in the list keep -1 / -2 / -1 / (0, 0) /
-        0xFF / -1."""
+        current state, from a list of ``push_table``s (one ``PushSolutionTable.query`` each on the current stream) and / or
+        ``push_tables`` batches (one launch for all their puzzles): the cost is in pushes, -1 at a dead end; environments whose
+        puzzle has no table in the list keep -1 / -2 / -1 / (0, 0) / 0xFF / -1.  ``q = vec.push_cost_to_go([batch]);
+        vec.step_push(q.push_from, q.push_action)`` is an expert in pushes over the whole mix."""
+        from .search import PushSolutionTableBatch
+
         tables = list(tables)
         for table in tables:
-            if table.search._engine is not self.engine:
+            if isinstance(table, PushSolutionTableBatch):
+                if table.engine is not self.engine:
+                    raise ValueError("the tables must be made on this environment (VecPushWorld.push_tables)")
+            elif table.search._engine is not self.engine:
                 raise ValueError("the tables must be made on this environment (VecPushWorld.push_table)")
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8)
@@ -670,8 +684,13 @@ class VecPushWorld:
         return out
 
     def _own_push_tables(self, tables) -> list:
+        from .search import PushSolutionTableBatch
+
         tables = list(tables)
         for table in tables:
+            if isinstance(table, PushSolutionTableBatch):
+                raise ValueError("PushSolutionTableBatch is not supported here yet (sampling, plans and demonstrations need a "
+                                 "cost index on the batch): pass push_table()s; push_cost_to_go / push_expert_actions take batches")
             if table.search._engine is not self.engine:
                 raise ValueError("the tables must be made on this environment (VecPushWorld.push_table)")
         return tables
