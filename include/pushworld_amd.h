@@ -1169,6 +1169,56 @@ int pw_push_mask(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, int32
                  uint8_t* push_mask /* [n][map_h][map_w] */, int32_t* num_pushes /* [n] or NULL */,
                  int32_t map_h, int32_t map_w, void* stream);
 
+/* Stepping by pushes with the mask kept (K23): what a learner in pushes calls once per step.  pw_step_push_mask steps a batch as
+ * pw_step_push does and leaves, per environment, the push mask and the walk map of the state that is left -- in one launch, and
+ * with one flood per environment where pw_step_push followed by pw_push_mask floods twice.
+ * The six buffers push_mask .. view_id are the VIEW of an environment.  The caller owns them; the library keeps no state:
+ *   push_mask   uint8  [batch][map_h][map_w]   as pw_push_mask writes it
+ *   num_pushes  int32  [batch]                 as pw_push_mask writes it
+ *   walk_map    uint16 [batch][map_h][map_w]   as pw_walk_regions writes it
+ *   region_size int32  [batch]                 as pw_walk_regions writes it
+ *   view_pos    int8   [batch][npad][2]        the first N (x, y) pairs of the state the view describes, zeros beyond
+ *   view_id     int32  [batch]                 the puzzle id of that state; -1: no state
+ * The view of environment e is CURRENT when view_id[e] == puzzle_id[e], an index into the set, and the first N pairs of
+ * view_pos[e] equal those of pos[e], N the puzzle's number of movables; nothing beyond N is compared.  Filling view_id with -1
+ * invalidates every view; a buffer fresh from the allocator must be invalidated that way.
+ * Per environment:
+ *   1. Step phase.  pos, steps, reward, dgoals, terminated, truncated, moves and status are bit for bit what pw_step_push writes
+ *      for the same inputs and flags (the reset under PW_STEP_AUTORESET, every refusal, the cuts, the sequential float64 reward
+ *      sum), and pw_counters advances as it does there.  reward, dgoals, moves and status may be NULL.
+ *   2. View phase.  The view of e then describes the state that was left: push_mask[e] / num_pushes[e] equal what pw_push_mask,
+ *      walk_map[e] / region_size[e] what pw_walk_regions writes for it; every entry is written.  A skipped item (an id outside
+ *      the set, a movable outside its grid) gets zeros in the mask, 0xFFFF in the map, num_pushes 0, region_size -1, view_id -1
+ *      and zeros in view_pos.  Otherwise view_pos[e] holds the first N pairs of the new pos[e] and zeros beyond, view_id[e] the id.
+ *   3. PW_PUSH_END_STUCK (flags, next to PW_STEP_AUTORESET; read by this function only) applies after the view phase to every
+ *      environment with num_pushes[e] == 0 and neither terminated nor truncated set: truncated[e] = 1, and episodes_ended of
+ *      pw_counters advances by one for it.  status, reward and moves stay as they are.  With PW_STEP_AUTORESET the next call
+ *      resets it.  Without the flag nothing of the kind happens.
+ * How the view is used.  A current view replaces the step phase's flood: the choice (from, a) is valid exactly when a is in
+ * 0..3, walk_map[from] != 0xFFFF and bit a of push_mask[from] is set; dist(from) is the entry's low 12 bits; the agent's position
+ * at a max_steps cut is found by following the parent actions back from `from`; the push itself is one evaluation of the step
+ * function's push set.  A stale view is rebuilt first, by one flood of the state on entry, and the same path follows.  A choice
+ * refused on a current view costs no flood: state and view stay as they are.  So a call whose push_action is all PUSH_NONE
+ * (0xFF), without PW_STEP_AUTORESET, is the "observe" operation: it rebuilds the stale views and steps nothing.
+ * A view that is current by id and positions but whose contents were not written by this function is the caller's error; it can
+ * lead to a wrong verdict, never to a read out of bounds or an endless loop: every position on the way back along the parents is
+ * range-checked, the way is at most dist <= 4 095 links long, and a link that is 0xFFFF or whose dist does not drop by one makes
+ * the view stale (it is rebuilt and the step goes on).
+ * Asynchronous on `stream`: one launch behind the four-byte clear of an item counter, no fill of the view, no allocation once
+ * the engine's replay workspace exists (shared, as for pw_step_push), nothing read on the host -- the call can be captured into
+ * a graph.  pos and view_pos are read and written as 2-byte pairs.
+ * PW_EINVAL before any launch, pw_last_error naming the function and the argument: everything pw_step_push refuses; a null
+ * push_mask, num_pushes, walk_map, region_size, view_pos or view_id; map_h / map_w outside 1 .. PW_MAX_DIM or below the set's
+ * largest dimensions. */
+#define PW_PUSH_END_STUCK 0x100u
+int pw_step_push_mask(PwEngine* e, const int32_t* puzzle_id, const int8_t* push_from /* [B][2] */,
+                      const uint8_t* push_action /* [B] */, int8_t* pos, int32_t* steps, double* reward, int8_t* dgoals,
+                      uint8_t* terminated, uint8_t* truncated, int32_t* moves, int8_t* status,
+                      uint8_t* push_mask /* [B][map_h][map_w] */, int32_t* num_pushes /* [B] */,
+                      uint16_t* walk_map /* [B][map_h][map_w] */, int32_t* region_size /* [B] */,
+                      int8_t* view_pos /* [B][npad][2] */, int32_t* view_id /* [B] */,
+                      int32_t map_h, int32_t map_w, int32_t batch, uint32_t flags, void* stream);
+
 /* Pushes unrolled into primitive actions (K21): the bridge from the push level back to the move level.  Item i is a state s
  * (puzzle_id[i], pos[i]; pos NULL: the initial states, as pw_walk_regions) and a choice (from, a) = (push_from[i],
  * push_action[i]).  The choice is VALID by pw_step_push's rule, unchanged: a in 0..3, from in the walk region R(s), (from, a) a

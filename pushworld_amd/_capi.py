@@ -31,6 +31,7 @@ PLAN_MAX_ACTIONS = 65536  # PW_PLAN_MAX_ACTIONS of include/pushworld_amd.h: acti
 STEP_AUTORESET = 1
 # status of an environment after pw_step_push
 PUSH_REFUSED, PUSH_DONE, PUSH_CUT, PUSH_RESET = 0, 1, 2, 3
+PUSH_END_STUCK = 0x100  # PW_PUSH_END_STUCK: a flag of pw_step_push_mask, next to STEP_AUTORESET
 
 
 class PwPuzzleInfo(ctypes.Structure):
@@ -244,6 +245,7 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_int32, c_uint32, c_void_p]),
     "pw_push_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                              c_void_p]),
+    "pw_step_push_mask": (c_int, [c_void_p] * 18 + [c_int32, c_int32, c_int32, c_uint32, c_void_p]),
     "pw_push_unroll_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                      c_void_p, c_void_p]),
     "pw_push_unroll_write": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
@@ -1213,6 +1215,15 @@ class Engine:
     def push_mask(self, puzzle_id, pos, mask, push_mask, num_pushes=None):
         check(lib.pw_push_mask(self.handle, _ptr(puzzle_id), _ptr(pos), self.np, _ptr(mask), puzzle_id.shape[0],
                                _ptr(push_mask), _ptr(num_pushes), push_mask.shape[1], push_mask.shape[2], self._stream()))
+
+    # stepping by pushes with the mask and the walk map kept (pw_step_push_mask): the six view tensors are the caller's, no wait
+    def step_push_mask(self, puzzle_id, push_from, push_action, pos, steps, reward, dgoals, terminated, truncated, moves,
+                       status, push_mask, num_pushes, walk_map, region_size, view_pos, view_id, flags=0):
+        check(lib.pw_step_push_mask(self.handle, _ptr(puzzle_id), _ptr(push_from), _ptr(push_action), _ptr(pos), _ptr(steps),
+                                    _ptr(reward), _ptr(dgoals), _ptr(terminated), _ptr(truncated), _ptr(moves), _ptr(status),
+                                    _ptr(push_mask), _ptr(num_pushes), _ptr(walk_map), _ptr(region_size), _ptr(view_pos),
+                                    _ptr(view_id), push_mask.shape[1], push_mask.shape[2], pos.shape[0], int(flags),
+                                    self._stream()))
 
     # pushes unrolled into primitive actions (pw_push_unroll_count / _write / _plans): device tensors in and out, no wait
     def push_unroll_count(self, puzzle_id, pos, push_from, push_action, mask, length, offset):

@@ -449,6 +449,7 @@ struct PageRec {
 #include "pw_plan_replay.inc"
 #include "pw_walk.inc"
 #include "pw_push_step.inc"
+#include "pw_push_env.inc"
 #include "pw_push_unroll.inc"
 #include "pw_push_search.inc"
 #include "pw_push_table.inc"

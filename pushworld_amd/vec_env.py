@@ -11,6 +11,7 @@ convention: the call after a finished episode resets that environment and return
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional, Sequence, Union
 
 import numpy as np
@@ -18,6 +19,9 @@ import torch
 
 from . import _capi
 from .puzzle import DEFAULT_BORDER_WIDTH, DEFAULT_PIXELS_PER_CELL, PushWorldPuzzle, default_device_index
+
+# what VecPushWorld.step_push_mask returns
+PushStep = namedtuple("PushStep", "obs reward terminated truncated moves status mask num_pushes")
 
 
 class VecPushWorld:
@@ -463,6 +467,23 @@ class VecPushWorld:
         There is no policy for that here: watch ``status`` or ``push_mask()`` / ``num_pushes`` and ``reset(mask=...)``."""
         if not self._has_reset:
             raise RuntimeError("reset() must be called before step_push() can be called.")
+        push_from, push_action = self._push_choice(push_from, push_action, choice)
+        if getattr(self, "push_status", None) is None:
+            self.push_moves_taken = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
+            self.push_status = torch.zeros((self.num_envs,), dtype=torch.int8, device=self.device)
+        if self.resample and self.flags & _capi.STEP_AUTORESET:
+            # finished environments draw the puzzle their autoreset (inside this step) starts from
+            self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
+                                 self.sample_table)
+        self.engine.step_push(self.puzzle_id, push_from, push_action, self.pos, self.steps, self.reward, self.dgoals,
+                              self.terminated, self.truncated, self.push_moves_taken, self.push_status, self.flags)
+        self._obs_current = False
+        if self.obs is not None:
+            self._render()
+        return self.obs, self.reward, self.terminated, self.truncated, self.push_moves_taken, self.push_status
+
+    def _push_choice(self, push_from, push_action, choice):
+        """The checked ``(push_from, push_action)`` of ``step_push`` / ``step_push_mask``: given, or decoded from ``choice``."""
         if choice is not None:
             if push_from is not None or push_action is not None:
                 raise ValueError("pass either push_from with push_action, or choice")
@@ -480,6 +501,29 @@ class VecPushWorld:
         if not isinstance(push_action, torch.Tensor) or push_action.dtype != torch.uint8 or push_action.device != self.device \
                 or push_action.shape != self._act_shape or not push_action.is_contiguous():
             raise ValueError("push_action must be a contiguous uint8 tensor of shape [num_envs] on the engine's device")
+        return push_from, push_action
+
+    def step_push_mask(self, push_from: Optional[torch.Tensor] = None, push_action: Optional[torch.Tensor] = None,
+                       choice: Optional[torch.Tensor] = None, end_stuck: bool = False):
+        """``step_push`` and the push mask of the states it leaves, in one launch (``pw_step_push_mask``): what a learner in
+        pushes calls once per step.  The arguments, checks and per-environment results are those of ``step_push``; the mask
+        is that of ``push_mask()`` for the new states.  The environment keeps a *view* per environment -- mask, number of push
+        moves, walk map, region size, and the state they describe -- and the launch uses it: while the view is current, the
+        choice is looked up in it and only the state that is left is flooded, one flood per step instead of the two of
+        ``step_push`` + ``push_mask``.  A view made stale by anything else that moved the environment (``step``, ``reset``,
+        ``set_states``, a new puzzle id) is noticed on the device and rebuilt first.
+
+        ``end_stuck``: an environment that is left without any push move and without a flag gets ``truncated`` set (and
+        counts as an ended episode), so that ``autoreset`` restarts it on the next call.
+
+        Returns the named tuple ``PushStep(obs, reward, terminated, truncated, moves, status, mask, num_pushes)``: the six of
+        ``step_push``, ``mask`` uint8 [B, map_h, map_w] (bit ``a`` of ``[y, x]``: ``((x, y), a)`` is a push move) and
+        ``num_pushes`` int32 [B] -- views of persistent device buffers, no wait.  ``self.push_walk_map`` and
+        ``self.push_region_size`` hold the walk maps and region sizes of the same states (``walk_regions(maps=True)``)."""
+        if not self._has_reset:
+            raise RuntimeError("reset() must be called before step_push_mask() can be called.")
+        push_from, push_action = self._push_choice(push_from, push_action, choice)
+        self._push_view()
         if getattr(self, "push_status", None) is None:
             self.push_moves_taken = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
             self.push_status = torch.zeros((self.num_envs,), dtype=torch.int8, device=self.device)
@@ -487,12 +531,44 @@ class VecPushWorld:
             # finished environments draw the puzzle their autoreset (inside this step) starts from
             self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
                                  self.sample_table)
-        self.engine.step_push(self.puzzle_id, push_from, push_action, self.pos, self.steps, self.reward, self.dgoals,
-                              self.terminated, self.truncated, self.push_moves_taken, self.push_status, self.flags)
+        self.engine.step_push_mask(self.puzzle_id, push_from, push_action, self.pos, self.steps, self.reward, self.dgoals,
+                                   self.terminated, self.truncated, self.push_moves_taken, self.push_status,
+                                   self.push_view_mask, self.push_view_count, self.push_walk_map, self.push_region_size,
+                                   self._push_view_pos, self._push_view_id,
+                                   self.flags | (_capi.PUSH_END_STUCK if end_stuck else 0))
         self._obs_current = False
         if self.obs is not None:
             self._render()
-        return self.obs, self.reward, self.terminated, self.truncated, self.push_moves_taken, self.push_status
+        return PushStep(self.obs, self.reward, self.terminated, self.truncated, self.push_moves_taken, self.push_status,
+                        self.push_view_mask, self.push_view_count)
+
+    def observe_pushes(self):
+        """``(mask, num_pushes)`` of every environment's current state, as ``push_mask()`` gives them, from the views that
+        ``step_push_mask`` keeps: the all-``PUSH_NONE`` call without autoreset, which rebuilds the views that are stale and
+        steps nothing (no flood at all where every view is current).  ``reward`` and the flags are not touched."""
+        if not self._has_reset:
+            raise RuntimeError("reset() must be called before observe_pushes() can be called.")
+        self._push_view()
+        # (reward, dgoals, moves and status are not written: a refusal would overwrite the last step's)
+        self.engine.step_push_mask(self.puzzle_id, self._push_none_from, self._push_none_action, self.pos, self.steps, None,
+                                   None, self.terminated, self.truncated, None, None, self.push_view_mask,
+                                   self.push_view_count, self.push_walk_map, self.push_region_size, self._push_view_pos,
+                                   self._push_view_id, 0)
+        return self.push_view_mask, self.push_view_count
+
+    def _push_view(self) -> None:
+        """The view tensors of ``step_push_mask`` / ``observe_pushes``, allocated on first use with every view invalid."""
+        if getattr(self, "_push_view_id", None) is not None:
+            return
+        B, mh, mw, dev = self.num_envs, self.pset.max_height, self.pset.max_width, self.device
+        self.push_view_mask = torch.empty((B, mh, mw), dtype=torch.uint8, device=dev)
+        self.push_view_count = torch.empty((B,), dtype=torch.int32, device=dev)
+        self.push_walk_map = torch.empty((B, mh, mw), dtype=torch.uint16, device=dev)
+        self.push_region_size = torch.empty((B,), dtype=torch.int32, device=dev)
+        self._push_view_pos = torch.zeros_like(self.pos)
+        self._push_none_from = torch.zeros((B, 2), dtype=torch.int8, device=dev)
+        self._push_none_action = torch.full((B,), 0xFF, dtype=torch.uint8, device=dev)
+        self._push_view_id = torch.full((B,), -1, dtype=torch.int32, device=dev)
 
     def solution_table(self, puzzle_index: int, max_states: int = 1 << 22):
         """A ``search.SolutionTable`` -- the exact cost-to-go, optimal actions and dead ends of every reachable state -- of

@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _compat
+from . import _capi, _compat
 from .config import PUZZLE_EXTENSION
 from .puzzle import DEFAULT_BORDER_WIDTH, DEFAULT_PIXELS_PER_CELL, NUM_ACTIONS, PushWorldPuzzle
 from ._single_env import pool_frame
@@ -269,3 +269,199 @@ class PushWorldDmVectorEnv(_VectorCore):
         discount = torch.where(done & ~first, 0.0, 1.0).to(torch.float64)
         self._was_done = done & ~first
         return self._timestep(step_type, reward, discount, obs)
+
+
+# ---------------------------------------------------------------------------------------------------------- push mode
+def push_action_spaces(map_h: int, map_w: int, num_envs: int):
+    """``(single_action_space, action_space)`` of the push-mode facades: an action is the flat index into ``[4, map_h,
+    map_w]`` -- (direction, y, x) of the agent position the push starts from -- what ``VecPushWorld.step_push(choice=...)``
+    takes."""
+    n = 4 * int(map_h) * int(map_w)
+    return _compat.make_discrete(n), _BatchSpace(_compat.Discrete(n), num_envs)
+
+
+class _PushCore(_VectorCore):
+    """The core of the push-mode facades: every step is ONE ``VecPushWorld.step_push_mask(choice=..., end_stuck=True)``."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        v = self.vec
+        self.map_h, self.map_w = v.pset.max_height, v.pset.max_width
+        self.num_choices = 4 * self.map_h * self.map_w
+        self._bits = torch.tensor([1, 2, 4, 8], dtype=torch.uint8, device=v.device).view(1, 4, 1, 1)
+        self._refused = torch.zeros((), dtype=torch.int64, device=v.device)  # refused choices since the last check
+        self._step = None  # the PushStep of the pending / last step
+
+    def _actions(self, actions) -> torch.Tensor:
+        """int64 [B] on the device.  Host arrays are range-checked here; a device tensor is checked by the step itself (an
+        index outside the shape decodes to ``PUSH_NONE``: a refused choice)."""
+        if isinstance(actions, torch.Tensor):
+            if actions.shape != (self.num_envs,) or actions.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8,
+                                                                          torch.uint8):
+                raise ValueError("The provided action is not in the action space.")
+            return actions.to(device=self.vec.device, dtype=torch.int64)
+        arr = np.asarray(actions)
+        if arr.shape != (self.num_envs,) or not np.issubdtype(arr.dtype, np.integer) or (arr < 0).any() \
+                or (arr >= self.num_choices).any():
+            raise ValueError("The provided action is not in the action space.")
+        return torch.as_tensor(arr.astype(np.int64)).to(self.vec.device)
+
+    def _launch(self, actions) -> None:
+        if self._pending:
+            raise RuntimeError("step_async() was called twice without step_wait()")
+        choice = self._actions(actions)
+        v = self.vec
+        if not v._has_reset:
+            raise RuntimeError("reset() must be called before step() can be called.")
+        # an environment without a push move has no choice to make: its refusal is the stuck rule's business, not an error.
+        # (the views are current here: reset() and every step leave them so)
+        could = v.push_view_count > 0
+        self._step = v.step_push_mask(choice=choice, end_stuck=True)  # asynchronous on the current HIP stream
+        self._refused += ((self._step.status == _capi.PUSH_REFUSED) & could).sum()
+        self._pending = True
+
+    def _collect(self):
+        if not self._pending:
+            raise RuntimeError("step_wait() called without a pending step_async()")
+        self._pending = False
+        if self.to_numpy:  # the host path synchronises anyway: a refused choice raises at once
+            self.check_actions()
+        return self._step
+
+    def _observe(self):
+        """After ``vec.reset``: the views of the first states (``observe_pushes``)."""
+        self.vec.observe_pushes()
+        self._refused.zero_()
+
+    def _action_mask(self) -> torch.Tensor:
+        """bool [B, 4 * map_h * map_w]: entry ``(a * map_h + y) * map_w + x`` is set when ``((x, y), a)`` is a push move."""
+        return ((self.vec.push_view_mask.unsqueeze(1) & self._bits) != 0).view(self.num_envs, self.num_choices)
+
+    def check_actions(self) -> None:
+        """Device-tensor mode (``to_numpy=False``) never synchronises, so a choice that is no push move cannot raise inside
+        ``step``: the environment is left as it was (reward 0, ``status`` 0) and the refusal is counted on the device.  This
+        reads and clears the count (one stream synchronisation) and raises ``ValueError`` if any choice was refused since the
+        last check.  Choices of environments without any push move (``stuck``) and of environments that the step reset are
+        not counted: there was nothing valid to choose."""
+        n = int(self._refused.item())
+        self._refused.zero_()
+        if n:
+            raise ValueError(f"The provided action is not in the action space: no push move. ({n} since the last check)")
+
+
+class PushWorldPushVectorEnv(_PushCore):
+    """``PushWorldVectorEnv`` in the push-level action space: an action is a push move -- the agent walks
+    to a cell of its walk region along the shortest path and pushes from there -- given as the flat index into ``[4, map_h,
+    map_w]`` (direction, y, x), the shape of a policy head's logits and of ``info["action_mask"]``.  One ``step`` is one
+    launch (``pw_step_push_mask``) plus the render; its reward is the sum of the primitive rewards of the walk and the push.
+
+    Constructor arguments as ``PushWorldVectorEnv``.  Next-step autoreset: the ``step`` after a finished episode ignores the
+    choice, draws a new puzzle and returns its first observation with reward 0.  An environment that is left without any
+    push move and is not solved is ``stuck``: it is truncated at once, and reset by the following ``step``.
+
+    ``info``: ``action_mask`` bool [B, 4 * map_h * map_w]; ``push_mask`` uint8 [B, map_h, map_w] (the same, packed: bit a of
+    [y, x]); ``num_pushes`` int32 [B]; ``moves`` int32 [B] primitive steps executed; ``status`` int8 [B] (``PUSH_DONE`` /
+    ``PUSH_CUT`` / ``PUSH_REFUSED`` / ``PUSH_RESET``); ``stuck`` bool [B]; ``puzzle_id``; ``puzzle_state``.  A choice that is
+    no push move is a refused no-op (reward 0, ``status`` 0); see ``check_actions``.  With ``to_numpy=True`` it raises."""
+
+    metadata = {"render_modes": ["rgb_array"], "autoreset_mode": "next_step"}
+    render_mode = "rgb_array"
+
+    def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int] = None,
+                 border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
+                 standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
+                 device: Optional[int] = None, to_numpy: bool = False):
+        super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
+                         observation, seed, sample_table, device, to_numpy)
+        self.single_action_space, self.action_space = push_action_spaces(self.map_h, self.map_w, num_envs)
+        self.single_observation_space = _compat.make_box(0, self._obs_high, self._obs_shape, self._obs_dtype)
+        self.observation_space = _BatchSpace(_compat.Box(0, self._obs_high, self._obs_shape, self._obs_dtype),
+                                             num_envs)
+
+    def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
+        """All environments draw a puzzle and start an episode.  Returns ``(obs, info)``; ``moves`` and ``status`` are zeros."""
+        self._pending = False
+        obs = self.vec.reset(seed=seed)
+        self._observe()
+        zeros = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.vec.device)
+        return self._out(obs), self._info(zeros, zeros.to(torch.int8))
+
+    def _info(self, moves, status) -> dict:
+        v = self.vec
+        return {"action_mask": self._out(self._action_mask()), "push_mask": self._out(v.push_view_mask),
+                "num_pushes": self._out(v.push_view_count), "moves": self._out(moves), "status": self._out(status),
+                "stuck": self._out((v.push_view_count == 0) & (v.terminated == 0)),
+                "puzzle_id": self._out(v.puzzle_id), "puzzle_state": self._out(v.pos)}
+
+    def step_async(self, actions) -> None:
+        self._launch(actions)
+
+    def step_wait(self):
+        s = self._collect()
+        info = self._info(s.moves, s.status)
+        if self.to_numpy:
+            return (s.obs.cpu().numpy(), s.reward.cpu().numpy(), s.terminated.cpu().numpy().astype(bool),
+                    s.truncated.cpu().numpy().astype(bool), info)
+        return s.obs, s.reward, s.terminated, s.truncated, info
+
+    def step(self, actions):
+        """One macro step per environment -> ``(obs, reward f64[B], terminated, truncated, info)``."""
+        self.step_async(actions)
+        return self.step_wait()
+
+    render = PushWorldVectorEnv.render
+
+
+class PushWorldPushDmVectorEnv(_PushCore):
+    """Batched ``dm_env`` flavour of ``PushWorldPushVectorEnv``: ``TimeStep.observation`` is ``{"board": obs, "action_mask":
+    bool [B, 4 * map_h * map_w]}``; step types and discounts follow ``PushWorldDmVectorEnv``'s rules (FIRST after a
+    (auto)reset with reward 0 / discount 1, LAST with discount 0 when terminated or truncated -- the stuck rule included --
+    MID otherwise)."""
+
+    def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int] = None,
+                 border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
+                 standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
+                 device: Optional[int] = None, to_numpy: bool = False):
+        super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
+                         observation, seed, sample_table, device, to_numpy)
+        self._action_spec = _compat.make_discrete_array(self.num_choices, int, "action")
+        self._observation_spec = {
+            "board": _compat.make_bounded_array(self._obs_shape, self._obs_dtype, "board", 0, self._obs_high),
+            "action_mask": _compat.make_bounded_array((self.num_choices,), np.bool_, "action_mask", False, True),
+        }
+        self._was_done = None
+
+    def action_spec(self):
+        return self._action_spec
+
+    def observation_spec(self):
+        return self._observation_spec
+
+    def _timestep(self, step_type, reward, discount, obs):
+        observation = {"board": self._out(obs), "action_mask": self._out(self._action_mask())}
+        return _compat.TimeStep(self._out(step_type), self._out(reward), self._out(discount), observation)
+
+    def reset(self, seed: Optional[int] = None):
+        self._pending = False
+        obs = self.vec.reset(seed=seed)
+        self._observe()
+        dev = self.vec.device
+        self._was_done = torch.zeros((self.num_envs,), dtype=torch.bool, device=dev)
+        return self._timestep(torch.full((self.num_envs,), int(_compat.StepType.FIRST), dtype=torch.int32, device=dev),
+                              torch.zeros((self.num_envs,), dtype=torch.float64, device=dev),
+                              torch.ones((self.num_envs,), dtype=torch.float64, device=dev), obs)
+
+    def step(self, actions):
+        if self._was_done is None:
+            raise RuntimeError("reset() must be called before step() can be called.")
+        self._launch(actions)
+        s = self._collect()
+        done = (s.terminated != 0) | (s.truncated != 0)
+        first = self._was_done  # this call reset those environments
+        step_type = torch.where(first, int(_compat.StepType.FIRST),
+                                torch.where(done, int(_compat.StepType.LAST), int(_compat.StepType.MID))).to(torch.int32)
+        discount = torch.where(done & ~first, 0.0, 1.0).to(torch.float64)
+        # (a reset clears the flags, but the stuck rule may set truncated again in the same call -- an initial state without a
+        # push move: the next call resets that environment once more, so it is FIRST again)
+        self._was_done = done
+        return self._timestep(step_type, s.reward, discount, s.obs)
