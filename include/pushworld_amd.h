@@ -1582,6 +1582,73 @@ int pw_push_solve_batch_query(PwPushSolveBatch* b, const int32_t* puzzle_id, con
                               int32_t n, int32_t* index, int32_t* cost, int8_t* push_from, uint8_t* push_action, int32_t* walk,
                               int8_t* action, void* stream);
 
+/* Best-first search over pushes (pw_push_planner_*, K17) of MANY puzzles or live states in ONE launch
+ * (csrc/pw_push_plan_batch.inc, K24), in the form of pw_plan_batch: persistent workgroups of one wavefront take items off a
+ * device counter and run the whole search of an item -- pop, the floods, the push rows, the closed set, the goal test, RGD, push
+ * -- inside the kernel.  Item i's info[0..9], store (the states as reached and their canon) and links (parent, from, action,
+ * goal) equal pw_push_planner_create(e, puzzle, max_states, batch, rgd_budget) + begin(start) + run(max_rounds), round by round
+ * (the seven steps listed there), as long as no finite key reaches cost_range.  The walk regions are flooded on the packed state
+ * word as pw_push_solve_batch does, so the limits are its limits: 16 x 16 cells with the border, at most 8 movables, overlap
+ * tables present, the start inside its grid.  An item beyond them is PW_PLAN_SKIPPED: info[0] = 6, info[1..10] = 0, plan_len -1,
+ * first_from (0, 0), first_action PW_PUSH_NONE; nothing of it is read past the test that skips it.
+ *
+ * pw_push_plan_batch_create: `puzzles` host int32 [n] set indices or NULL = 0 .. n - 1; batch = K, 1 .. 64; max_states per item,
+ *   1 .. 2^28; rgd_budget 0 = the default; cost_range 1 .. 65536 finite keys with a bucket (0 = 65536): a finite key at or
+ *   above it ends that item with PW_PLAN_RANGE.  Builds the RGD tables of every listed puzzle within the limits and the
+ *   workgroups' slabs: at most two per CU, one per item, within a quarter of the free memory.  Per state of max_states a slab
+ *   holds 21 bytes (key 8, agent byte 1, parent 4, from 2, action 1, goal 1, next 4) and 16 to 32 bytes of the closed set
+ *   (tag << 32 | index + 1, a power of two >= 2 max_states slots), plus 4 bytes per bucket.
+ * pw_push_plan_batch_run: item i is listed puzzle i from its initial state.  Asynchronous on `stream`: a one-thread kernel that
+ *   zeroes the item counter and takes n fresh closed-set tags from a counter ON THE DEVICE, then the search kernel; no allocation,
+ *   no wait, nothing read on the host.  Capturable, and a captured call may be replayed any number of times: every replay takes
+ *   its own tags, so it never meets the closed-set entries of the replay before, and it plans from whatever the inputs hold then.
+ *   max_rounds per item (<= 0: no limit); time_limit seconds per item on the device's constant clock (0 = none; an item past it
+ *   ends with PW_PLAN_TIMEOUT; checked between rounds); pw_push_plan_batch_cancel stops every eager launch made so far, queued
+ *   ones included, and every replay of a captured launch that has begun, within 32 rounds per item (status PW_PLAN_RUNNING with
+ *   the counts reached; items not started: 0 rounds, goal index -1).  A replay that begins after the cancel runs as usual: a
+ *   captured launch carries no sequence number, it compares the cancel generation it found when it began.
+ *   All outputs are device memory; any but info may be NULL:
+ *     info         int64 [n][PW_PUSH_PLAN_BATCH_INFO]: pw_push_planner_run's ten values, then the item's search time in ns
+ *     plan_len     int32 [n]: the number of pushes of the plan; -1 no plan; -2 the plan is longer than push_cap and nothing of
+ *                  it is written (only with plan arrays); 0 the start is a goal state
+ *     plan_from    int8 [n][push_cap][2], plan_action uint8 [n][push_cap]: the chain of parents written forwards
+ *     plan_pos     int8 [n][push_cap][npad][2]: the state as reached that push t is made from, zeros beyond N -- the rows that
+ *                  pw_push_unroll_count / _write take.  Entries at and past plan_len are left as they are.
+ * pw_push_plan_batch_run_states: item i is the state pos[i] (device int8 [n][npad][2], the engine's layout) of puzzle
+ *   puzzle_id[i] (device int32 [n]); mask device uint8 [n] or NULL, 0 = skip.  Items that are masked out, name a puzzle outside
+ *   the set or one the handle did not prepare, or hold a movable outside its grid are PW_PLAN_SKIPPED.  first_from int8 [n][2]
+ *   and first_action uint8 [n]: the first push of a plan with plan_len > 0, else (0, 0) and PW_PUSH_NONE; either way
+ *   pw_step_push takes them as they are.  The same two kernels, capturable and replayable once the workgroups exist: a call with more
+ *   items than workgroups (below two per CU) replaces the slabs first and waits for the device once, as pw_plan_batch_run_states
+ *   does -- make one eager call with the batch size before capturing.
+ * pw_push_plan_batch_read_states / _read_links: the store of `item` of the last launch into device buffers (any may be NULL):
+ *   pos int8 [count][npad][2] and canon int8 [count][2]; parent int32, from int8 [count][2], action uint8 (PW_PUSH_NONE for the
+ *   start), goal uint8.  A workgroup keeps the store of the LAST item it ran: every item of a launch with n <= the number of
+ *   workgroups can be read, of a larger launch those that no later item displaced; a displaced or skipped item is PW_EINVAL.
+ *   Synchronises `stream` once per call.
+ * PW_EINVAL before any launch, pw_last_error naming the function and the argument: a null engine, out, handle, puzzle_id, pos
+ * or info; n < 1; batch outside 1 .. 64; max_states outside 1 .. 2^28; a negative rgd_budget; cost_range outside 0 .. 65536; a
+ * negative time_limit; npad not 4 / 8 / 16 / 32 or below the prepared movables; push_cap < 0; plan arrays without plan_len; a
+ * puzzle index outside the set; a read before a run, of a range outside the store or of an item whose store is gone. */
+#define PW_PUSH_PLAN_BATCH_INFO 11
+#define PW_PUSH_NONE 0xFF
+typedef struct PwPushPlanBatch PwPushPlanBatch;
+int pw_push_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int64_t max_states, int32_t batch,
+                              int64_t rgd_budget, int32_t cost_range, PwPushPlanBatch** out);
+int pw_push_plan_batch_run(PwPushPlanBatch* b, int64_t max_rounds, double time_limit, int64_t* info, int32_t* plan_len,
+                           int8_t* plan_from, uint8_t* plan_action, int8_t* plan_pos, int32_t push_cap, int32_t npad,
+                           void* stream);
+int pw_push_plan_batch_run_states(PwPushPlanBatch* b, const int32_t* puzzle_id, const int8_t* pos, int32_t npad,
+                                  const uint8_t* mask, int32_t n, int64_t max_rounds, double time_limit, int64_t* info,
+                                  int32_t* plan_len, int8_t* plan_from, uint8_t* plan_action, int8_t* plan_pos, int32_t push_cap,
+                                  int8_t* first_from, uint8_t* first_action, void* stream);
+int pw_push_plan_batch_read_states(PwPushPlanBatch* b, int32_t item, int64_t first, int64_t count, int8_t* pos, int32_t npad,
+                                   int8_t* canon, void* stream);
+int pw_push_plan_batch_read_links(PwPushPlanBatch* b, int32_t item, int64_t first, int64_t count, int32_t* parent, int8_t* from,
+                                  uint8_t* action, uint8_t* goal, void* stream);
+int pw_push_plan_batch_cancel(PwPushPlanBatch* b);
+void pw_push_plan_batch_destroy(PwPushPlanBatch* b);
+
 #ifdef __cplusplus
 }
 #endif

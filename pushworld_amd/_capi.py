@@ -293,6 +293,17 @@ SIGNATURES = {
     "pw_push_planner_read_states": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "pw_push_planner_read_links": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_planner_plan": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pw_push_plan_batch_create": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int64, c_int32, POINTER(c_void_p)]),
+    "pw_push_plan_batch_run": (c_int, [c_void_p, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int32, c_int32, c_void_p]),
+    "pw_push_plan_batch_run_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, ctypes.c_double,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                              c_void_p]),
+    "pw_push_plan_batch_read_states": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pw_push_plan_batch_read_links": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "pw_push_plan_batch_cancel": (c_int, [c_void_p]),
+    "pw_push_plan_batch_destroy": (None, [c_void_p]),
 }
 
 # pw_plan_replay_check verdicts and the `include` choices (include/pushworld_amd.h)
@@ -1390,6 +1401,55 @@ class PushPlannerHandle:
         h = getattr(self, "handle", None)
         if h and lib is not None:
             lib.pw_push_planner_destroy(h)
+        self.handle = None
+
+    __del__ = close
+
+
+PUSH_PLAN_BATCH_INFO = 11  # PW_PUSH_PLAN_BATCH_INFO: pw_push_planner_run's ten values, then the search time in nanoseconds
+
+
+class PushPlanBatchHandle:
+    """A ``PwPushPlanBatch`` (``pw_push_plan_batch_*``: best-first search over pushes of many puzzles or live states in one
+    launch) over the set indices ``puzzles`` of ``engine``'s set.  Thin: every method is one call of the C ABI on the current
+    stream."""
+
+    def __init__(self, engine: "Engine", puzzles, max_states: int, batch: int, rgd_budget: int, cost_range: int):
+        self.engine = engine  # (keeps the engine alive as long as the searches)
+        self.handle = None
+        ids = (c_int32 * len(puzzles))(*[int(p) for p in puzzles])
+        h = c_void_p()
+        check(lib.pw_push_plan_batch_create(engine.handle, ids, len(puzzles), int(max_states), int(batch), int(rgd_budget),
+                                            int(cost_range), ctypes.byref(h)))
+        self.handle = h
+
+    def run(self, max_rounds, time_limit, info, plan_len, plan_from, plan_action, plan_pos, push_cap, npad) -> None:
+        check(lib.pw_push_plan_batch_run(self.handle, int(max_rounds), float(time_limit), _ptr(info), _ptr(plan_len),
+                                         _ptr(plan_from), _ptr(plan_action), _ptr(plan_pos), int(push_cap), int(npad),
+                                         self.engine._stream()))
+
+    def run_states(self, puzzle_id, pos, npad, mask, n, max_rounds, time_limit, info, plan_len, plan_from, plan_action, plan_pos,
+                   push_cap, first_from, first_action) -> None:
+        check(lib.pw_push_plan_batch_run_states(self.handle, _ptr(puzzle_id), _ptr(pos), int(npad), _ptr(mask), int(n),
+                                                int(max_rounds), float(time_limit), _ptr(info), _ptr(plan_len), _ptr(plan_from),
+                                                _ptr(plan_action), _ptr(plan_pos), int(push_cap), _ptr(first_from),
+                                                _ptr(first_action), self.engine._stream()))
+
+    def read_states(self, item, first, count, pos, npad, canon) -> None:
+        check(lib.pw_push_plan_batch_read_states(self.handle, int(item), int(first), int(count), _ptr(pos), int(npad), _ptr(canon),
+                                                 self.engine._stream()))
+
+    def read_links(self, item, first, count, parent, frm, action, goal) -> None:
+        check(lib.pw_push_plan_batch_read_links(self.handle, int(item), int(first), int(count), _ptr(parent), _ptr(frm),
+                                                _ptr(action), _ptr(goal), self.engine._stream()))
+
+    def cancel(self) -> None:
+        check(lib.pw_push_plan_batch_cancel(self.handle))
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.pw_push_plan_batch_destroy(h)
         self.handle = None
 
     __del__ = close

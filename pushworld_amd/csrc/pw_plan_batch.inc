@@ -97,7 +97,8 @@ __device__ __forceinline__ uint32_t pb_hash(const uint32_t* w, int nw) {
 }
 
 // lowest non-empty bucket >= b, nb when there is none (lane-serial; level 1 has at most 64 words)
-__device__ uint32_t pb_next_bucket(const PbArgs& a, const unsigned long long* bits0, const unsigned long long* bits1, uint32_t b) {
+template <class A>  // (PbArgs, or pw_push_plan_batch.inc's arguments: nb, n0, n1)
+__device__ uint32_t pb_next_bucket(const A& a, const unsigned long long* bits0, const unsigned long long* bits1, uint32_t b) {
   uint32_t w0 = b >> 6;
   if (w0 >= a.n0) return a.nb;
   unsigned long long m = bits0[w0] & (~0ull << (b & 63u));

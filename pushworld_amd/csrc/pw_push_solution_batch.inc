@@ -30,7 +30,8 @@
 #define PW_PSB_META_OUTSIDE 0x80000000u  // the successor leaves the grid (kept out of the flags that are stored)
 
 // row y of board k of one lane: the boards of the 256 lanes are interleaved (consecutive lanes, consecutive 16-bit words)
-#define PW_PSB_B(b, k, y) (b)[((k) * 16 + (y)) * 256]
+#define PW_PSB_BS(b, k, y, lanes) (b)[((k) * 16 + (y)) * (lanes)]
+#define PW_PSB_B(b, k, y) PW_PSB_BS(b, k, y, 256)
 
 struct PushSolveBatchArgs {
   const PwPuzzleHeader* hdrs;
@@ -104,56 +105,63 @@ __device__ __forceinline__ int pw_psb_step(const P& p, const PwPuzzleHeader* h, 
 
 // The walk region of the state PP from (x0, y0), a fixed point over a to-do board: board 0 visited, board 1 to do, and with
 // kPush boards 2 .. 5 the positions that push by action 0 .. 3.  At most 256 cells, four steps each.  Returns canon as x | y << 4.
-template <bool kPush, class P>
-__device__ __forceinline__ uint32_t pw_psb_region(const P& p, const PwPuzzleHeader* h, const uint32_t (&OT)[8],
+// kLanes: the lanes whose boards are interleaved at `b` (256 here, 64 in pw_push_plan_batch.inc).
+template <bool kPush, int kLanes, class P>
+__device__ __forceinline__ uint32_t pw_psb_region_lanes(const P& p, const PwPuzzleHeader* h, const uint32_t (&OT)[8],
                                                   const uint32_t (&PP)[4], int x0, int y0, uint16_t* b) {
   const int W = h->W, H = h->H, aw = static_cast<int>(OT[0] & 0xffu), ah = static_cast<int>((OT[0] >> 8) & 0xffu);
   for (int y = 0; y < 16; y++) {
-    PW_PSB_B(b, 0, y) = 0;
-    PW_PSB_B(b, 1, y) = 0;
+    PW_PSB_BS(b, 0, y, kLanes) = 0;
+    PW_PSB_BS(b, 1, y, kLanes) = 0;
     if (kPush) {
-      PW_PSB_B(b, 2, y) = 0;
-      PW_PSB_B(b, 3, y) = 0;
-      PW_PSB_B(b, 4, y) = 0;
-      PW_PSB_B(b, 5, y) = 0;
+      PW_PSB_BS(b, 2, y, kLanes) = 0;
+      PW_PSB_BS(b, 3, y, kLanes) = 0;
+      PW_PSB_BS(b, 4, y, kLanes) = 0;
+      PW_PSB_BS(b, 5, y, kLanes) = 0;
     }
   }
-  PW_PSB_B(b, 0, y0) = static_cast<uint16_t>(1u << x0);
-  PW_PSB_B(b, 1, y0) = static_cast<uint16_t>(1u << x0);
+  PW_PSB_BS(b, 0, y0, kLanes) = static_cast<uint16_t>(1u << x0);
+  PW_PSB_BS(b, 1, y0, kLanes) = static_cast<uint16_t>(1u << x0);
   for (int cell = 0; cell < 256; cell++) {
     int y = 0;
     uint32_t row = 0;
     for (; y < 16; y++) {
-      row = PW_PSB_B(b, 1, y);
+      row = PW_PSB_BS(b, 1, y, kLanes);
       if (row) break;
     }
     if (y >= 16) break;
     const int x = __ffs(row) - 1;
-    PW_PSB_B(b, 1, y) = static_cast<uint16_t>(row & (row - 1u));
+    PW_PSB_BS(b, 1, y, kLanes) = static_cast<uint16_t>(row & (row - 1u));
 #pragma unroll 1
     for (int act = 0; act < 4; act++) {
       const int rx = x + (act == 0 ? -1 : (act == 1 ? 1 : 0)), ry = y + (act == 2 ? -1 : (act == 3 ? 1 : 0));
       // the agent would leave its grid (not in the region) or the cell is known already: a walk move there adds nothing, so
       // the flood for a canon alone does not ask for the step's verdict (the flood for the push boards needs it: a push?)
-      const bool fresh = !(rx < 0 || ry < 0 || rx + aw > W || ry + ah > H || rx > 15 || ry > 15) && !((PW_PSB_B(b, 0, ry) >> rx) & 1u);
+      const bool fresh = !(rx < 0 || ry < 0 || rx + aw > W || ry + ah > H || rx > 15 || ry > 15) && !((PW_PSB_BS(b, 0, ry, kLanes) >> rx) & 1u);
       if (!kPush && !fresh) continue;
       LaneEnv<8> s;
       const int kind = pw_psb_step(p, h, OT, PP, x, y, act, s);
       if (kind == 1) {
         if (!fresh) continue;
-        const uint32_t seen = PW_PSB_B(b, 0, ry);
-        PW_PSB_B(b, 0, ry) = static_cast<uint16_t>(seen | (1u << rx));
-        PW_PSB_B(b, 1, ry) = static_cast<uint16_t>(PW_PSB_B(b, 1, ry) | (1u << rx));
+        const uint32_t seen = PW_PSB_BS(b, 0, ry, kLanes);
+        PW_PSB_BS(b, 0, ry, kLanes) = static_cast<uint16_t>(seen | (1u << rx));
+        PW_PSB_BS(b, 1, ry, kLanes) = static_cast<uint16_t>(PW_PSB_BS(b, 1, ry, kLanes) | (1u << rx));
       } else if (kPush && kind == 2) {
-        PW_PSB_B(b, 2 + act, y) = static_cast<uint16_t>(PW_PSB_B(b, 2 + act, y) | (1u << x));
+        PW_PSB_BS(b, 2 + act, y, kLanes) = static_cast<uint16_t>(PW_PSB_BS(b, 2 + act, y, kLanes) | (1u << x));
       }
     }
   }
   for (int y = 0; y < 16; y++) {
-    const uint32_t row = PW_PSB_B(b, 0, y);
+    const uint32_t row = PW_PSB_BS(b, 0, y, kLanes);
     if (row) return static_cast<uint32_t>(__ffs(row) - 1) | (static_cast<uint32_t>(y) << 4);
   }
   return static_cast<uint32_t>(x0) | (static_cast<uint32_t>(y0) << 4);  // (never: the start is visited)
+}
+
+template <bool kPush, class P>
+__device__ __forceinline__ uint32_t pw_psb_region(const P& p, const PwPuzzleHeader* h, const uint32_t (&OT)[8],
+                                                  const uint32_t (&PP)[4], int x0, int y0, uint16_t* b) {
+  return pw_psb_region_lanes<kPush, 256>(p, h, OT, PP, x0, y0, b);
 }
 
 __global__ __launch_bounds__(256) void pw_push_solve_batch_kernel(PushSolveBatchArgs a) {

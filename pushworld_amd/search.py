@@ -2585,3 +2585,322 @@ def push_rows_to_plans(engine_or_vec, puzzle_id_rows: torch.Tensor, rows, item_o
     u = unroll_pushes(engine, puzzle_id_rows, rows.push_from, rows.push_action, pos=rows.pos)
     engine.push_unroll_plans(item_offset, u.length, u.offset, u.actions, T, u.num_actions, plans, plan_len)
     return plans, plan_len, pushes
+
+
+# ---- best-first search over pushes of many puzzles or live states in one launch (pw_push_plan_batch_*) ----------
+PUSH_PLAN_BATCH_INFO = _capi.PUSH_PLAN_BATCH_INFO  # the ten PushPlannerInfo values, then the search time on the device in ns
+PUSH_PLAN_CUT = -2  # plan_len of a plan with more pushes than push_cap: nothing of it is written
+
+PushPlanQuery = namedtuple("PushPlanQuery", "push_from push_action pushes status")
+PushPlanQuery.__doc__ = """What ``PushStatePlanner.plan`` returns, device tensors with one entry per item: ``push_from`` int8 [n, 2]
+and ``push_action`` uint8 [n], the first push of the item's plan ((0, 0) / ``PUSH_NONE`` where ``pushes`` <= 0), ``pushes`` int32
+[n] the number of pushes of the plan (-1: no plan, 0: the state is a goal state) and ``status`` int64 [n] (``PLAN_STATUS``)."""
+
+
+def _push_plan_run_args(max_rounds, time_limit, push_cap):
+    if max_rounds is not None and int(max_rounds) <= 0:
+        raise ValueError("max_rounds must be positive (or None)")
+    if time_limit is not None and not float(time_limit) > 0:
+        raise ValueError("time_limit must be positive seconds (or None)")
+    if int(push_cap) < 0:
+        raise ValueError("push_cap must be >= 0")
+    return 0 if max_rounds is None else int(max_rounds), 0.0 if time_limit is None else float(time_limit), int(push_cap)
+
+
+def _push_plan_create_args(batch, max_states, rgd_budget, cost_range):
+    if not 1 <= int(batch) <= 64:
+        raise ValueError("batch must be in 1 .. 64")
+    if not 1 <= int(max_states) <= 1 << 28:
+        raise ValueError("max_states must be in 1 .. 2^28")
+    if rgd_budget is not None and int(rgd_budget) < 1:
+        raise ValueError("rgd_budget must be >= 1 (or None)")
+    if cost_range is not None and not 1 <= int(cost_range) <= 65536:
+        raise ValueError("cost_range must be in 1 .. 65536 (or None)")
+    return int(batch), int(max_states), 0 if rgd_budget is None else int(rgd_budget), 0 if cost_range is None else int(cost_range)
+
+
+def _push_plan_results(info, plan_len, plan_from, plan_action):
+    """``(pushes as [((x, y), action)] or None, PushPlannerInfo, device seconds)`` per item from host arrays."""
+    out = []
+    for i in range(info.shape[0]):
+        pi = PushPlannerInfo(int(v) for v in info[i, :10])
+        n = int(plan_len[i])
+        pushes = None
+        if pi.status == "solved" and 0 <= n <= plan_from.shape[1]:
+            pushes = [((int(plan_from[i, t, 0]), int(plan_from[i, t, 1])), int(plan_action[i, t])) for t in range(n)]
+        out.append((pushes, pi, float(info[i, 10]) * 1e-9))
+    return out
+
+
+def _push_plans_to_primitive(engine, puzzle_id, plan_len, plan_from, plan_action, plan_pos, plan_cap: int):
+    """The push plans of a run as primitive plans in ``replay_plans``' format: one ``unroll_pushes`` over the plans' rows (its
+    one wait, plus one for the number of rows) and one gather launch."""
+    n, cap = int(plan_len.shape[0]), int(plan_from.shape[1])
+    plan_cap = int(plan_cap)
+    if not 1 <= plan_cap <= _capi.PLAN_MAX_ACTIONS:
+        raise ValueError(f"plan_cap must be in 1 .. {_capi.PLAN_MAX_ACTIONS}")
+    dev = plan_len.device
+    pushes = plan_len.clamp(min=0)
+    item_offset = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    item_offset[1:] = torch.cumsum(pushes.to(torch.int64), 0)
+    plans = torch.zeros((n, plan_cap), dtype=torch.uint8, device=dev)
+    out_len = torch.zeros((n,), dtype=torch.int32, device=dev)
+    keep = torch.arange(cap, device=dev).view(1, cap) < pushes.view(n, 1)
+    T = int(item_offset[n].item())
+    if T > 0:
+        ids = puzzle_id.view(n, 1).expand(n, cap)[keep].contiguous()
+        u = unroll_pushes(engine, ids, plan_from[keep].contiguous(), plan_action[keep].contiguous(), pos=plan_pos[keep].contiguous())
+        engine.push_unroll_plans(item_offset, u.length, u.offset, u.actions, T, u.num_actions, plans, out_len)
+    out_len = torch.where(plan_len < 0, torch.full_like(out_len, REPLAY_NONE), out_len)
+    return plans, out_len, pushes.to(torch.int32)
+
+
+class PushPlanBatch:
+    """Best-first search over pushes (``PushBestFirstSearch``'s semantics) of MANY puzzles in ONE launch
+    (``pw_push_plan_batch_*``, K24): persistent workgroups of one wavefront run each puzzle's whole search inside the kernel.
+    Item i's ``PushPlannerInfo``, plan, store and links equal ``PushBestFirstSearch(puzzles[i], batch, max_states, rgd_budget)``
+    + ``begin()`` + ``run(max_rounds)`` as long as no finite RGD cost reaches ``cost_range``; three statuses are new:
+    ``timeout``, ``range`` and ``skipped`` (a puzzle beyond 16 x 16 cells with the border or 8 movables).
+
+    Args:
+        puzzles: ``PushWorldPuzzle`` objects (each in its own object order), all on one device.
+        batch: K, states popped per round (1 .. 64).
+        max_states: states per puzzle; every workgroup owns a slab of that many (see ``pw_push_plan_batch_create``).
+        cost_range: finite costs with a bucket (None: 65536)."""
+
+    def __init__(self, puzzles: Sequence[PushWorldPuzzle], batch: int = 1, max_states: int = 1 << 16,
+                 rgd_budget: Optional[int] = None, cost_range: Optional[int] = None):
+        self.handle = None
+        args = _push_plan_create_args(batch, max_states, rgd_budget, cost_range)
+        self.puzzles = list(puzzles)
+        if not self.puzzles:
+            raise ValueError("puzzles must not be empty")
+        from .puzzle import default_device_index
+
+        self.batch, self.max_states = args[0], args[1]
+        self._pset = _capi.PuzzleSet([p._parsed for p in self.puzzles], default_device_index())
+        self._engine = _capi.Engine(self._pset, None, 3, 1, _capi.OBS_U8)
+        self.device, self.npad, self.n = self._engine.device, int(self._engine.np), len(self.puzzles)
+        self.handle = _capi.PushPlanBatchHandle(self._engine, list(range(self.n)), args[1], args[0], args[2], args[3])
+        self._out = None
+
+    def run(self, max_rounds: Optional[int] = None, time_limit: Optional[float] = None, push_cap: int = 256) -> None:
+        """Starts the searches (one launch on the current stream; returns at once).  ``max_rounds`` per puzzle (None: no
+        limit), ``time_limit`` seconds per puzzle on the device's clock (None: none); plans of more than ``push_cap`` pushes
+        are not written (``plan_len`` -2).  ``results`` waits for them."""
+        rounds, limit, cap = _push_plan_run_args(max_rounds, time_limit, push_cap)
+        if self.handle is None:
+            raise ValueError("the batch is closed")
+        info = torch.empty((self.n, PUSH_PLAN_BATCH_INFO), dtype=torch.int64, device=self.device)
+        plan_len = torch.empty((self.n,), dtype=torch.int32, device=self.device)
+        plan_from = torch.zeros((self.n, cap, 2), dtype=torch.int8, device=self.device)
+        plan_action = torch.zeros((self.n, cap), dtype=torch.uint8, device=self.device)
+        plan_pos = torch.zeros((self.n, cap, self.npad, 2), dtype=torch.int8, device=self.device)
+        self.handle.run(rounds, limit, info, plan_len, plan_from, plan_action, plan_pos, cap, self.npad)
+        self._out = (info, plan_len, plan_from, plan_action, plan_pos)
+
+    def _last(self):
+        if self._out is None:
+            raise RuntimeError("run() has not been called")
+        return self._out
+
+    def cancel(self) -> None:
+        """Stops the searches of every ``run`` so far soon (their status stays ``running``).  Replays of a captured ``run``
+        that begin afterwards are not cancelled."""
+        if self.handle is None:
+            raise ValueError("the batch is closed")
+        self.handle.cancel()
+
+    def results(self):
+        """``(pushes as [((x, y), action)] or None, PushPlannerInfo, device seconds)`` per puzzle of the last ``run`` (waits
+        for it).  A plan of more than ``push_cap`` pushes is None."""
+        info, plan_len, plan_from, plan_action, _ = self._last()
+        return _push_plan_results(*(t.cpu().numpy() for t in (info, plan_len, plan_from, plan_action)))
+
+    def primitive_plans(self, plan_cap: int = 4096):
+        """``(plans uint8 [n, plan_cap], plan_len int32 [n], pushes int32 [n])`` on the device, in ``replay_plans``' format:
+        every push plan of the last ``run`` unrolled into primitive actions (``unroll_pushes`` over the states each push is
+        made from, then ``pw_push_unroll_plans``).  ``plan_len`` is ``REPLAY_NONE`` for an item without a written plan; a
+        plan longer than ``plan_cap`` keeps its length and its first ``plan_cap`` actions."""
+        _, plan_len, plan_from, plan_action, plan_pos = self._last()
+        ids = torch.arange(self.n, dtype=torch.int32, device=self.device)
+        return _push_plans_to_primitive(self._engine, ids, plan_len, plan_from, plan_action, plan_pos, plan_cap)
+
+    def validate(self, plan_cap: int = 4096) -> torch.Tensor:
+        """int8 [n] on the device: the ``is_valid_plan`` verdict (``REPLAY_VERDICT``) of every plan of the last ``run``,
+        unrolled by ``primitive_plans`` and replayed by one launch (``replay_plans``)."""
+        plans, plan_len, _ = self.primitive_plans(plan_cap)
+        ids = torch.arange(self.n, dtype=torch.int32, device=self.device)
+        return replay_plans(self._engine, ids, plans, plan_len, rows=False).verdict
+
+    def states(self, item: int, first: int = 0, count: Optional[int] = None):
+        """(pos int8 [count, NP, 2] the states as reached, canon int8 [count, 2]) of the store of ``item`` of the last ``run``,
+        on the device.  A workgroup keeps the store of the last item it ran: ``ValueError`` for an item that a later one
+        displaced (runs of more items than workgroups) or that was skipped."""
+        count = self._stored(item) - first if count is None else int(count)
+        pos = torch.empty((count, self.npad, 2), dtype=torch.int8, device=self.device)
+        canon = torch.empty((count, 2), dtype=torch.int8, device=self.device)
+        self.handle.read_states(item, first, count, pos, self.npad, canon)
+        return pos, canon
+
+    def links(self, item: int, first: int = 0, count: Optional[int] = None):
+        """(parent int32, from int8 [count, 2], action uint8, goal uint8) of the store of ``item``, as ``states``; the start
+        state has parent -1 and action 0xFF."""
+        count = self._stored(item) - first if count is None else int(count)
+        parent = torch.empty((count,), dtype=torch.int32, device=self.device)
+        frm = torch.empty((count, 2), dtype=torch.int8, device=self.device)
+        action = torch.empty((count,), dtype=torch.uint8, device=self.device)
+        goal = torch.empty((count,), dtype=torch.uint8, device=self.device)
+        self.handle.read_links(item, first, count, parent, frm, action, goal)
+        return parent, frm, action, goal
+
+    def _stored(self, item: int) -> int:
+        if not 0 <= int(item) < self.n:
+            raise ValueError("item out of bounds")
+        return int(self._last()[0][int(item), 3].item())
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h is not None:
+            try:  # (a launch in flight on any stream still uses the slabs)
+                torch.cuda.synchronize(self.device)
+            except Exception:
+                pass
+            h.close()
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+
+def solve_many_pushes(puzzles: Sequence[PushWorldPuzzle], batch: int = 1, max_states: int = 1 << 16,
+                      time_limit: Optional[float] = None, rgd_budget: Optional[int] = None, cost_range: Optional[int] = None,
+                      push_cap: int = 256):
+    """The best-first search over pushes of many puzzles in one launch (``PushPlanBatch``): ``(pushes or None,
+    PushPlannerInfo, device seconds)`` per puzzle.  Nothing is raised for a puzzle that ends at ``max_states``, ``time_limit``
+    or ``cost_range`` or that is beyond the kernel's limits: its ``PushPlannerInfo.status`` says so."""
+    with PushPlanBatch(puzzles, batch=batch, max_states=max_states, rgd_budget=rgd_budget, cost_range=cost_range) as pb:
+        pb.run(time_limit=time_limit, push_cap=push_cap)
+        return pb.results()
+
+
+class PushStatePlanner:
+    """Best-first search over pushes from given states of a puzzle set, MANY in ONE launch
+    (``pw_push_plan_batch_run_states``): typically the live states of a ``VecPushWorld`` -- an expert in pushes where no
+    table can be exhausted.  Item i's ``PushPlannerInfo`` and push plan equal ``PushBestFirstSearch(puzzle puzzle_id[i], batch,
+    max_states, rgd_budget)`` + ``begin(start=pos[i])`` + ``run(max_rounds)`` as long as no finite RGD cost reaches
+    ``cost_range``.  Items that are masked out, name a puzzle outside ``puzzles`` or beyond the kernel's limits (16 x 16 cells
+    with the border, 8 movables) or hold a movable outside its grid are ``skipped``.
+
+    Args:
+        source: a ``VecPushWorld`` or an ``_capi.Engine``: the planner uses its puzzle set (object order, ``NP``).
+        puzzles: the set indices to prepare (None: every puzzle of the set); construction builds one RGD table set each.
+        batch: K, states popped per round (1 .. 64).
+        max_states: states per item; every workgroup owns a slab of that many (see ``pw_push_plan_batch_create``).
+        cost_range: finite costs with a bucket (None: 65536)."""
+
+    def __init__(self, source, puzzles: Optional[Sequence[int]] = None, batch: int = 1, max_states: int = 1 << 16,
+                 rgd_budget: Optional[int] = None, cost_range: Optional[int] = None):
+        self.handle = None
+        args = _push_plan_create_args(batch, max_states, rgd_budget, cost_range)
+        engine = source if isinstance(source, _capi.Engine) else getattr(source, "engine", None)
+        if not isinstance(engine, _capi.Engine):
+            raise ValueError("source must be a VecPushWorld or an _capi.Engine")
+        self.engine, self.device, self.npad = engine, engine.device, int(engine.np)
+        count = len(engine.pset)
+        self.puzzles = list(range(count)) if puzzles is None else [int(p) for p in puzzles]
+        if not self.puzzles:
+            raise ValueError("puzzles must not be empty")
+        if min(self.puzzles) < 0 or max(self.puzzles) >= count:
+            raise ValueError(f"puzzles must be indices into the set (0 .. {count - 1})")
+        self.batch, self.max_states = args[0], args[1]
+        self.handle = _capi.PushPlanBatchHandle(engine, self.puzzles, args[1], args[0], args[2], args[3])
+        self._out = None
+
+    def plan(self, puzzle_id: torch.Tensor, pos: torch.Tensor, mask: Optional[torch.Tensor] = None,
+             max_rounds: Optional[int] = None, time_limit: Optional[float] = None, push_cap: int = 0) -> PushPlanQuery:
+        """Starts the searches from ``pos`` (int8 [n, NP, 2], the engine's layout) of puzzles ``puzzle_id`` (int32 [n]), both
+        on the device, on the current stream; does not wait.  ``mask`` (uint8 / bool [n]): 0 skips an item.  ``max_rounds``
+        per item (None: no limit), ``time_limit`` seconds per item on the device's clock (None: none).  ``push_cap`` > 0 also
+        keeps the whole plans of at most that many pushes for ``results`` / ``primitive_plans`` (longer ones: ``pushes`` -2).
+        Returns a ``PushPlanQuery``."""
+        n = _state_inputs(puzzle_id, pos, mask, self.npad, self.device)
+        rounds, limit, cap = _push_plan_run_args(max_rounds, time_limit, push_cap)
+        if self.handle is None:
+            raise ValueError("the planner is closed")
+        dev = self.device
+        info = torch.empty((n, PUSH_PLAN_BATCH_INFO), dtype=torch.int64, device=dev)
+        plan_len = torch.empty((n,), dtype=torch.int32, device=dev)
+        first_from = torch.empty((n, 2), dtype=torch.int8, device=dev)
+        first_action = torch.empty((n,), dtype=torch.uint8, device=dev)
+        plan_from = plan_action = plan_pos = None
+        if cap > 0:
+            plan_from = torch.zeros((n, cap, 2), dtype=torch.int8, device=dev)
+            plan_action = torch.zeros((n, cap), dtype=torch.uint8, device=dev)
+            plan_pos = torch.zeros((n, cap, self.npad, 2), dtype=torch.int8, device=dev)
+        if mask is not None and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        self.handle.run_states(puzzle_id, pos, self.npad, mask, n, rounds, limit, info, plan_len, plan_from, plan_action, plan_pos,
+                               cap, first_from, first_action)
+        # (the inputs stay referenced until the results are read: the launch reads them on the device)
+        self._out = (info, plan_len, plan_from, plan_action, plan_pos, puzzle_id, pos, mask)
+        return PushPlanQuery(first_from, first_action, plan_len, info[:, 0])
+
+    def _last(self, plans: bool):
+        if self._out is None:
+            raise RuntimeError("plan() has not been called")
+        if plans and self._out[2] is None:
+            raise ValueError("the last plan() call kept no plans (push_cap 0)")
+        return self._out
+
+    def info(self) -> torch.Tensor:
+        """int64 [n, 11] on the device: the ``PushPlannerInfo`` values of every item of the last ``plan``, then device ns."""
+        return self._last(False)[0]
+
+    def results(self):
+        """``(pushes as [((x, y), action)] or None, PushPlannerInfo, device seconds)`` per item of the last ``plan`` (waits
+        for it), as ``PushPlanBatch.results``; needs ``push_cap`` > 0."""
+        info, plan_len, plan_from, plan_action = self._last(True)[:4]
+        return _push_plan_results(*(t.cpu().numpy() for t in (info, plan_len, plan_from, plan_action)))
+
+    def primitive_plans(self, plan_cap: int = 4096):
+        """As ``PushPlanBatch.primitive_plans``, for the items of the last ``plan`` (from that call's start states)."""
+        _, plan_len, plan_from, plan_action, plan_pos, puzzle_id = self._last(True)[:6]
+        return _push_plans_to_primitive(self.engine, puzzle_id, plan_len, plan_from, plan_action, plan_pos, plan_cap)
+
+    def validate(self, plan_cap: int = 4096) -> torch.Tensor:
+        """int8 [n] on the device: the ``is_valid_plan`` verdict of every plan of the last ``plan`` call, replayed from that
+        call's start states."""
+        plans, plan_len, _ = self.primitive_plans(plan_cap)
+        puzzle_id, pos, mask = self._out[5:8]
+        return replay_plans(self.engine, puzzle_id, plans, plan_len, pos=pos, mask=mask, rows=False).verdict
+
+    def cancel(self) -> None:
+        """Stops the searches of every ``plan`` so far soon (their status stays ``running``).  Replays of a captured ``plan``
+        that begin afterwards are not cancelled."""
+        if self.handle is None:
+            raise ValueError("the planner is closed")
+        self.handle.cancel()
+
+    def close(self) -> None:
+        h = getattr(self, "handle", None)
+        if h is not None:
+            try:  # (a launch in flight still uses the slabs)
+                torch.cuda.synchronize(self.device)
+            except Exception:
+                pass
+            h.close()
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close

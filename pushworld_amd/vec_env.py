@@ -373,6 +373,28 @@ class VecPushWorld:
             mask = mask.to(device=self.device, dtype=torch.uint8)
         return planner.plan(self.puzzle_id, self.pos, mask=mask, plan_cap=0, **run_kw)[3]
 
+    def push_planner(self, **kw):
+        """A ``search.PushStatePlanner`` over this batch's puzzle set: the best-first search over pushes from live states;
+        ``kw`` are its arguments (``puzzles``, ``batch``, ``max_states``, ``rgd_budget``, ``cost_range``)."""
+        from .search import PushStatePlanner
+
+        return PushStatePlanner(self, **kw)
+
+    def planned_pushes(self, planner, mask: Optional[torch.Tensor] = None, **run_kw):
+        """A ``search.PushPlanQuery`` of device tensors: ``push_from`` int8 [B, 2] / ``push_action`` uint8 [B], the first push
+        of ``planner``'s plan from every environment's current state -- (0, 0) / ``PUSH_NONE`` where there is none (unsolved
+        within the limits, already at the goal, masked out or skipped), which ``step_push`` refuses -- ``pushes`` int32 [B]
+        (the plan's length, -1 without a plan) and ``status`` int64 [B].  One launch on the current stream after whatever
+        was queued there, no wait: ``vec.step_push(q.push_from, q.push_action)`` follows it directly.  ``run_kw``:
+        ``max_rounds``, ``time_limit`` and ``push_cap`` of ``PushStatePlanner.plan``.  ``push_cap`` (default 0) > 0 keeps the whole
+        plans of at most that many pushes, which ``planner.results()`` / ``primitive_plans()`` / ``validate()`` need;
+        ``planner.info()`` reads the counts either way."""
+        if planner.engine is not self.engine:
+            raise ValueError("the planner must be made on this environment (VecPushWorld.push_planner)")
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8)
+        return planner.plan(self.puzzle_id, self.pos, mask=mask, **run_kw)
+
     def demonstrations(self, planner, observation: Optional[str] = "own", include: str = "valid",
                        mask: Optional[torch.Tensor] = None, plan_cap: int = 1024, **run_kw):
         """A flat demonstration dataset from every environment's current state: ``planner`` plans from the live states, the
