@@ -377,6 +377,12 @@ int64_t pw_engine_obs_stride(const PwEngine* e);       /* recommended env stride
                                       (1 takes whichever the tuner measured faster, the list when it never ran) */
 #define PW_OPT_OBS_LIVE_PAGES 54     /* read-only: length of the live-page list of the retained observation, 0 when nothing is retained (synchronises
                                       the device when the list was last rebuilt in-stream) */
+#define PW_OPT_RESAMPLE_FENCE 55     /* pw_resample_weighted: 0 (default) the binary search reads the cdf alone, 1 every workgroup that draws first
+                                      copies a sampled fence of the cdf into LDS.  A/B runs; same draws either way */
+#define PW_OPT_STATS_LDS_PUZZLES 56  /* pw_episode_stats: largest set whose launch sums per workgroup in LDS before it adds to the block, 1 .. 1024;
+                                      0 the default, 2048 never (every contributing lane adds to the block).  Same sums either way */
+#define PW_OPT_STATS_GROUPS 57       /* pw_episode_stats: most workgroups of a launch (they stride over the batch); 0 (default) one per 256
+                                      environments */
 int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value);
 int64_t pw_engine_get_option(const PwEngine* e, int32_t option);
 /* Durations (milliseconds) of the render launches recorded since the last call, in launch order
@@ -496,6 +502,54 @@ uint64_t pw_mix64(uint64_t seed, uint64_t env, uint64_t episode); /* host copy o
 int pw_resample(PwEngine* e, int32_t* puzzle_id, const uint8_t* terminated, const uint8_t* truncated,
                 const int32_t* table, int32_t table_len, uint64_t seed, uint32_t* episode,
                 int32_t batch, void* stream);
+
+/* The level above the single puzzle: statistics per puzzle, sampling weights made from them, and a weighted draw,
+ * all on the device.  Integer arithmetic only: every result is exact and independent of launch geometry and atomic order.  The
+ * three launches run on `stream`, allocate nothing, never synchronise and can be captured.  Every argument error returns PW_EINVAL
+ * with the function's name and the offending argument in pw_last_error, before anything is read through a pointer.
+ *
+ * pw_episode_stats: called once after a step launch, on the flags that step left (with PW_STEP_AUTORESET: without it a finished
+ * environment keeps its flags and would be counted by every call).  P = the size of the engine's puzzle set; `stats` is a device
+ * block int64 [P][PW_EPISODE_STATS] that the caller zeroes once.  Environment i contributes when
+ *     (terminated[i] | truncated[i]) != 0  and  terminated[i] != 0xFF  and  0 <= puzzle_id[i] < P
+ * (a refused action is no episode end, and the episode it abandons is not counted; an id outside the set is skipped) and adds to
+ * row puzzle_id[i]:  EPISODES += 1;  STEPS += steps[i];  and when terminated[i] != 0:  SOLVED += 1;  SOLVED_STEPS += steps[i].
+ * batch == 0 is a no-op.  No atomic of the launch returns a value. */
+#define PW_EPISODE_STATS 4   /* EPISODES, SOLVED, STEPS, SOLVED_STEPS */
+#define PW_STATS_EPISODES 0
+#define PW_STATS_SOLVED 1
+#define PW_STATS_STEPS 2
+#define PW_STATS_SOLVED_STEPS 3
+int pw_episode_stats(PwEngine* e, const int32_t* puzzle_id, const int32_t* steps, const uint8_t* terminated,
+                     const uint8_t* truncated, int64_t* stats, int32_t batch, void* stream);
+
+/* pw_curriculum_update: ONE launch turns statistics into sampling weights (Q16, uint32) and their inclusive prefix sums.  Per
+ * puzzle p, with n = EPISODES and s = SOLVED of stats[p] - base[p] (base NULL = zero; a negative difference counts as 0):
+ *     k = max(0, bit_length(n) - 20);  n' = n >> k;  s' = min(s >> k, n');  f' = n' - s'          (unsigned 64-bit throughout)
+ *     PW_CURRICULUM_UNIFORM   w = 65536
+ *     PW_CURRICULUM_FAILURE   w = floor(65536 (f' + 1) / (n' + 2))                    -- unseen: 32768
+ *     PW_CURRICULUM_FRONTIER  w = floor(262144 (s' + 1)(f' + 1) / (n' + 2)^2)         -- largest (65536) at a success rate of 1/2 and
+ *                                                                                        unseen; the product stays below 2^61
+ *     PW_CURRICULUM_GIVEN     w = given[p]                                            -- device uint32 [P]
+ * then  w = max(w, floor_q16),  weights[p] = w (when given)  and  cdf[p] = w_0 + ... + w_p  (device uint64 [P]).
+ * `stats` is read by FAILURE and FRONTIER only and may be NULL otherwise; `given` is read by GIVEN only. */
+#define PW_CURRICULUM_UNIFORM 0
+#define PW_CURRICULUM_FAILURE 1
+#define PW_CURRICULUM_FRONTIER 2
+#define PW_CURRICULUM_GIVEN 3
+int pw_curriculum_update(PwEngine* e, int32_t mode, const int64_t* stats, const int64_t* base, const uint32_t* given,
+                         uint32_t floor_q16, uint32_t* weights, uint64_t* cdf, void* stream);
+
+/* pw_resample_weighted: pw_resample with the prefix sums of pw_curriculum_update in place of a table.  It redraws exactly the
+ * environments pw_resample would (either flag non-zero; either pointer may be NULL; both NULL = every environment), on
+ * pw_resample's own stream:
+ *     episode[i] += 1;  r = pw_mix64(seed, i, episode[i]);  total = cdf[P - 1]
+ *     total == 0:  puzzle_id[i] = mulhi64(r, P)                                  -- the uniform draw of pw_resample
+ *     otherwise:   t = mulhi64(r, total);  puzzle_id[i] = the smallest p with cdf[p] > t
+ * (mulhi64(a, b) = floor(a b / 2^64)), so a puzzle of weight 0 is never drawn and the draw is a pure function of
+ * (seed, i, episode[i], cdf).  A bound puzzle_id buffer is re-bound behind the draw as behind pw_resample.  batch == 0 is a no-op. */
+int pw_resample_weighted(PwEngine* e, int32_t* puzzle_id, const uint8_t* terminated, const uint8_t* truncated,
+                         const uint64_t* cdf, uint64_t seed, uint32_t* episode, int32_t batch, void* stream);
 
 /* gym_env.py:188-226 step() without the observation:
  *   pos <- get_next_state(pos, action)                 puzzle.py:348-394

@@ -11,6 +11,7 @@ Drop-in for the hot path of google-deepmind/pushworld (``PushWorldPuzzle.get_nex
     from pushworld_amd.vector_env import PushWorldVectorEnv        # gymnasium.vector surface, new
     from pushworld_amd import SolutionTable                        # search.SolutionTable: exact cost-to-go tables, new
     from pushworld_amd import SolutionTableBatch                   # ... of many small puzzles in one launch, new
+    from pushworld_amd.curriculum import Curriculum, EpisodeStats  # statistics per puzzle and weighted draws, new
 """
 __version__ = "0.1.0"
 

@@ -304,7 +304,17 @@ SIGNATURES = {
                                               c_void_p]),
     "pw_push_plan_batch_cancel": (c_int, [c_void_p]),
     "pw_push_plan_batch_destroy": (None, [c_void_p]),
+    "pw_episode_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_curriculum_update": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p,
+                                     c_void_p]),
+    "pw_resample_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_int32,
+                                     c_void_p]),
 }
+
+# pw_episode_stats: the columns of a statistics block; pw_curriculum_update: its modes (include/pushworld_amd.h)
+EPISODE_STATS = 4
+STATS_EPISODES, STATS_SOLVED, STATS_STEPS, STATS_SOLVED_STEPS = 0, 1, 2, 3
+CURRICULUM_MODES = {"uniform": 0, "failure": 1, "frontier": 2, "given": 3}
 
 # pw_plan_replay_check verdicts and the `include` choices (include/pushworld_amd.h)
 REPLAY_VALID, REPLAY_NOT_GOAL, REPLAY_EARLY, REPLAY_NONE, REPLAY_CUT, REPLAY_SKIPPED = 1, 0, 2, -1, -2, -3
@@ -368,6 +378,9 @@ OPTIONS = {
     "obs_padding_once": 53,    # pw_step_render into a retained library-owned buffer of the bound batch renders the live pages only: 0 off, 1 on
                                # (2 / 3: on, with the early-exit / the list form -- A/B runs)
     "obs_live_pages": 54,      # read-only: length of the live-page list of the retained observation (0: nothing retained)
+    "resample_fence": 55,      # pw_resample_weighted: 0 the search reads the cdf alone, 1 a sampled fence of the cdf in LDS (A/B runs)
+    "stats_lds_puzzles": 56,   # pw_episode_stats: largest set summed per workgroup in LDS, 1 .. 1024 (0 default, 2048 never)
+    "stats_groups": 57,        # pw_episode_stats: most workgroups of a launch (0: one per 256 environments)
 }
 _OPTION_VALUES = {"group": 0, "wave": 1, "lane": 2, "auto": 0, "page": 0, "lds": 1, "big": 3, "all": 1, "none": 2,
                   "forward": 0, "reverse": 1, "never": 2**31}
@@ -609,6 +622,16 @@ class PuzzleSet:
 
 def _ptr(t):
     return None if t is None else c_void_p(t.data_ptr())
+
+
+def _tensor_arg(fn: str, name: str, t, dtype, shape):
+    """``t`` must be a contiguous tensor of ``dtype`` and ``shape`` (None = any extent); returns its shape.  The message
+    names the entry point and the argument, as the library's own checks do."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != len(shape) or not t.is_contiguous() \
+            or any(want is not None and have != want for have, want in zip(t.shape, shape)):
+        dims = ", ".join("*" if s is None else str(s) for s in shape)
+        raise ValueError(f"{fn}: {name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape [{dims}]")
+    return tuple(t.shape)
 
 
 # the raw hipStream_t of torch's current stream without building a torch.cuda.Stream object (~0.2 us instead of ~1.5 us;
@@ -988,6 +1011,40 @@ class Engine:
             return rc  # (1: the engine's completion word will be written -- pw_engine_set_step_signal)
         return call
 
+    def bind_episode_stats(self, puzzle_id, steps, terminated, truncated, stats):
+        """Returns ``call()`` == ``episode_stats(...)`` on the current stream (the arguments are checked once, here)."""
+        B = _tensor_arg("pw_episode_stats", "puzzle_id", puzzle_id, torch.int32, (None,))[0]
+        _tensor_arg("pw_episode_stats", "steps", steps, torch.int32, (B,))
+        _tensor_arg("pw_episode_stats", "terminated", terminated, torch.uint8, (B,))
+        _tensor_arg("pw_episode_stats", "truncated", truncated, torch.uint8, (B,))
+        _tensor_arg("pw_episode_stats", "stats", stats, torch.int64, (len(self.pset), EPISODE_STATS))
+        fn, h, dev = lib.pw_episode_stats, self.handle, self.device.index
+        keep = (puzzle_id, steps, terminated, truncated, stats)
+        a = [_ptr(t) for t in keep]
+
+        def call(_keep=keep):
+            rc = fn(h, a[0], a[1], a[2], a[3], a[4], B, _raw_stream(dev))
+            if rc:
+                check(rc)
+        return call
+
+    def bind_resample_weighted(self, puzzle_id, episode, cdf, terminated, truncated):
+        """Returns ``call(seed)`` == ``resample_weighted(puzzle_id, episode, seed, cdf, terminated, truncated)``."""
+        B = _tensor_arg("pw_resample_weighted", "puzzle_id", puzzle_id, torch.int32, (None,))[0]
+        _tensor_arg("pw_resample_weighted", "episode", episode, torch.int32, (B,))
+        _tensor_arg("pw_resample_weighted", "cdf", cdf, torch.uint64, (len(self.pset),))
+        _tensor_arg("pw_resample_weighted", "terminated", terminated, torch.uint8, (B,))
+        _tensor_arg("pw_resample_weighted", "truncated", truncated, torch.uint8, (B,))
+        fn, h, dev = lib.pw_resample_weighted, self.handle, self.device.index
+        keep = (puzzle_id, terminated, truncated, cdf, episode)
+        a = [_ptr(t) for t in keep]
+
+        def call(seed, _keep=keep):
+            rc = fn(h, a[0], a[1], a[2], a[3], seed & 0xFFFFFFFFFFFFFFFF, a[4], B, _raw_stream(dev))
+            if rc:
+                check(rc)
+        return call
+
     def set_step_signal(self, word) -> None:
         """``pw_engine_set_step_signal``: ``word`` = a pinned int64 / uint64 tensor of one element, or None."""
         check(lib.pw_engine_set_step_signal(self.handle, None if word is None else c_void_p(word.data_ptr())))
@@ -1113,6 +1170,59 @@ class Engine:
         check(lib.pw_resample(self.handle, _ptr(puzzle_id), _ptr(terminated), _ptr(truncated), _ptr(table),
                               0 if table is None else table.shape[0], int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(episode),
                               puzzle_id.shape[0], self._stream()))
+
+    # statistics per puzzle, weights and the weighted draw (pw_episode_stats / pw_curriculum_update / pw_resample_weighted):
+    # device tensors in and out, no wait.  The shapes are checked here: the library sees pointers only.
+    def episode_stats(self, puzzle_id, steps, terminated, truncated, stats):
+        """``pw_episode_stats``: the episodes that the flags of the last step ended are added to ``stats``, int64
+        ``[P, EPISODE_STATS]`` (EPISODES, SOLVED, STEPS, SOLVED_STEPS per puzzle of the set)."""
+        B = _tensor_arg("pw_episode_stats", "puzzle_id", puzzle_id, torch.int32, (None,))[0]
+        _tensor_arg("pw_episode_stats", "steps", steps, torch.int32, (B,))
+        _tensor_arg("pw_episode_stats", "terminated", terminated, torch.uint8, (B,))
+        _tensor_arg("pw_episode_stats", "truncated", truncated, torch.uint8, (B,))
+        _tensor_arg("pw_episode_stats", "stats", stats, torch.int64, (len(self.pset), EPISODE_STATS))
+        check(lib.pw_episode_stats(self.handle, _ptr(puzzle_id), _ptr(steps), _ptr(terminated), _ptr(truncated), _ptr(stats),
+                                   B, self._stream()))
+
+    def curriculum_update(self, mode, stats, cdf, weights=None, base=None, given=None, floor_q16=0):
+        """``pw_curriculum_update``: ``weights`` (uint32 ``[P]``, optional) and their inclusive prefix sums ``cdf`` (uint64
+        ``[P]``) from ``stats`` (minus ``base``) in ``mode``, a name or number of ``CURRICULUM_MODES``; ``given`` (uint32
+        ``[P]``) holds the weights of mode "given"."""
+        if isinstance(mode, str):
+            if mode not in CURRICULUM_MODES:
+                raise ValueError(f"pw_curriculum_update: unknown mode {mode!r} (one of {', '.join(CURRICULUM_MODES)})")
+            mode = CURRICULUM_MODES[mode]
+        mode = int(mode)
+        if mode not in CURRICULUM_MODES.values():
+            raise ValueError(f"pw_curriculum_update: unknown mode {mode}")
+        if not 0 <= int(floor_q16) < 1 << 32:
+            raise ValueError("pw_curriculum_update: floor_q16 must be in 0 .. 2^32 - 1")
+        P = len(self.pset)
+        if stats is not None or mode in (CURRICULUM_MODES["failure"], CURRICULUM_MODES["frontier"]):
+            _tensor_arg("pw_curriculum_update", "stats", stats, torch.int64, (P, EPISODE_STATS))
+        if base is not None:
+            _tensor_arg("pw_curriculum_update", "base", base, torch.int64, (P, EPISODE_STATS))
+        if mode == CURRICULUM_MODES["given"]:
+            _tensor_arg("pw_curriculum_update", "given", given, torch.uint32, (P,))
+        if weights is not None:
+            _tensor_arg("pw_curriculum_update", "weights", weights, torch.uint32, (P,))
+        _tensor_arg("pw_curriculum_update", "cdf", cdf, torch.uint64, (P,))
+        check(lib.pw_curriculum_update(self.handle, mode, _ptr(stats), _ptr(base),
+                                       _ptr(given) if mode == CURRICULUM_MODES["given"] else None, int(floor_q16),
+                                       _ptr(weights), _ptr(cdf), self._stream()))
+
+    def resample_weighted(self, puzzle_id, episode, seed, cdf, terminated=None, truncated=None):
+        """Finished environments (flags set; both None = all) draw their next puzzle by the weights behind ``cdf``
+        (``pw_resample_weighted``), on ``resample``'s own stream of draws."""
+        B = _tensor_arg("pw_resample_weighted", "puzzle_id", puzzle_id, torch.int32, (None,))[0]
+        _tensor_arg("pw_resample_weighted", "episode", episode, torch.int32, (B,))
+        _tensor_arg("pw_resample_weighted", "cdf", cdf, torch.uint64, (len(self.pset),))
+        if terminated is not None:
+            _tensor_arg("pw_resample_weighted", "terminated", terminated, torch.uint8, (B,))
+        if truncated is not None:
+            _tensor_arg("pw_resample_weighted", "truncated", truncated, torch.uint8, (B,))
+        check(lib.pw_resample_weighted(self.handle, _ptr(puzzle_id), _ptr(terminated), _ptr(truncated), _ptr(cdf),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(episode), B, self._stream()))
 
     def rollout(self, puzzle_id, actions, pos, steps, reward, dgoals, terminated, truncated, reward_hist=None,
                 terminated_hist=None, truncated_hist=None, flags=0):

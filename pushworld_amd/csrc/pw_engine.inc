@@ -671,6 +671,9 @@ int pw_engine_create(const PwPuzzleSet* s, const PwEngineConfig* cfg, PwEngine**
   e->search_chunk = 0;
   e->search_keys = 0;
   e->push_search_fp_bits = 0;
+  e->resample_fence = 0;
+  e->stats_lds_puzzles = 0;
+  e->stats_groups = 0;
   e->expand_pair_dims = 0;
   e->step_lds_tables = 0;
   e->step_wide_groups = 0;
@@ -2375,6 +2378,18 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
       e->ret.option = static_cast<int>(value);
       e->ret.valid = false;  // (established by the next full render)
       return PW_OK;
+    case PW_OPT_RESAMPLE_FENCE:
+      if (value != 0 && value != 1) return pw_fail(PW_EINVAL, "PW_OPT_RESAMPLE_FENCE: 0 the search reads the cdf alone, 1 a fence in LDS");
+      e->resample_fence = static_cast<int>(value);
+      return PW_OK;
+    case PW_OPT_STATS_LDS_PUZZLES:
+      if (value < 0 || (value > 1024 && value != 2048)) return pw_fail(PW_EINVAL, "PW_OPT_STATS_LDS_PUZZLES: 0 default, 1 .. 1024 puzzles, 2048 never");
+      e->stats_lds_puzzles = static_cast<int>(value);
+      return PW_OK;
+    case PW_OPT_STATS_GROUPS:
+      if (value < 0 || value > (1 << 20)) return pw_fail(PW_EINVAL, "PW_OPT_STATS_GROUPS: 0 one workgroup per 256 environments, or the most workgroups of a launch");
+      e->stats_groups = static_cast<int>(value);
+      return PW_OK;
     case PW_OPT_OBS_CHUNK_MB:
       if (value < 0 || value > 4096) return pw_fail(PW_EINVAL, "PW_OPT_OBS_CHUNK_MB: 0 (the default, 32 MiB) .. 4096");
       e->obs_chunk_mb = static_cast<int>(value);
@@ -2459,6 +2474,9 @@ int64_t pw_engine_get_option(const PwEngine* e, int32_t option) try {
     case PW_OPT_TUNED_NS: return e->tuned_ns;
     case PW_OPT_PAGE_LOAD_ALL: return e->page_load_all;
     case PW_OPT_OBS_PADDING_ONCE: return e->ret.option;
+    case PW_OPT_RESAMPLE_FENCE: return e->resample_fence;
+    case PW_OPT_STATS_LDS_PUZZLES: return e->stats_lds_puzzles;
+    case PW_OPT_STATS_GROUPS: return e->stats_groups;
     case PW_OPT_OBS_LIVE_PAGES: {
       if (!e->ret.valid) return 0;
       if (e->ret.n_live >= 0) return e->ret.n_live;

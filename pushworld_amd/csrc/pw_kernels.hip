@@ -175,6 +175,9 @@ struct PwEngine {
   int64_t page_slice_envs; // PW_OPT_PAGE_SLICE_ENVS: environments per page-kernel launch (0 = what 2^31 chunks allow)
   int64_t search_chunk;    // PW_OPT_SEARCH_CHUNK: parents per pw_search_expand pass (0 = 2^20)
   int search_keys;         // PW_OPT_SEARCH_KEYS: closed set of pw_search_*: 0 fingerprinted entries, 1 exact 63-bit keys where the state packs
+  int resample_fence;       // PW_OPT_RESAMPLE_FENCE: 1 pw_resample_weighted keeps a sampled fence of the cdf in LDS, 0 (default) not
+  int stats_lds_puzzles;    // PW_OPT_STATS_LDS_PUZZLES: largest set whose pw_episode_stats launch sums in LDS (0 default, 2048 never)
+  int stats_groups;         // PW_OPT_STATS_GROUPS: most workgroups of a pw_episode_stats launch (0: one per 256 environments)
   int push_search_fp_bits;  // PW_OPT_PUSH_SEARCH_FP_BITS: fingerprint bits of pw_push_search_create's closed set (0 = 32)
   int step_mixed;          // PW_OPT_STEP_MIXED_GROUPS: lanes per environment chosen per workgroup on N_pad 8 / 16 sets (0 auto, 2 never)
   int step_wide_groups;    // PW_OPT_STEP_WIDE_GROUPS: 32 lanes per environment for N_pad 32 instead of two movables per lane
@@ -457,4 +460,5 @@ struct PageRec {
 #include "pw_push_solution_batch.inc"
 #include "pw_push_planner.inc"
 #include "pw_push_plan_batch.inc"
+#include "pw_curriculum.inc"
 #include "pw_generate.inc"

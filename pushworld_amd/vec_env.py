@@ -72,7 +72,21 @@ class VecPushWorld:
             hold every environment.  Same results either way.
         engine_options: ``pw_engine_set_option`` settings (``_capi.OPTIONS``), e.g. ``{"step_kernel": "lane"}`` --
             kernel selection for tests and A/B runs; results never depend on them.
+        episode_stats: keep statistics per puzzle on the device (``curriculum.EpisodeStats``): one
+            ``pw_episode_stats`` launch follows the step launch of ``step`` / ``step_push`` / ``step_push_mask`` and counts
+            the episodes that step ended -- ``self.stats``, read with ``puzzle_stats()``.  Needs ``autoreset`` (without it a
+            finished environment keeps its flags and would be counted by every call); ``rollout`` and ``mailbox`` are refused while it is on: their steps cannot be observed.
+        curriculum: draw the puzzle of every new episode by weights made from those statistics
+            (``pw_resample_weighted``) instead of uniformly: a mode name ("uniform", "failure", "frontier", "given") or a
+            ``curriculum.Curriculum``.  Implies ``episode_stats``, needs ``resample=True``.  ``self.curriculum.update()``
+            refreshes the weights (one launch, no wait); until the first update the draw is uniform.
     """
+
+    # statistics per puzzle and the weighted draw (K25): off unless the constructor was asked for them
+    stats = None
+    curriculum = None
+    _call_stats = None
+    _call_resample_weighted = None
 
     def __init__(self, puzzles: Sequence[Union[str, PushWorldPuzzle]], num_envs: int,
                  puzzle_ids: Optional[Sequence[int]] = None, max_steps: Optional[int] = None,
@@ -80,7 +94,20 @@ class VecPushWorld:
                  observation: Optional[str] = "float32", pad_cells=None, device: Optional[int] = None,
                  autoreset: bool = False, fused: bool = True, resample=False, seed: int = 0,
                  incremental: bool = False, engine_options: Optional[dict] = None, tune: Optional[bool] = None,
-                 tune_allocations: Optional[int] = None, bind: Optional[bool] = None):
+                 tune_allocations: Optional[int] = None, bind: Optional[bool] = None, episode_stats: bool = False,
+                 curriculum=None):
+        # (the new options' refusals come first: nothing has been parsed or allocated yet)
+        if curriculum is not None:
+            if isinstance(curriculum, str) and curriculum not in _capi.CURRICULUM_MODES:
+                raise ValueError(f"curriculum must be one of {', '.join(_capi.CURRICULUM_MODES)} or a Curriculum, "
+                                 f"not {curriculum!r}")
+            if resample is not True:
+                raise ValueError("curriculum needs resample=True: it replaces the uniform draw of the next puzzle "
+                                 "(a sampling table has no place beside it)")
+            episode_stats = True
+        if episode_stats and not autoreset:
+            raise ValueError("episode_stats needs autoreset=True: without it a finished environment keeps its flags and "
+                             "would be counted by every step")
         if observation not in ("uint8", "float32", "cells", None):
             raise ValueError("observation must be 'uint8', 'float32', 'cells' or None")
         if observation == "cells" and (incremental or tune or tune_allocations):
@@ -224,6 +251,17 @@ class VecPushWorld:
             self._call_step_delta = self.engine.bind_step_render(
                 self.puzzle_id, self.pos, self.steps, self.reward, self.dgoals, self.terminated, self.truncated,
                 self._obs_storage, self.flags, delta=True)
+        # statistics per puzzle and the weighted draw (K25): nothing is allocated or launched unless they were asked for
+        if episode_stats:
+            from .curriculum import EpisodeStats, make_curriculum
+
+            self.stats = EpisodeStats(self.engine)
+            self._call_stats = self.engine.bind_episode_stats(self.puzzle_id, self.steps, self.terminated, self.truncated,
+                                                              self.stats.tensor)
+            self.curriculum = make_curriculum(self, curriculum)
+            if self.curriculum is not None:
+                self._call_resample_weighted = self.engine.bind_resample_weighted(
+                    self.puzzle_id, self.episode, self.curriculum.cdf, self.terminated, self.truncated)
 
     # --------------------------------------------------------------------------------
     @property
@@ -251,7 +289,9 @@ class VecPushWorld:
 
     def _reset_states(self, mask: Optional[torch.Tensor]) -> None:
         """``reset`` up to its render: the (masked) environments draw their puzzle and return to its initial state."""
-        if self.resample:
+        if self.curriculum is not None:
+            self.engine.resample_weighted(self.puzzle_id, self.episode, self.seed, self.curriculum.cdf, terminated=mask)
+        elif self.resample:
             self.engine.resample(self.puzzle_id, self.episode, self.seed, terminated=mask, table=self.sample_table)
         self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, mask)
         self._has_reset = True
@@ -279,12 +319,16 @@ class VecPushWorld:
         if actions.dtype != torch.uint8 or actions.device != self.device or actions.shape != self._act_shape \
                 or not actions.is_contiguous():
             raise ValueError("actions must be a contiguous uint8 tensor of shape [num_envs] on the engine's device")
-        if self.resample and self.flags & _capi.STEP_AUTORESET:
+        if self._call_resample_weighted is not None:
+            self._call_resample_weighted(self.seed)  # ... by the curriculum's weights
+        elif self.resample and self.flags & _capi.STEP_AUTORESET:
             # finished environments draw the puzzle their autoreset (inside this step) starts from
             self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
                                  self.sample_table)
         if self.obs is None:
             self._call_step(actions.data_ptr())  # one ctypes call with ready arguments: the launch is host bound
+            if self._call_stats is not None:
+                self._call_stats()
             return None, self.reward, self.terminated, self.truncated
         if self.observation == "cells":
             self._call_step_render(actions.data_ptr())  # pw_step_cells
@@ -295,6 +339,8 @@ class VecPushWorld:
         else:
             self._call_step(actions.data_ptr())
             self.engine.render(self.puzzle_id, self.pos, self._obs_storage)
+        if self._call_stats is not None:
+            self._call_stats()  # the episodes this step ended, per puzzle
         self._obs_current = True
         return self.obs, self.reward, self.terminated, self.truncated
 
@@ -306,6 +352,14 @@ class VecPushWorld:
     def counters_reset(self) -> None:
         self.engine.counters_reset()
 
+    def puzzle_stats(self):
+        """The statistics per puzzle kept on the device (``episode_stats=True`` / ``curriculum=...``): a
+        ``curriculum.PuzzleStats`` of numpy arrays -- ``episodes``, ``solved``, ``steps``, ``solved_steps``, ``success_rate``,
+        ``mean_steps``, one entry per puzzle of the pool.  Waits for the stream."""
+        if self.stats is None:
+            raise RuntimeError("this VecPushWorld keeps no statistics per puzzle (episode_stats=True or curriculum=...)")
+        return self.stats.read()
+
     def rollout(self, actions: torch.Tensor, history: bool = False):
         """T steps in ONE launch without observations (``pw_rollout``): ``actions`` is a uint8 tensor
         [T, B] on the device.  Same semantics as T calls of ``step`` with ``observation=None``.
@@ -313,6 +367,9 @@ class VecPushWorld:
         Returns ``(reward, terminated, truncated)`` of the last step, or, with ``history=True``,
         the per-step tensors of shape [T, B].
         """
+        if self.stats is not None:
+            raise RuntimeError("rollout() is not available while statistics per puzzle are kept (episode_stats / curriculum): "
+                               "the steps inside the launch cannot be observed; use step()")
         if not self._has_reset:
             raise RuntimeError("reset() must be called before step() can be called.")
         if actions.dtype != torch.uint8 or actions.device != self.device or actions.dim() != 2 \
@@ -338,6 +395,9 @@ class VecPushWorld:
         ``observation=None`` (this object's ``pos`` / ``steps`` / ``reward`` / ... tensors are kept up to date); state only, up to
         65 536 environments; ``step`` / ``rollout`` / ``reset`` of this object fail while it is open.  Bad
         actions are flagged 0xFF in ``terminated`` / ``truncated`` and counted (``counters()['bad_actions']``) as in ``step``."""
+        if self.stats is not None:
+            raise RuntimeError("mailbox() is not available while statistics per puzzle are kept (episode_stats / curriculum): "
+                               "the resident kernel's steps are not counted; use step()")
         if not self._has_reset:
             raise RuntimeError("reset() must be called before step() can be called.")
         self._obs_current = False
@@ -493,12 +553,16 @@ class VecPushWorld:
         if getattr(self, "push_status", None) is None:
             self.push_moves_taken = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
             self.push_status = torch.zeros((self.num_envs,), dtype=torch.int8, device=self.device)
-        if self.resample and self.flags & _capi.STEP_AUTORESET:
+        if self._call_resample_weighted is not None:
+            self._call_resample_weighted(self.seed)  # ... by the curriculum's weights
+        elif self.resample and self.flags & _capi.STEP_AUTORESET:
             # finished environments draw the puzzle their autoreset (inside this step) starts from
             self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
                                  self.sample_table)
         self.engine.step_push(self.puzzle_id, push_from, push_action, self.pos, self.steps, self.reward, self.dgoals,
                               self.terminated, self.truncated, self.push_moves_taken, self.push_status, self.flags)
+        if self._call_stats is not None:
+            self._call_stats()
         self._obs_current = False
         if self.obs is not None:
             self._render()
@@ -549,7 +613,9 @@ class VecPushWorld:
         if getattr(self, "push_status", None) is None:
             self.push_moves_taken = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
             self.push_status = torch.zeros((self.num_envs,), dtype=torch.int8, device=self.device)
-        if self.resample and self.flags & _capi.STEP_AUTORESET:
+        if self._call_resample_weighted is not None:
+            self._call_resample_weighted(self.seed)  # ... by the curriculum's weights
+        elif self.resample and self.flags & _capi.STEP_AUTORESET:
             # finished environments draw the puzzle their autoreset (inside this step) starts from
             self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
                                  self.sample_table)
@@ -558,6 +624,8 @@ class VecPushWorld:
                                    self.push_view_mask, self.push_view_count, self.push_walk_map, self.push_region_size,
                                    self._push_view_pos, self._push_view_id,
                                    self.flags | (_capi.PUSH_END_STUCK if end_stuck else 0))
+        if self._call_stats is not None:
+            self._call_stats()
         self._obs_current = False
         if self.obs is not None:
             self._render()

@@ -66,7 +66,13 @@ def _load_pool(puzzle_path, standard_padding: bool):
 class _VectorCore:
     def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int], border_width: int, pixels_per_cell: int,
                  standard_padding: bool, observation: str, seed: int, sample_table, device: Optional[int],
-                 to_numpy: bool, incremental: bool = True):
+                 to_numpy: bool, incremental: bool = True, curriculum=None, curriculum_update_every: Optional[int] = None):
+        if curriculum_update_every is not None:
+            if curriculum is None:
+                raise ValueError("curriculum_update_every needs a curriculum")
+            if isinstance(curriculum_update_every, bool) or not isinstance(curriculum_update_every, int) \
+                    or curriculum_update_every < 1:
+                raise ValueError("curriculum_update_every must be None or an integer >= 1")
         if border_width < 1:
             raise ValueError("border_width must be >= 1")
         if pixels_per_cell < 3:
@@ -78,7 +84,11 @@ class _VectorCore:
         self.vec = VecPushWorld(puzzles, num_envs, max_steps=max_steps, border_width=border_width,
                                 pixels_per_cell=pixels_per_cell, observation=observation, pad_cells=pad,
                                 device=device, autoreset=True, resample=True if sample_table is None else sample_table,
-                                seed=seed, incremental=incremental and not cells)
+                                seed=seed, incremental=incremental and not cells, curriculum=curriculum)
+        # steps counted on the host (no wait): after every `curriculum_update_every`-th step the weights are made anew from the
+        # statistics that step left, so the draws of the following step are the first to use them
+        self.curriculum_update_every = curriculum_update_every
+        self._steps_to_update = curriculum_update_every
         self.num_envs = int(num_envs)
         self.to_numpy = bool(to_numpy)
         self._obs_dtype = np.float32 if observation == "float32" else np.uint8
@@ -95,6 +105,22 @@ class _VectorCore:
     @property
     def puzzles(self):
         return self.vec.puzzles
+
+    @property
+    def curriculum(self):
+        """The ``curriculum.Curriculum`` the puzzles are drawn by (None: uniformly or from the sample table)."""
+        return self.vec.curriculum
+
+    def puzzle_stats(self):
+        """``VecPushWorld.puzzle_stats``: the statistics per puzzle kept on the device (needs ``curriculum``).  Waits."""
+        return self.vec.puzzle_stats()
+
+    def _count_step(self) -> None:
+        if self._steps_to_update is not None:
+            self._steps_to_update -= 1
+            if self._steps_to_update == 0:
+                self.vec.curriculum.update()
+                self._steps_to_update = self.curriculum_update_every
 
     @property
     def puzzle_ids(self) -> torch.Tensor:
@@ -126,6 +152,7 @@ class _VectorCore:
         if self._pending:
             raise RuntimeError("step_async() was called twice without step_wait()")
         self.vec.step(self._actions(actions))  # asynchronous on the current HIP stream
+        self._count_step()
         self._pending = True
 
     def _collect(self):
@@ -163,6 +190,10 @@ class PushWorldVectorEnv(_VectorCore):
             cell-grid observation uint8 [B, 3, Hc, Wc]; ``render()`` still returns RGB frames).
         seed: seed of the per-episode puzzle draw.
         sample_table: optional pool indices to draw from (repeats = weights); default uniform.
+        curriculum: draw by weights made on the device from the statistics per puzzle: a mode name
+            ("uniform", "failure", "frontier", "given") or a ``curriculum.Curriculum``; not together with ``sample_table``.
+            ``puzzle_stats()`` reads the statistics, ``curriculum.update()`` refreshes the weights.
+        curriculum_update_every: refresh the weights after every that many steps (counted on the host: no wait).
         to_numpy: return host numpy arrays (and python-side checks) instead of device tensors.
     """
 
@@ -172,9 +203,11 @@ class PushWorldVectorEnv(_VectorCore):
     def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int] = None,
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
-                 device: Optional[int] = None, to_numpy: bool = False):
+                 device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
+                 curriculum_update_every: Optional[int] = None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
-                         observation, seed, sample_table, device, to_numpy)
+                         observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
+                         curriculum_update_every=curriculum_update_every)
         self.single_action_space = _compat.make_discrete(NUM_ACTIONS)
         self.single_observation_space = _compat.make_box(0, self._obs_high, self._obs_shape, self._obs_dtype)
         self.action_space = _BatchSpace(_compat.Discrete(NUM_ACTIONS), num_envs)
@@ -231,9 +264,11 @@ class PushWorldDmVectorEnv(_VectorCore):
     def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int] = None,
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
-                 device: Optional[int] = None, to_numpy: bool = False):
+                 device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
+                 curriculum_update_every: Optional[int] = None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
-                         observation, seed, sample_table, device, to_numpy)
+                         observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
+                         curriculum_update_every=curriculum_update_every)
         self._action_spec = _compat.make_discrete_array(NUM_ACTIONS, int, "action")
         self._observation_spec = _compat.make_bounded_array(self._obs_shape, self._obs_dtype, "board", 0,
                                                             self._obs_high)
@@ -283,8 +318,8 @@ def push_action_spaces(map_h: int, map_w: int, num_envs: int):
 class _PushCore(_VectorCore):
     """The core of the push-mode facades: every step is ONE ``VecPushWorld.step_push_mask(choice=..., end_stuck=True)``."""
 
-    def __init__(self, *args):
-        super().__init__(*args)
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
         v = self.vec
         self.map_h, self.map_w = v.pset.max_height, v.pset.max_width
         self.num_choices = 4 * self.map_h * self.map_w
@@ -318,6 +353,7 @@ class _PushCore(_VectorCore):
         could = v.push_view_count > 0
         self._step = v.step_push_mask(choice=choice, end_stuck=True)  # asynchronous on the current HIP stream
         self._refused += ((self._step.status == _capi.PUSH_REFUSED) & could).sum()
+        self._count_step()
         self._pending = True
 
     def _collect(self):
@@ -370,9 +406,11 @@ class PushWorldPushVectorEnv(_PushCore):
     def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int] = None,
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
-                 device: Optional[int] = None, to_numpy: bool = False):
+                 device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
+                 curriculum_update_every: Optional[int] = None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
-                         observation, seed, sample_table, device, to_numpy)
+                         observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
+                         curriculum_update_every=curriculum_update_every)
         self.single_action_space, self.action_space = push_action_spaces(self.map_h, self.map_w, num_envs)
         self.single_observation_space = _compat.make_box(0, self._obs_high, self._obs_shape, self._obs_dtype)
         self.observation_space = _BatchSpace(_compat.Box(0, self._obs_high, self._obs_shape, self._obs_dtype),
@@ -421,9 +459,11 @@ class PushWorldPushDmVectorEnv(_PushCore):
     def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int] = None,
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
-                 device: Optional[int] = None, to_numpy: bool = False):
+                 device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
+                 curriculum_update_every: Optional[int] = None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
-                         observation, seed, sample_table, device, to_numpy)
+                         observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
+                         curriculum_update_every=curriculum_update_every)
         self._action_spec = _compat.make_discrete_array(self.num_choices, int, "action")
         self._observation_spec = {
             "board": _compat.make_bounded_array(self._obs_shape, self._obs_dtype, "board", 0, self._obs_high),
