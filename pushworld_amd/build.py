@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libpushworld_amd.so")
 SOURCES = ["pw_host.cpp", "pw_kernels.hip"]
-HEADERS = ["pw_host.h", "pw_format.h", "pw_zone.h", "pw_device_guard.h", "pw_search.inc", "pw_solution.inc", "pw_solution_batch.inc", "pw_table_sample.inc", "pw_rgd.inc", "pw_planner.inc", "pw_plan_batch.inc", "pw_plan_replay.inc", "pw_walk.inc", "pw_push_step.inc", "pw_push_env.inc", "pw_push_unroll.inc", "pw_push_search.inc", "pw_push_table.inc", "pw_push_table_sample.inc", "pw_push_solution_batch.inc", "pw_push_planner.inc", "pw_push_plan_batch.inc", "pw_curriculum.inc", "pw_generate.inc", "pw_step_kernels.inc", "pw_seg_kernels.inc", "pw_mailbox_kernels.inc", "pw_expand_kernels.inc", "pw_mailbox.inc", "pw_render_kernels.inc",
-           "pw_cells_kernels.inc", "pw_engine.inc", "pw_cells.inc", os.path.join("..", "..", "include", "pushworld_amd.h")]
+# what the library is built from besides SOURCES: every header and include file of csrc/, and the public header
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join("..", "..", "include", "pushworld_amd.h")]
 ARCH = "gfx950"
 
 

@@ -28,12 +28,6 @@ const uint8_t kPaletteRGB[PW_NUM_COLORS][3] = {
     {0xB9, 0x00, 0x00},  // GOAL_BORDER          :73
 };
 
-int check_launch(const char* what) {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pw_fail(PW_EDEVICE, std::string(what) + ": " + hipGetErrorString(err));
-  return PW_OK;
-}
-
 int fill_render_args(const PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* obs, int64_t stride,
                      int32_t batch, RenderArgs* ra) {
   if (!puzzle_id || !pos || !obs) return pw_fail(PW_EINVAL, "null device pointer");

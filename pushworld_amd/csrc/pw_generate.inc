@@ -580,10 +580,7 @@ int pw_puzzleset_from_grids(int device, const uint8_t* grids, const int32_t* dim
   if (err == hipSuccess) err = hipMemcpyAsync(s->headers.data(), s->d_headers, hb, hipMemcpyDeviceToHost, st);
   if (err == hipSuccess) err = hipMemcpyAsync(s->blob.data(), s->d_blob, bb, hipMemcpyDeviceToHost, st);
   if (err == hipSuccess) err = hipStreamSynchronize(st);
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_puzzleset_from_grids: ") + hipGetErrorString(err);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
-  }
+  if (err != hipSuccess) return pw_hip_fail("pw_puzzleset_from_grids", err);
   for (int32_t i = 0; i < count; i++)
     if (status[i] != PW_OK) {
       const int code = status[i];

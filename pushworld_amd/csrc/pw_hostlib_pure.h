@@ -1,0 +1,31 @@
+// pw_hostlib_pure.h -- the arithmetic of the host plumbing (pw_hostlib.inc).  No HIP, no engine: a stand-alone host program
+// compiles this header alone (tests/hostlib_pure_main.cpp).
+#ifndef PW_HOSTLIB_PURE_H
+#define PW_HOSTLIB_PURE_H
+
+#include <algorithm>
+#include <cstdint>
+
+// v rounded up to the 256-byte granule of every slab field
+inline uint64_t pw_pad256(uint64_t v) { return (v + 255u) & ~uint64_t(255); }
+
+// slots of a closed set that stays at most half full: the smallest power of two >= 2 * max_states
+inline uint64_t pw_table_slots(uint64_t max_states) {
+  uint64_t slots = 1;
+  while (slots < 2ull * max_states) slots <<= 1;
+  return slots;
+}
+
+// a time limit in seconds as wall-clock ticks of a kernel: 0 = no limit, at least 1 otherwise, ~0 where the product leaves
+// 64 bits (+inf included)
+inline unsigned long long pw_deadline_ticks(double time_limit, uint32_t clock_khz) {
+  if (!(time_limit > 0.0)) return 0ull;
+  const double ticks = time_limit * static_cast<double>(clock_khz) * 1000.0;
+  if (ticks >= 1.8e19) return ~0ull;
+  return std::max<unsigned long long>(1ull, static_cast<unsigned long long>(ticks));
+}
+
+// the padded movable counts of the position layouts
+inline bool pw_npad_ok(int npad) { return !(npad != 4 && npad != 8 && npad != 16 && npad != 32); }
+
+#endif  // PW_HOSTLIB_PURE_H

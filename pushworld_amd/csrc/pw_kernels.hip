@@ -434,6 +434,7 @@ struct PageRec {
   uint64_t rows;  // bit y: some movable's bounding box covers grid row y
 };
 
+#include "pw_hostlib.inc"
 #include "pw_step_kernels.inc"
 #include "pw_mailbox_kernels.inc"
 #include "pw_expand_kernels.inc"

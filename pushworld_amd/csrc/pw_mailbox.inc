@@ -137,9 +137,7 @@ int pw_mailbox_open(PwEngine* e, const int32_t* puzzle_id, int8_t* pos, int32_t*
   // action addresses included: a wavefront that met such a word before the fill read its actions from an address that is gone
   // (a memory access fault in one bench run of this round, at a host address)
   if (hipMemsetAsync(m->d_arrive, 0, dev_bytes, m->stream) != hipSuccess) return fail(PW_EDEVICE, "pw_mailbox_open: hipMemsetAsync failed");
-  int khz = 0;
-  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, e->set->device) != hipSuccess || khz <= 0) khz = 100000;  // (100 MHz)
-  m->clock_khz = khz;
+  m->clock_khz = pw_wall_clock_khz(e->set->device);
   MailboxArgs k;
   k.s = a;
   k.slots = reinterpret_cast<const unsigned long long*>(m->dev + m->off_slots);
@@ -158,7 +156,7 @@ int pw_mailbox_open(PwEngine* e, const int32_t* puzzle_id, int8_t* pos, int32_t*
   k.waves = groups * 4u;
   k.groups = groups;
   const unsigned grid = groups + ((k.mode & 3u) == 3u ? 1u : 0u) + ((k.mode & 11u) == 11u ? 1u : 0u);  // (+ the relay, + the publisher)
-  k.idle_ticks = static_cast<unsigned long long>(khz) * static_cast<unsigned long long>(idle_ms);
+  k.idle_ticks = static_cast<unsigned long long>(m->clock_khz) * static_cast<unsigned long long>(idle_ms);
   // (the caller's stream order ends here: what it queued on its stream for these arrays must be complete -- the wrappers
   // synchronise their stream before they open a mailbox)
   // sets of 8 x 8 puzzles: the whole-grid boards (what pw_step launches for them); any other set: one lane per environment

@@ -502,13 +502,10 @@ struct PwPlanBatch {
   int32_t* d_slot_of;  // [set count] the first item of each set index, -1 = none (the states form)
   int32_t max_n;       // the largest prepared puzzle's movables
   uint8_t* d_groups;
-  uint8_t* d_slab;     // counter (256 B), then `groups` slabs
-  int64_t groups;
+  PwSlabPool pool;
   PbArgs args;         // everything but the per-run fields
   size_t lds;
-  int64_t* h_cancel;   // pinned, mapped
-  int64_t* d_cancel;
-  int64_t seq;
+  PwCancelWord cancel;
   uint64_t tags_used;
 };
 
@@ -516,11 +513,12 @@ extern "C" {
 
 void pw_plan_batch_destroy(PwPlanBatch* b) {
   if (!b) return;
+  PwDeviceGuard guard(b->eng->set->device);
   if (b->d_items) (void)hipFree(b->d_items);
   if (b->d_slot_of) (void)hipFree(b->d_slot_of);
   if (b->d_groups) (void)hipFree(b->d_groups);
-  if (b->d_slab) (void)hipFree(b->d_slab);
-  if (b->h_cancel) (void)hipHostFree(b->h_cancel);
+  if (b->pool.d_slab) (void)hipFree(b->pool.d_slab);
+  cancel_word_destroy(&b->cancel);
   for (PwRgd* r : b->rgd) pw_rgd_destroy(r);
   delete b;
 }
@@ -539,10 +537,7 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
   if (n < 1) return pw_fail(PW_EINVAL, "n must be >= 1");
   if (!e || !out) return pw_fail(PW_EINVAL, "null argument");
   *out = nullptr;
-  for (int32_t i = 0; i < n; i++) {
-    const int32_t pid = puzzles ? puzzles[i] : i;
-    if (pid < 0 || pid >= e->set->count) return pw_fail(PW_EINVAL, "puzzle index out of range");
-  }
+  if (!pw_puzzles_ok(e, puzzles, n)) return pw_fail(PW_EINVAL, "puzzle index out of range");
   PwPlanBatch* b = new (std::nothrow) PwPlanBatch();
   if (!b) return pw_fail(PW_ENOMEM, "out of memory");
   b->eng = e;
@@ -580,8 +575,7 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
     levels = std::max(levels, std::max(h.N - 2, 1));
   }
   b->max_n = max_n;
-  std::vector<int32_t> slot_of(static_cast<size_t>(e->set->count), -1);
-  for (int32_t i = n - 1; i >= 0; i--) slot_of[static_cast<size_t>(items[static_cast<size_t>(i)].pid)] = i;  // the first wins
+  const std::vector<int32_t> slot_of = pw_slot_of(items, e->set->count);
   PbArgs& a = b->args;
   std::memset(static_cast<void*>(&a), 0, sizeof(a));
   a.hdrs = e->set->d_headers;
@@ -594,81 +588,54 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
   a.nb = (mode == PW_PLAN_RGD ? b->cost_range : 3u * b->cost_range) + 2u;
   a.n0 = (a.nb + 63u) / 64u;
   a.n1 = (a.n0 + 63u) / 64u;
-  uint64_t slots = 1;
-  while (slots < 2ull * static_cast<uint64_t>(max_states)) slots <<= 1;
+  const uint64_t ms = static_cast<uint64_t>(max_states), slots = pw_table_slots(ms);
   a.slot_mask = static_cast<uint32_t>(slots - 1u);
   a.nw = (max_n + 1) / 2;
   a.levels = levels;
-  const uint64_t ms = static_cast<uint64_t>(max_states);
-  auto al = [](uint64_t v) { return (v + 255u) & ~uint64_t(255); };
-  uint64_t off = al(ms * a.nw * 4);
+  uint64_t off = pw_pad256(ms * a.nw * 4);
   a.off_parent = off;
-  off += al(ms * 4);
+  off += pw_pad256(ms * 4);
   a.off_action = off;
-  off += al(ms);
+  off += pw_pad256(ms);
   a.off_next = off;
-  off += al(ms * 4);
+  off += pw_pad256(ms * 4);
   a.off_table = off;
-  off += al(slots * 8);
+  off += pw_pad256(slots * 8);
   a.off_head = off;
-  off += al(static_cast<uint64_t>(a.nb) * 4);
+  off += pw_pad256(static_cast<uint64_t>(a.nb) * 4);
   a.off_bits0 = off;
-  off += al(static_cast<uint64_t>(a.n0) * 8);
+  off += pw_pad256(static_cast<uint64_t>(a.n0) * 8);
   a.off_bits1 = off;
-  off += al(static_cast<uint64_t>(a.n1) * 8);
+  off += pw_pad256(static_cast<uint64_t>(a.n1) * 8);
   a.off_cand = off;
-  off += al(4ull * kPbMaxK * a.nw * 4);
+  off += pw_pad256(4ull * kPbMaxK * a.nw * 4);
   a.off_nov = off;
-  off += al(static_cast<uint64_t>(nov_words) * 4);
+  off += pw_pad256(static_cast<uint64_t>(nov_words) * 4);
   a.slab_bytes = off;
   b->lds = static_cast<size_t>(PW_WAVE) * (16 * levels + 2 * 32);
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
-  // persistent workgroups: one per item up to two per CU, fewer when the slabs would not fit a quarter of the free memory
-  size_t free_b = 0, total_b = 0;
-  if (err == hipSuccess && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0)) free_b = total_b / 2;
-  b->groups = std::min<int64_t>(n, 2ll * e->num_cus);
-  b->groups = std::max<int64_t>(1, std::min<int64_t>(b->groups, static_cast<int64_t>(free_b / 4 / a.slab_bytes)));
-  auto alloc = [&](void* ptr, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(ptr), bytes);
-  };
-  alloc(&b->d_items, sizeof(PbItem) * static_cast<size_t>(n));
-  alloc(&b->d_slot_of, sizeof(int32_t) * slot_of.size());
-  alloc(&b->d_groups, kPlanGroups);
-  alloc(&b->d_slab, 256 + static_cast<size_t>(b->groups) * static_cast<size_t>(a.slab_bytes));
-  if (err == hipSuccess) err = hipHostMalloc(reinterpret_cast<void**>(&b->h_cancel), 64, hipHostMallocMapped);
-  if (err == hipSuccess) {
-    *b->h_cancel = 0;
-    err = hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_cancel), b->h_cancel, 0);
-  }
-  if (err == hipSuccess) err = hipMemcpy(b->d_items, items.data(), sizeof(PbItem) * static_cast<size_t>(n), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(b->d_slot_of, slot_of.data(), sizeof(int32_t) * slot_of.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess) {
-    uint8_t packed[kPlanGroups];
-    uint8_t raw[4 * kPlanGroups];
-    plan_action_groups(raw);
-    for (int g = 0; g < kPlanGroups; g++)
-      packed[g] = static_cast<uint8_t>(raw[4 * g] | (raw[4 * g + 1] << 2) | (raw[4 * g + 2] << 4) | (raw[4 * g + 3] << 6));
-    err = hipMemcpy(b->d_groups, packed, kPlanGroups, hipMemcpyHostToDevice);
-  }
-  if (err == hipSuccess)  // tag 0 is no puzzle's: the tables start empty
-    err = hipMemset(b->d_slab, 0, 256 + static_cast<size_t>(b->groups) * static_cast<size_t>(a.slab_bytes));
-  int khz = 0;
-  if (err == hipSuccess) err = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, e->set->device);
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_plan_batch_create: ") + hipGetErrorString(err);
+  PwHipChain c(guard.status());
+  slab_pool_create(&b->pool, c, n, e->num_cus, a.slab_bytes);
+  c.alloc(&b->d_items, sizeof(PbItem) * items.size());
+  c.alloc(&b->d_slot_of, sizeof(int32_t) * slot_of.size());
+  c.alloc(&b->d_groups, kPlanGroups);
+  cancel_word_create(&b->cancel, c);
+  c.then([&] { return hipMemcpy(b->d_items, items.data(), sizeof(PbItem) * items.size(), hipMemcpyHostToDevice); });
+  c.then([&] { return hipMemcpy(b->d_slot_of, slot_of.data(), sizeof(int32_t) * slot_of.size(), hipMemcpyHostToDevice); });
+  c.then([&] { return plan_upload_groups(b->d_groups); });
+  c.then([] { return hipDeviceSynchronize(); });
+  if (!c.ok()) {
     pw_plan_batch_destroy(b);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_plan_batch_create", c.err);
   }
   a.items = b->d_items;
   a.slot_of = b->d_slot_of;
   a.set_count = e->set->count;
   a.groups = flags == PW_PLAN_ACTIONS_FIXED ? nullptr : b->d_groups;
-  a.slab = b->d_slab + 256;
-  a.next_item = reinterpret_cast<uint32_t*>(b->d_slab);
-  a.cancel = b->d_cancel;
-  a.clock_khz = khz > 0 ? static_cast<uint32_t>(khz) : 100000u;
+  a.slab = b->pool.slabs();
+  a.next_item = b->pool.counter();
+  a.cancel = b->cancel.d;
+  a.clock_khz = pw_wall_clock_khz(e->set->device);
   b->tags_used = 0;
   *out = b;
   return PW_OK;
@@ -682,7 +649,7 @@ int pw_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, int32_t
 static int pb_launch(PwPlanBatch* b, PbArgs& a, int32_t n, int64_t max_rounds, double time_limit, int64_t* info,
                      uint8_t* plans, int32_t* plan_len, int32_t plan_cap, hipStream_t st, const char* what) {
   if (b->tags_used + static_cast<uint64_t>(n) >= 0xFFFFFFFFull) {  // tags would wrap: empty the slabs once more
-    if (hipMemsetAsync(a.slab, 0, static_cast<size_t>(b->groups) * static_cast<size_t>(a.slab_bytes), st) != hipSuccess)
+    if (hipMemsetAsync(a.slab, 0, static_cast<size_t>(b->pool.groups) * static_cast<size_t>(a.slab_bytes), st) != hipSuccess)
       return pw_fail(PW_EDEVICE, std::string(what) + ": hipMemsetAsync failed");
     b->tags_used = 0;
   }
@@ -690,49 +657,16 @@ static int pb_launch(PwPlanBatch* b, PbArgs& a, int32_t n, int64_t max_rounds, d
   a.tag_base = static_cast<uint32_t>(b->tags_used + 1u);
   b->tags_used += static_cast<uint64_t>(n);
   a.max_rounds = max_rounds;
-  const double ticks = time_limit * static_cast<double>(a.clock_khz) * 1000.0;
-  a.time_ticks = time_limit > 0.0 ? (ticks >= 1.8e19 ? ~0ull : std::max<unsigned long long>(1ull, static_cast<unsigned long long>(ticks))) : 0ull;
-  a.seq = ++b->seq;
+  a.time_ticks = pw_deadline_ticks(time_limit, a.clock_khz);
+  a.seq = ++b->cancel.seq;
   a.info = info;
   a.plans = plans;
   a.plan_len = plan_len;
   a.plan_cap = plans ? plan_cap : 0;
   if (hipMemsetAsync(a.next_item, 0, 4, st) != hipSuccess) return pw_fail(PW_EDEVICE, std::string(what) + ": hipMemsetAsync failed");
-  const int64_t groups = std::min<int64_t>(b->groups, n);
+  const int64_t groups = std::min<int64_t>(b->pool.groups, n);
   hipLaunchKernelGGL(pw_plan_batch_kernel, dim3(static_cast<unsigned>(groups)), dim3(PW_WAVE), b->lds, st, a);
   return check_launch(what);
-}
-
-// the states form's runs may hold more items than the handle prepared puzzles: up to two workgroups per CU as memory allows.
-// Replacing the slabs waits for the device once (a launch in flight on any stream still uses the old ones).
-static int pb_grow(PwPlanBatch* b, int32_t n) {
-  const int64_t want = std::min<int64_t>(n, 2ll * b->eng->num_cus);
-  if (want <= b->groups) return PW_OK;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return PW_OK;  // (keep what there is)
-  const uint64_t slab = b->args.slab_bytes;
-  const int64_t fit = static_cast<int64_t>((free_b + static_cast<uint64_t>(b->groups) * slab) / 4 / slab);
-  const int64_t groups = std::min<int64_t>(want, fit);
-  if (groups <= b->groups) return PW_OK;
-  uint8_t* fresh = nullptr;
-  const size_t bytes = 256 + static_cast<size_t>(groups) * static_cast<size_t>(slab);
-  if (hipMalloc(reinterpret_cast<void**>(&fresh), bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return PW_OK;  // (the launch runs on the workgroups it has)
-  }
-  hipError_t err = hipDeviceSynchronize();
-  if (err == hipSuccess) err = hipMemset(fresh, 0, bytes);  // tag 0 is no item's: the tables start empty
-  if (err == hipSuccess) err = hipFree(b->d_slab);
-  if (err != hipSuccess) {
-    (void)hipFree(fresh);
-    return pw_fail(PW_EDEVICE, std::string("pw_plan_batch_run_states: ") + hipGetErrorString(err));
-  }
-  b->d_slab = fresh;
-  b->groups = groups;
-  b->args.slab = fresh + 256;
-  b->args.next_item = reinterpret_cast<uint32_t*>(fresh);
-  b->tags_used = 0;
-  return PW_OK;
 }
 
 extern "C" {
@@ -755,7 +689,7 @@ int pw_plan_batch_run_states(PwPlanBatch* b, const int32_t* puzzle_id, const int
                              int32_t* plan_len, int32_t plan_cap, int8_t* first_action, void* stream) try {
   // (every check but the last needs no handle)
   if (n < 1) return pw_fail(PW_EINVAL, "n must be >= 1");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, "npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad("", npad)) return rc;
   if (!puzzle_id || !pos || !info) return pw_fail(PW_EINVAL, "null argument (puzzle_id, pos and info are required)");
   if (!(time_limit >= 0.0)) return pw_fail(PW_EINVAL, "time_limit must be >= 0 seconds (0 = none)");
   if (plans && (!plan_len || plan_cap < 1)) return pw_fail(PW_EINVAL, "plans need plan_len and plan_cap >= 1");
@@ -763,7 +697,13 @@ int pw_plan_batch_run_states(PwPlanBatch* b, const int32_t* puzzle_id, const int
   if (npad < b->max_n) return pw_fail(PW_EINVAL, "npad is smaller than the largest prepared puzzle's number of movables");
   PwDeviceGuard guard(b->eng->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int rc = pb_grow(b, n)) return rc;
+  bool replaced = false;
+  if (int rc = slab_pool_grow(&b->pool, n, b->eng->num_cus, "pw_plan_batch_run_states", &replaced)) return rc;
+  if (replaced) {
+    b->args.slab = b->pool.slabs();
+    b->args.next_item = b->pool.counter();
+    b->tags_used = 0;
+  }
   PbArgs a = b->args;
   a.state_pid = puzzle_id;
   a.state_pos = pos;
@@ -777,7 +717,7 @@ int pw_plan_batch_run_states(PwPlanBatch* b, const int32_t* puzzle_id, const int
 
 int pw_plan_batch_cancel(PwPlanBatch* b) try {
   if (!b) return pw_fail(PW_EINVAL, "null argument");
-  __atomic_store_n(b->h_cancel, b->seq, __ATOMIC_RELEASE);  // every launch made so far
+  cancel_word_cancel(&b->cancel);
   return PW_OK;
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI

@@ -252,7 +252,7 @@ static int replay_check_args(const PwEngine* e, const int32_t* puzzle_id, int32_
                              const int64_t* offset, int64_t cap, const char* what) {
   const std::string w = std::string(what) + ": ";
   if (n < 1) return pw_fail(PW_EINVAL, w + "n must be >= 1");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, w + "npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad(w, npad)) return rc;
   if (!puzzle_id) return pw_fail(PW_EINVAL, w + "null puzzle_id");
   if (!plans) return pw_fail(PW_EINVAL, w + "null plans");
   if (!plan_len) return pw_fail(PW_EINVAL, w + "null plan_len");
@@ -307,7 +307,7 @@ int pw_plan_replay_check(PwEngine* e, const int32_t* puzzle_id, const int8_t* po
   hipError_t err = rocprim::exclusive_scan(nullptr, scan_bytes, offset, offset, static_cast<int64_t>(0), count,
                                            rocprim::plus<int64_t>(), st);
   if (err != hipSuccess) return pw_fail(PW_EDEVICE, std::string("pw_plan_replay_check: ") + hipGetErrorString(err));
-  scan_bytes = (scan_bytes + 255) & ~static_cast<size_t>(255);
+  scan_bytes = pw_pad256(scan_bytes);
   if (int rc = replay_workspace(e, scan_bytes, "pw_plan_replay_check")) return rc;
   ReplayArgs a{};
   a.puzzle_id = puzzle_id;

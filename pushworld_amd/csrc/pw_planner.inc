@@ -341,6 +341,16 @@ static void plan_action_groups(uint8_t* out) {  // RandomActionIterator(1000): r
   }
 }
 
+// the groups packed two bits per action, on the device (kPlanGroups bytes)
+static hipError_t plan_upload_groups(uint8_t* d_groups) {
+  uint8_t packed[kPlanGroups];
+  uint8_t raw[4 * kPlanGroups];
+  plan_action_groups(raw);
+  for (int g = 0; g < kPlanGroups; g++)
+    packed[g] = static_cast<uint8_t>(raw[4 * g] | (raw[4 * g + 1] << 2) | (raw[4 * g + 2] << 4) | (raw[4 * g + 3] << 6));
+  return hipMemcpy(d_groups, packed, kPlanGroups, hipMemcpyHostToDevice);
+}
+
 static BfsPlanArgs plan_args(PwPlanner* p) {
   BfsPlanArgs a;
   a.info = p->d_info;
@@ -448,53 +458,43 @@ int pw_planner_create(PwEngine* e, int32_t puzzle, int32_t mode, int64_t max_sta
   p->q.n1 = (p->q.n0 + 63u) / 64u;
   p->q.n2 = (p->q.n1 + 63u) / 64u;
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
-  auto alloc = [&](void* ptr, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(ptr), bytes);
-  };
+  PwHipChain c(guard.status());
   const size_t ms = static_cast<size_t>(max_states);
-  alloc(&p->q.head, static_cast<size_t>(p->q.nb) * 4);
-  alloc(&p->q.bits0, static_cast<size_t>(p->q.n0) * 8);
-  alloc(&p->q.bits1, static_cast<size_t>(p->q.n1) * 8);
-  alloc(&p->q.bits2, static_cast<size_t>(p->q.n2) * 8);
-  alloc(&p->q.seg_start, ms * 4);
-  alloc(&p->q.seg_len, ms * 4);
-  alloc(&p->q.seg_next, ms * 4);
-  alloc(&p->q.ent, ms * 4);
-  alloc(&p->d_info, kPSlots * 8);
-  alloc(&p->d_plist, static_cast<size_t>(batch) * 4);
-  alloc(&p->d_pperm, static_cast<size_t>(batch));
-  alloc(&p->d_groups, kPlanGroups);
-  alloc(&p->d_rsrc, static_cast<size_t>(batch) * 4);
-  alloc(&p->d_rlen, static_cast<size_t>(batch) * 4);
-  alloc(&p->d_roff, static_cast<size_t>(batch) * 4);
-  alloc(&p->d_rows, static_cast<size_t>(slots) * h.N * 4);
-  alloc(&p->d_cost, static_cast<size_t>(slots) * 4);
+  c.alloc(&p->q.head, static_cast<size_t>(p->q.nb) * 4);
+  c.alloc(&p->q.bits0, static_cast<size_t>(p->q.n0) * 8);
+  c.alloc(&p->q.bits1, static_cast<size_t>(p->q.n1) * 8);
+  c.alloc(&p->q.bits2, static_cast<size_t>(p->q.n2) * 8);
+  c.alloc(&p->q.seg_start, ms * 4);
+  c.alloc(&p->q.seg_len, ms * 4);
+  c.alloc(&p->q.seg_next, ms * 4);
+  c.alloc(&p->q.ent, ms * 4);
+  c.alloc(&p->d_info, kPSlots * 8);
+  c.alloc(&p->d_plist, static_cast<size_t>(batch) * 4);
+  c.alloc(&p->d_pperm, static_cast<size_t>(batch));
+  c.alloc(&p->d_groups, kPlanGroups);
+  c.alloc(&p->d_rsrc, static_cast<size_t>(batch) * 4);
+  c.alloc(&p->d_rlen, static_cast<size_t>(batch) * 4);
+  c.alloc(&p->d_roff, static_cast<size_t>(batch) * 4);
+  c.alloc(&p->d_rows, static_cast<size_t>(slots) * h.N * 4);
+  c.alloc(&p->d_cost, static_cast<size_t>(slots) * 4);
   for (int k = 0; k < 2; k++) {
-    alloc(&p->d_keys[k], static_cast<size_t>(slots) * 4);
-    alloc(&p->d_vals[k], static_cast<size_t>(slots) * 4);
+    c.alloc(&p->d_keys[k], static_cast<size_t>(slots) * 4);
+    c.alloc(&p->d_vals[k], static_cast<size_t>(slots) * 4);
   }
-  if (err == hipSuccess)
-    err = rocprim::radix_sort_pairs(nullptr, p->sort_tmp_bytes, p->d_keys[0], p->d_keys[1], p->d_vals[0], p->d_vals[1],
-                                    static_cast<size_t>(slots), 0, kPlanSortBits, nullptr);
-  alloc(&p->d_sort_tmp, std::max<size_t>(p->sort_tmp_bytes, 16));
+  c.then([&] {
+    return rocprim::radix_sort_pairs(nullptr, p->sort_tmp_bytes, p->d_keys[0], p->d_keys[1], p->d_vals[0], p->d_vals[1],
+                                     static_cast<size_t>(slots), 0, kPlanSortBits, nullptr);
+  });
+  c.alloc(&p->d_sort_tmp, std::max<size_t>(p->sort_tmp_bytes, 16));
   if (mode == PW_PLAN_N_RGD) {
-    alloc(&p->d_state_nov, ms);
-    alloc(&p->s->d_cand_moved, static_cast<size_t>(slots) * 4);
-    alloc(&p->s->d_cand_nov, static_cast<size_t>(slots));
+    c.alloc(&p->d_state_nov, ms);
+    c.alloc(&p->s->d_cand_moved, static_cast<size_t>(slots) * 4);
+    c.alloc(&p->s->d_cand_nov, static_cast<size_t>(slots));
   }
-  if (err == hipSuccess) {
-    uint8_t packed[kPlanGroups];
-    uint8_t raw[4 * kPlanGroups];
-    plan_action_groups(raw);
-    for (int g = 0; g < kPlanGroups; g++)
-      packed[g] = static_cast<uint8_t>(raw[4 * g] | (raw[4 * g + 1] << 2) | (raw[4 * g + 2] << 4) | (raw[4 * g + 3] << 6));
-    err = hipMemcpy(p->d_groups, packed, kPlanGroups, hipMemcpyHostToDevice);
-  }
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_planner_create: ") + hipGetErrorString(err);
+  c.then([&] { return plan_upload_groups(p->d_groups); });
+  if (!c.ok()) {
     pw_planner_destroy(p);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_planner_create", c.err);
   }
   if (mode == PW_PLAN_N_RGD) {
     if (int rc = novelty_alloc(e->set->device, h.N, h.W, h.H, &p->s->nov)) {

@@ -639,14 +639,11 @@ struct PwPushPlanBatch {
   std::vector<PwRgd*> rgd;
   PpbItem* d_items;
   int32_t* d_slot_of;  // [set count] the first item of each set index, -1 = none (the states form)
-  uint8_t* d_slab;     // counter (256 B), then `groups` slabs
-  int64_t groups;
+  PwSlabPool pool;
   int64_t ran_groups;  // workgroups of the last launch (0: no run yet)
   PpbArgs args;        // everything but the per-run fields
   size_t lds;
-  int64_t* h_cancel;   // pinned, mapped
-  int64_t* d_cancel;
-  int64_t seq;
+  PwCancelWord cancel;
 };
 
 extern "C" {
@@ -656,8 +653,8 @@ void pw_push_plan_batch_destroy(PwPushPlanBatch* b) {
   PwDeviceGuard guard(b->eng->set->device);
   if (b->d_items) (void)hipFree(b->d_items);
   if (b->d_slot_of) (void)hipFree(b->d_slot_of);
-  if (b->d_slab) (void)hipFree(b->d_slab);
-  if (b->h_cancel) (void)hipHostFree(b->h_cancel);
+  if (b->pool.d_slab) (void)hipFree(b->pool.d_slab);
+  cancel_word_destroy(&b->cancel);
   for (PwRgd* r : b->rgd) pw_rgd_destroy(r);
   delete b;
 }
@@ -674,10 +671,7 @@ int pw_push_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, in
   if (cost_range < 0 || cost_range > static_cast<int32_t>(kPbCostRange))
     return pw_fail(PW_EINVAL, "pw_push_plan_batch_create: cost_range must be in 1 .. 65536 (0 = 65536)");
   *out = nullptr;
-  for (int32_t i = 0; i < n; i++) {
-    const int32_t pid = puzzles ? puzzles[i] : i;
-    if (pid < 0 || pid >= e->set->count) return pw_fail(PW_EINVAL, "pw_push_plan_batch_create: puzzle index out of range");
-  }
+  if (!pw_puzzles_ok(e, puzzles, n)) return pw_fail(PW_EINVAL, "pw_push_plan_batch_create: puzzle index out of range");
   PwPushPlanBatch* b = new (std::nothrow) PwPushPlanBatch();
   if (!b) return pw_fail(PW_ENOMEM, "pw_push_plan_batch_create: out of memory");
   b->eng = e;
@@ -708,8 +702,7 @@ int pw_push_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, in
     levels = std::max(levels, std::max(h.N - 2, 1));
   }
   b->max_n = max_n;
-  std::vector<int32_t> slot_of(static_cast<size_t>(e->set->count), -1);
-  for (int32_t i = n - 1; i >= 0; i--) slot_of[static_cast<size_t>(items[static_cast<size_t>(i)].pid)] = i;  // the first wins
+  const std::vector<int32_t> slot_of = pw_slot_of(items, e->set->count);
   PpbArgs& a = b->args;
   std::memset(static_cast<void*>(&a), 0, sizeof(a));
   a.hdrs = e->set->d_headers;
@@ -723,74 +716,54 @@ int pw_push_plan_batch_create(PwEngine* e, const int32_t* puzzles, int32_t n, in
   a.nb = b->cost_range + 2u;
   a.n0 = (a.nb + 63u) / 64u;
   a.n1 = (a.n0 + 63u) / 64u;
-  uint64_t slots = 1;
-  while (slots < 2ull * static_cast<uint64_t>(max_states)) slots <<= 1;
+  const uint64_t ms = static_cast<uint64_t>(max_states), slots = pw_table_slots(ms);
   a.slot_mask = static_cast<uint32_t>(slots - 1u);
   a.levels = levels;
-  const uint64_t ms = static_cast<uint64_t>(max_states);
-  auto al = [](uint64_t v) { return (v + 255u) & ~uint64_t(255); };
-  uint64_t off = al(ms * 8);
+  uint64_t off = pw_pad256(ms * 8);
   a.off_agent = off;
-  off += al(ms);
+  off += pw_pad256(ms);
   a.off_parent = off;
-  off += al(ms * 4);
+  off += pw_pad256(ms * 4);
   a.off_from = off;
-  off += al(ms * 2);
+  off += pw_pad256(ms * 2);
   a.off_action = off;
-  off += al(ms);
+  off += pw_pad256(ms);
   a.off_goal = off;
-  off += al(ms);
+  off += pw_pad256(ms);
   a.off_next = off;
-  off += al(ms * 4);
+  off += pw_pad256(ms * 4);
   a.off_table = off;
-  off += al(slots * 8);
+  off += pw_pad256(slots * 8);
   a.off_head = off;
-  off += al(static_cast<uint64_t>(a.nb) * 4);
+  off += pw_pad256(static_cast<uint64_t>(a.nb) * 4);
   a.off_bits0 = off;
-  off += al(static_cast<uint64_t>(a.n0) * 8);
+  off += pw_pad256(static_cast<uint64_t>(a.n0) * 8);
   a.off_bits1 = off;
-  off += al(static_cast<uint64_t>(a.n1) * 8);
+  off += pw_pad256(static_cast<uint64_t>(a.n1) * 8);
   a.off_last = off;
   off += 256;
   a.slab_bytes = off;
   b->lds = static_cast<size_t>(PW_WAVE) * (16 * levels + 2 * 8);
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
-  // persistent workgroups: one per item up to two per CU, fewer when the slabs would not fit a quarter of the free memory
-  size_t free_b = 0, total_b = 0;
-  if (err == hipSuccess && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0)) free_b = total_b / 2;
-  b->groups = std::min<int64_t>(n, 2ll * e->num_cus);
-  b->groups = std::max<int64_t>(1, std::min<int64_t>(b->groups, static_cast<int64_t>(free_b / 4 / a.slab_bytes)));
-  auto alloc = [&](void* ptr, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(ptr), bytes);
-  };
-  alloc(&b->d_items, sizeof(PpbItem) * static_cast<size_t>(n));
-  alloc(&b->d_slot_of, sizeof(int32_t) * slot_of.size());
-  alloc(&b->d_slab, 256 + static_cast<size_t>(b->groups) * static_cast<size_t>(a.slab_bytes));
-  if (err == hipSuccess) err = hipHostMalloc(reinterpret_cast<void**>(&b->h_cancel), 64, hipHostMallocMapped);
-  if (err == hipSuccess) {
-    b->h_cancel[0] = b->h_cancel[1] = 0;
-    err = hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_cancel), b->h_cancel, 0);
-  }
-  if (err == hipSuccess) err = hipMemcpy(b->d_items, items.data(), sizeof(PpbItem) * static_cast<size_t>(n), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(b->d_slot_of, slot_of.data(), sizeof(int32_t) * slot_of.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess)  // tag 0 is no item's: the tables start empty
-    err = hipMemset(b->d_slab, 0, 256 + static_cast<size_t>(b->groups) * static_cast<size_t>(a.slab_bytes));
-  int khz = 0;
-  if (err == hipSuccess) err = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, e->set->device);
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_push_plan_batch_create: ") + hipGetErrorString(err);
+  PwHipChain c(guard.status());
+  slab_pool_create(&b->pool, c, n, e->num_cus, a.slab_bytes);
+  c.alloc(&b->d_items, sizeof(PpbItem) * items.size());
+  c.alloc(&b->d_slot_of, sizeof(int32_t) * slot_of.size());
+  cancel_word_create(&b->cancel, c);
+  c.then([&] { return hipMemcpy(b->d_items, items.data(), sizeof(PpbItem) * items.size(), hipMemcpyHostToDevice); });
+  c.then([&] { return hipMemcpy(b->d_slot_of, slot_of.data(), sizeof(int32_t) * slot_of.size(), hipMemcpyHostToDevice); });
+  c.then([] { return hipDeviceSynchronize(); });
+  if (!c.ok()) {
     pw_push_plan_batch_destroy(b);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_push_plan_batch_create", c.err);
   }
   a.items = b->d_items;
   a.slot_of = b->d_slot_of;
   a.set_count = e->set->count;
-  a.slab = b->d_slab + 256;
-  a.next_item = reinterpret_cast<uint32_t*>(b->d_slab);
-  a.cancel = b->d_cancel;
-  a.clock_khz = khz > 0 ? static_cast<uint32_t>(khz) : 100000u;
+  a.slab = b->pool.slabs();
+  a.next_item = b->pool.counter();
+  a.cancel = b->cancel.d;
+  a.clock_khz = pw_wall_clock_khz(e->set->device);
   *out = b;
   return PW_OK;
 } catch (...) {
@@ -810,7 +783,7 @@ static int ppb_check_run(const char* fn, const PwPushPlanBatch* b, double time_l
   if (push_cap < 0) return pw_fail(PW_EINVAL, f + ": push_cap must be >= 0");
   if ((plan_from || plan_action || plan_pos) && !plan_len)
     return pw_fail(PW_EINVAL, f + ": plan_from, plan_action and plan_pos need plan_len");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, f + ": npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad(f + ": ", npad)) return rc;
   if (npad < b->max_n) return pw_fail(PW_EINVAL, f + ": npad is smaller than the largest prepared puzzle's number of movables");
   return PW_OK;
 }
@@ -822,14 +795,13 @@ static int ppb_launch(PwPushPlanBatch* b, PpbArgs& a, int32_t n, int64_t max_rou
                       int32_t npad_out, hipStream_t st, const char* what) {
   a.n = n;
   a.max_rounds = max_rounds;
-  const double ticks = time_limit * static_cast<double>(a.clock_khz) * 1000.0;
-  a.time_ticks = time_limit > 0.0 ? (ticks >= 1.8e19 ? ~0ull : std::max<unsigned long long>(1ull, static_cast<unsigned long long>(ticks))) : 0ull;
+  a.time_ticks = pw_deadline_ticks(time_limit, a.clock_khz);
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &capturing) != hipSuccess) {
     (void)hipGetLastError();
     capturing = hipStreamCaptureStatusNone;
   }
-  a.seq = ++b->seq;
+  a.seq = ++b->cancel.seq;
   if (capturing != hipStreamCaptureStatusNone) a.seq = INT64_MAX;  // (replays: cancelled by the generation alone)
   a.info = info;
   a.plan_len = plan_len;
@@ -839,42 +811,10 @@ static int ppb_launch(PwPushPlanBatch* b, PpbArgs& a, int32_t n, int64_t max_rou
   a.push_cap = push_cap;
   a.npad_out = npad_out;
   hipLaunchKernelGGL(pw_push_plan_batch_begin_kernel, dim3(1), dim3(1), 0, st, a.next_item, static_cast<uint32_t>(n), a.cancel);
-  const int64_t groups = std::min<int64_t>(b->groups, n);
+  const int64_t groups = std::min<int64_t>(b->pool.groups, n);
   hipLaunchKernelGGL(pw_push_plan_batch_kernel, dim3(static_cast<unsigned>(groups)), dim3(PW_WAVE), b->lds, st, a);
   b->ran_groups = groups;
   return check_launch(what);
-}
-
-// the states form's runs may hold more items than the handle prepared puzzles: up to two workgroups per CU as memory allows.
-// Replacing the slabs waits for the device once (a launch in flight on any stream still uses the old ones).
-static int ppb_grow(PwPushPlanBatch* b, int32_t n) {
-  const int64_t want = std::min<int64_t>(n, 2ll * b->eng->num_cus);
-  if (want <= b->groups) return PW_OK;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return PW_OK;  // (keep what there is)
-  const uint64_t slab = b->args.slab_bytes;
-  const int64_t fit = static_cast<int64_t>((free_b + static_cast<uint64_t>(b->groups) * slab) / 4 / slab);
-  const int64_t groups = std::min<int64_t>(want, fit);
-  if (groups <= b->groups) return PW_OK;
-  uint8_t* fresh = nullptr;
-  const size_t bytes = 256 + static_cast<size_t>(groups) * static_cast<size_t>(slab);
-  if (hipMalloc(reinterpret_cast<void**>(&fresh), bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return PW_OK;  // (the launch runs on the workgroups it has)
-  }
-  hipError_t err = hipDeviceSynchronize();
-  if (err == hipSuccess) err = hipMemset(fresh, 0, bytes);  // tag 0 is no item's: the tables start empty
-  if (err == hipSuccess) err = hipFree(b->d_slab);
-  if (err != hipSuccess) {
-    (void)hipFree(fresh);
-    return pw_fail(PW_EDEVICE, std::string("pw_push_plan_batch_run_states: ") + hipGetErrorString(err));
-  }
-  b->d_slab = fresh;
-  b->groups = groups;
-  b->ran_groups = 0;
-  b->args.slab = fresh + 256;
-  b->args.next_item = reinterpret_cast<uint32_t*>(fresh);  // (zeroed: the tags start again on empty tables)
-  return PW_OK;
 }
 
 // the slab that ran `item` last, for a read: PW_OK and the slab, or the error (synchronises `st` for the slabs' last words)
@@ -946,7 +886,13 @@ int pw_push_plan_batch_run_states(PwPushPlanBatch* b, const int32_t* puzzle_id, 
   if (!pos) return pw_fail(PW_EINVAL, std::string(fn) + ": null pos");
   PwDeviceGuard guard(b->eng->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int rc = ppb_grow(b, n)) return rc;
+  bool replaced = false;
+  if (int rc = slab_pool_grow(&b->pool, n, b->eng->num_cus, fn, &replaced)) return rc;
+  if (replaced) {  // (the counter is zeroed: the tags start again on empty tables)
+    b->args.slab = b->pool.slabs();
+    b->args.next_item = b->pool.counter();
+    b->ran_groups = 0;
+  }
   PpbArgs a = b->args;
   a.state_pid = puzzle_id;
   a.state_pos = pos;
@@ -961,8 +907,8 @@ int pw_push_plan_batch_run_states(PwPushPlanBatch* b, const int32_t* puzzle_id, 
 
 int pw_push_plan_batch_read_states(PwPushPlanBatch* b, int32_t item, int64_t first, int64_t count, int8_t* pos, int32_t npad,
                                    int8_t* canon, void* stream) try {
-  if (pos && npad != 4 && npad != 8 && npad != 16 && npad != 32)
-    return pw_fail(PW_EINVAL, "pw_push_plan_batch_read_states: npad must be 4, 8, 16 or 32");
+  if (pos)
+    if (int rc = pw_check_npad("pw_push_plan_batch_read_states: ", npad)) return rc;
   PpbReadArgs r{};
   r.pos = pos;
   r.npad = npad;
@@ -986,8 +932,8 @@ int pw_push_plan_batch_read_links(PwPushPlanBatch* b, int32_t item, int64_t firs
 
 int pw_push_plan_batch_cancel(PwPushPlanBatch* b) try {
   if (!b) return pw_fail(PW_EINVAL, "pw_push_plan_batch_cancel: null handle");
-  __atomic_store_n(b->h_cancel, b->seq, __ATOMIC_RELEASE);  // every eager launch made so far, queued ones included
-  __atomic_store_n(b->h_cancel + 1, b->h_cancel[1] + 1, __ATOMIC_RELEASE);  // and whatever has begun, replays of a capture included
+  cancel_word_cancel(&b->cancel);  // every eager launch made so far
+  __atomic_store_n(b->cancel.h + 1, b->cancel.h[1] + 1, __ATOMIC_RELEASE);  // and whatever has begun, replays of a capture included
   return PW_OK;
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI

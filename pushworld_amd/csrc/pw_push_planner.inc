@@ -215,25 +215,22 @@ static int push_planner_reserve_eval(PwPushPlanner* p, int64_t rows, const char*
   if (rows <= p->eval_cap) return PW_OK;
   push_planner_free_eval(p);
   const int64_t cap = (std::max<int64_t>(rows + rows / 2, 4096) + 3) & ~3ll;
-  hipError_t err = hipSuccess;
-  auto alloc = [&](void* ptr, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(ptr), bytes);
-  };
+  PwHipChain c;
   const size_t n = static_cast<size_t>(cap);
-  alloc(&p->d_rows, n * p->s->N * 4);
-  alloc(&p->d_cost, n * 4);
+  c.alloc(&p->d_rows, n * p->s->N * 4);
+  c.alloc(&p->d_cost, n * 4);
   for (int k = 0; k < 2; k++) {
-    alloc(&p->d_keys[k], n * 4);
-    alloc(&p->d_vals[k], n * 4);
+    c.alloc(&p->d_keys[k], n * 4);
+    c.alloc(&p->d_vals[k], n * 4);
   }
-  if (err == hipSuccess)
-    err = rocprim::radix_sort_pairs(nullptr, p->sort_tmp_bytes, p->d_keys[0], p->d_keys[1], p->d_vals[0], p->d_vals[1], n, 0,
-                                    kPlanSortBits, nullptr);
-  alloc(&p->d_sort_tmp, std::max<size_t>(p->sort_tmp_bytes, 16));
-  if (err != hipSuccess) {
-    const std::string msg = std::string(what) + ": " + hipGetErrorString(err);
+  c.then([&] {
+    return rocprim::radix_sort_pairs(nullptr, p->sort_tmp_bytes, p->d_keys[0], p->d_keys[1], p->d_vals[0], p->d_vals[1], n, 0,
+                                     kPlanSortBits, nullptr);
+  });
+  c.alloc(&p->d_sort_tmp, std::max<size_t>(p->sort_tmp_bytes, 16));
+  if (!c.ok()) {
     push_planner_free_eval(p);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail(what, c.err);
   }
   p->eval_cap = cap;
   return PW_OK;
@@ -336,29 +333,25 @@ int pw_push_planner_create(PwEngine* e, int32_t puzzle, int64_t max_states, int3
   p->q.n1 = (p->q.n0 + 63u) / 64u;
   p->q.n2 = (p->q.n1 + 63u) / 64u;
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
-  auto alloc = [&](void* ptr, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(ptr), bytes);
-  };
+  PwHipChain c(guard.status());
   const size_t ms = static_cast<size_t>(max_states), k = static_cast<size_t>(batch);
-  alloc(&p->q.head, static_cast<size_t>(p->q.nb) * 4);
-  alloc(&p->q.bits0, static_cast<size_t>(p->q.n0) * 8);
-  alloc(&p->q.bits1, static_cast<size_t>(p->q.n1) * 8);
-  alloc(&p->q.bits2, static_cast<size_t>(p->q.n2) * 8);
-  alloc(&p->q.seg_start, ms * 4);
-  alloc(&p->q.seg_len, ms * 4);
-  alloc(&p->q.seg_next, ms * 4);
-  alloc(&p->q.ent, ms * 4);
-  alloc(&p->d_info, kPSlots * 8);
-  alloc(&p->d_plist, k * 4);
-  alloc(&p->d_rsrc, k * 4);
-  alloc(&p->d_rlen, k * 4);
-  alloc(&p->d_roff, k * 4);
-  alloc(&p->d_gpos, k * p->s->npad * 2);
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_push_planner_create: ") + hipGetErrorString(err);
+  c.alloc(&p->q.head, static_cast<size_t>(p->q.nb) * 4);
+  c.alloc(&p->q.bits0, static_cast<size_t>(p->q.n0) * 8);
+  c.alloc(&p->q.bits1, static_cast<size_t>(p->q.n1) * 8);
+  c.alloc(&p->q.bits2, static_cast<size_t>(p->q.n2) * 8);
+  c.alloc(&p->q.seg_start, ms * 4);
+  c.alloc(&p->q.seg_len, ms * 4);
+  c.alloc(&p->q.seg_next, ms * 4);
+  c.alloc(&p->q.ent, ms * 4);
+  c.alloc(&p->d_info, kPSlots * 8);
+  c.alloc(&p->d_plist, k * 4);
+  c.alloc(&p->d_rsrc, k * 4);
+  c.alloc(&p->d_rlen, k * 4);
+  c.alloc(&p->d_roff, k * 4);
+  c.alloc(&p->d_gpos, k * p->s->npad * 2);
+  if (!c.ok()) {
     pw_push_planner_destroy(p);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_push_planner_create", c.err);
   }
   *out = p;
   return PW_OK;

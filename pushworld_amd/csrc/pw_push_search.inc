@@ -374,37 +374,33 @@ static int push_search_reserve_rows(PwPushSearch* s, int64_t rows, hipStream_t s
   push_search_free_rows(s);
   const int64_t cap = std::max<int64_t>(rows + rows / 2, 4096);
   size_t scan_bytes = 0;
-  hipError_t err = rocprim::exclusive_scan(nullptr, scan_bytes, s->d_flag, s->d_rank, 0u, static_cast<size_t>(cap) + 1,
-                                           rocprim::plus<uint32_t>(), st);
-  scan_bytes = std::max<size_t>((scan_bytes + 255) & ~static_cast<size_t>(255), 256);
-  auto alloc = [&](void* p, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(p), bytes);
-  };
+  PwHipChain c(rocprim::exclusive_scan(nullptr, scan_bytes, s->d_flag, s->d_rank, 0u, static_cast<size_t>(cap) + 1,
+                                       rocprim::plus<uint32_t>(), st));
+  scan_bytes = std::max<size_t>(pw_pad256(scan_bytes), 256);
   const size_t n = static_cast<size_t>(cap), ids = static_cast<size_t>(std::max<int64_t>(cap, s->chunk));
-  alloc(&s->d_ids, ids * 4);
-  alloc(&s->d_row_item, n * 4);
-  alloc(&s->d_row_from, n * 2);
-  alloc(&s->d_row_action, n);
-  alloc(&s->d_row_walk, n * 4);
-  alloc(&s->d_row_goal, n);
-  alloc(&s->d_row_next, n * s->npad * 2);
-  alloc(&s->d_s_size, n * 4);
-  alloc(&s->d_s_canon, n * 2);
-  alloc(&s->d_s_offset, (n + 1) * 8);
-  alloc(&s->d_cand_state, n * s->NW * 4);
-  alloc(&s->d_cand_hash, n * 4);
-  alloc(&s->d_cand_fp, n * 4);
-  alloc(&s->d_cand_slot, n * 4);
-  alloc(&s->d_cand_won, n);
-  alloc(&s->d_cand_lost, n);
-  alloc(&s->d_flag, (n + 1) * 4);
-  alloc(&s->d_rank, (n + 1) * 4);
-  alloc(&s->d_r_scan, scan_bytes);
-  if (err == hipSuccess) err = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_ids), s->puzzle, ids, st);
-  if (err != hipSuccess) {
-    const std::string msg = std::string(what) + ": " + hipGetErrorString(err);
+  c.alloc(&s->d_ids, ids * 4);
+  c.alloc(&s->d_row_item, n * 4);
+  c.alloc(&s->d_row_from, n * 2);
+  c.alloc(&s->d_row_action, n);
+  c.alloc(&s->d_row_walk, n * 4);
+  c.alloc(&s->d_row_goal, n);
+  c.alloc(&s->d_row_next, n * s->npad * 2);
+  c.alloc(&s->d_s_size, n * 4);
+  c.alloc(&s->d_s_canon, n * 2);
+  c.alloc(&s->d_s_offset, (n + 1) * 8);
+  c.alloc(&s->d_cand_state, n * s->NW * 4);
+  c.alloc(&s->d_cand_hash, n * 4);
+  c.alloc(&s->d_cand_fp, n * 4);
+  c.alloc(&s->d_cand_slot, n * 4);
+  c.alloc(&s->d_cand_won, n);
+  c.alloc(&s->d_cand_lost, n);
+  c.alloc(&s->d_flag, (n + 1) * 4);
+  c.alloc(&s->d_rank, (n + 1) * 4);
+  c.alloc(&s->d_r_scan, scan_bytes);
+  c.then([&] { return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_ids), s->puzzle, ids, st); });
+  if (!c.ok()) {
     push_search_free_rows(s);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail(what, c.err);
   }
   s->r_scan_bytes = scan_bytes;
   s->row_cap = cap;
@@ -560,39 +556,35 @@ static int push_search_create(PwEngine* e, int32_t puzzle, int64_t max_states, i
   s->max_states = max_states;
   const int64_t chunk = e->search_chunk > 0 ? e->search_chunk : (1 << 16);  // PW_OPT_SEARCH_CHUNK
   s->chunk = static_cast<int32_t>(parents > 0 ? parents : std::min<int64_t>(std::min<int64_t>(chunk, 1 << 24), max_states));
-  uint64_t slots = 1024;
-  while (slots < 2ull * (static_cast<uint64_t>(max_states) + 1ull)) slots <<= 1;  // load factor below one half
+  const uint64_t slots = std::max<uint64_t>(1024, pw_table_slots(static_cast<uint64_t>(max_states) + 1ull));  // load factor below one half
   s->table_slots = slots;
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
+  PwHipChain c(guard.status());
   size_t scan_bytes = 0;
-  if (err == hipSuccess)
-    err = rocprim::exclusive_scan(nullptr, scan_bytes, s->d_f_offset, s->d_f_offset, static_cast<int64_t>(0),
-                                  static_cast<size_t>(s->chunk) + 1, rocprim::plus<int64_t>(), static_cast<hipStream_t>(nullptr));
-  s->f_scan_bytes = std::max<size_t>((scan_bytes + 255) & ~static_cast<size_t>(255), 256);
-  auto alloc = [&](void* p, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(p), bytes);
-  };
+  c.then([&] {
+    return rocprim::exclusive_scan(nullptr, scan_bytes, s->d_f_offset, s->d_f_offset, static_cast<int64_t>(0),
+                                   static_cast<size_t>(s->chunk) + 1, rocprim::plus<int64_t>(), static_cast<hipStream_t>(nullptr));
+  });
+  s->f_scan_bytes = std::max<size_t>(pw_pad256(scan_bytes), 256);
   const size_t n = static_cast<size_t>(max_states);
-  alloc(&s->d_pos, n * s->npad * 2);
-  alloc(&s->d_canon, n * 2);
-  alloc(&s->d_parent, n * 4);
-  alloc(&s->d_from, n * 2);
-  alloc(&s->d_action, n);
-  alloc(&s->d_walk, n * 4);
-  alloc(&s->d_goal, n);
-  alloc(&s->d_rsize, n * 4);
-  alloc(&s->d_npush, n * 4);
-  alloc(&s->d_table, static_cast<size_t>(slots) * 8);
-  alloc(&s->d_f_size, 256);
-  alloc(&s->d_f_offset, (static_cast<size_t>(s->chunk) + 1) * 8);
-  alloc(&s->d_f_scan, s->f_scan_bytes);
-  alloc(&s->d_counter, 64);
-  alloc(&s->d_info, PW_PS_I_WORDS * sizeof(unsigned long long));
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_push_search_create: ") + hipGetErrorString(err);
+  c.alloc(&s->d_pos, n * s->npad * 2);
+  c.alloc(&s->d_canon, n * 2);
+  c.alloc(&s->d_parent, n * 4);
+  c.alloc(&s->d_from, n * 2);
+  c.alloc(&s->d_action, n);
+  c.alloc(&s->d_walk, n * 4);
+  c.alloc(&s->d_goal, n);
+  c.alloc(&s->d_rsize, n * 4);
+  c.alloc(&s->d_npush, n * 4);
+  c.alloc(&s->d_table, static_cast<size_t>(slots) * 8);
+  c.alloc(&s->d_f_size, 256);
+  c.alloc(&s->d_f_offset, (static_cast<size_t>(s->chunk) + 1) * 8);
+  c.alloc(&s->d_f_scan, s->f_scan_bytes);
+  c.alloc(&s->d_counter, 64);
+  c.alloc(&s->d_info, PW_PS_I_WORDS * sizeof(unsigned long long));
+  if (!c.ok()) {
     pw_push_search_destroy(s);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_push_search_create", c.err);
   }
   *out = s;
   return PW_OK;
@@ -796,8 +788,7 @@ static int push_search_plan(PwPushSearch* s, int64_t index, int64_t chain_cap64,
   } chain_mem, mem;
   const size_t L0 = static_cast<size_t>(chain_cap);
   hipError_t err = hipMalloc(&chain_mem.p, (L0 + 1) * 4);
-  if (err != hipSuccess)
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_push_search_plan: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return pw_hip_fail("pw_push_search_plan", err);
   int32_t* d_chain = static_cast<int32_t*>(chain_mem.p);
   int32_t* d_len = d_chain + L0;
   hipLaunchKernelGGL(pw_push_search_chain_kernel, dim3(1), dim3(64), 0, st, s->d_parent, index, chain_cap, d_chain, d_len);
@@ -809,13 +800,11 @@ static int push_search_plan(PwPushSearch* s, int64_t index, int64_t chain_cap64,
   if (pushes) *pushes = len;
   if (len == 0) return 0;
   const size_t L = static_cast<size_t>(len);
-  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-  const size_t o_ids = 0, o_size = o_ids + up(L * 4), o_off = o_size + up(L * 4), o_pos = o_off + up((L + 1) * 8),
-               o_from = o_pos + up(L * row), o_act = o_from + up(L * 2), o_walk = o_act + up(L), o_map = o_walk + up(L * 4),
-               bytes = o_map + up(L * cells * 2);
+  const size_t o_ids = 0, o_size = o_ids + pw_pad256(L * 4), o_off = o_size + pw_pad256(L * 4), o_pos = o_off + pw_pad256((L + 1) * 8),
+               o_from = o_pos + pw_pad256(L * row), o_act = o_from + pw_pad256(L * 2), o_walk = o_act + pw_pad256(L),
+               o_map = o_walk + pw_pad256(L * 4), bytes = o_map + pw_pad256(L * cells * 2);
   err = hipMalloc(&mem.p, bytes);
-  if (err != hipSuccess)
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_push_search_plan: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return pw_hip_fail("pw_push_search_plan", err);
   uint8_t* base = static_cast<uint8_t*>(mem.p);
   int32_t* d_ids = reinterpret_cast<int32_t*>(base + o_ids);
   int8_t* d_gpos = reinterpret_cast<int8_t*>(base + o_pos);

@@ -836,25 +836,21 @@ int pw_push_solve_batch_create(PwEngine* e, int64_t states_cap, int64_t rows_cap
   b->states_cap = states_cap;
   b->rows_cap = rows_cap;
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
-  auto alloc = [&](void* p, size_t bytes) {
-    if (err == hipSuccess && bytes) err = hipMalloc(static_cast<void**>(p), bytes);
-  };
+  PwHipChain c(guard.status());
   const size_t ns = static_cast<size_t>(states_cap), nr = static_cast<size_t>(rows_cap);
-  alloc(&b->d_key, ns * 8);
-  alloc(&b->d_srow, ns * 8);
-  alloc(&b->d_cost, ns * 4);
-  alloc(&b->d_best, ns * 4);
-  alloc(&b->d_succ, nr * 4);
-  alloc(&b->d_from, nr * 2);
-  alloc(&b->d_action, nr);
-  alloc(&b->d_flags, nr);
-  alloc(&b->d_item_of_puzzle, static_cast<size_t>(e->set->count) * 4);
-  alloc(&b->d_counters, 32);
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_push_solve_batch_create: ") + hipGetErrorString(err);
+  c.alloc_nonzero(&b->d_key, ns * 8);
+  c.alloc_nonzero(&b->d_srow, ns * 8);
+  c.alloc_nonzero(&b->d_cost, ns * 4);
+  c.alloc_nonzero(&b->d_best, ns * 4);
+  c.alloc_nonzero(&b->d_succ, nr * 4);
+  c.alloc_nonzero(&b->d_from, nr * 2);
+  c.alloc_nonzero(&b->d_action, nr);
+  c.alloc_nonzero(&b->d_flags, nr);
+  c.alloc_nonzero(&b->d_item_of_puzzle, static_cast<size_t>(e->set->count) * 4);
+  c.alloc_nonzero(&b->d_counters, 32);
+  if (!c.ok()) {
     pw_push_solve_batch_destroy(b);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_push_solve_batch_create", c.err);
   }
   *out = b;
   return PW_OK;
@@ -868,8 +864,8 @@ int pw_push_solve_batch_run(PwPushSolveBatch* b, const int32_t* puzzles, const i
   if (n < 1) return pw_fail(PW_EINVAL, "pw_push_solve_batch_run: n must be >= 1");
   if (max_states_each < 1 || max_states_each > (1ll << 26))
     return pw_fail(PW_EINVAL, "pw_push_solve_batch_run: max_states_each must be in 1 .. 2^26");
-  if (starts && npad != 4 && npad != 8 && npad != 16 && npad != 32)
-    return pw_fail(PW_EINVAL, "pw_push_solve_batch_run: npad must be 4, 8, 16 or 32");
+  if (starts)
+    if (int rc = pw_check_npad("pw_push_solve_batch_run: ", npad)) return rc;
   PwEngine* e = b->eng;
   if (starts && npad < e->set->max_n)
     return pw_fail(PW_EINVAL, "pw_push_solve_batch_run: npad is smaller than the set's largest number of movables");
@@ -882,20 +878,17 @@ int pw_push_solve_batch_run(PwPushSolveBatch* b, const int32_t* puzzles, const i
     b->n = 0;
     const size_t items = static_cast<size_t>(n);
     const int64_t slots_cap = b->states_cap ? 4 * b->states_cap + 16 * static_cast<int64_t>(n) : 0;
-    hipError_t err = hipSuccess;
-    auto alloc = [&](void* p, size_t bytes) {
-      if (err == hipSuccess && bytes) err = hipMalloc(static_cast<void**>(p), bytes);
-    };
-    alloc(&b->d_slots, static_cast<size_t>(slots_cap) * 4);
-    alloc(&b->d_status, items);
-    alloc(&b->d_summary, items * 24);
-    alloc(&b->d_state_off, items * 8);
-    alloc(&b->d_row_off, items * 8);
-    alloc(&b->d_slot_off, items * 8);
-    alloc(&b->d_slot_log2, items);
-    if (err != hipSuccess) {
+    PwHipChain c;
+    c.alloc_nonzero(&b->d_slots, static_cast<size_t>(slots_cap) * 4);
+    c.alloc_nonzero(&b->d_status, items);
+    c.alloc_nonzero(&b->d_summary, items * 24);
+    c.alloc_nonzero(&b->d_state_off, items * 8);
+    c.alloc_nonzero(&b->d_row_off, items * 8);
+    c.alloc_nonzero(&b->d_slot_off, items * 8);
+    c.alloc_nonzero(&b->d_slot_log2, items);
+    if (!c.ok()) {
       push_solve_batch_free_items(b);
-      return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_push_solve_batch_run: ") + hipGetErrorString(err));
+      return pw_hip_fail("pw_push_solve_batch_run", c.err);
     }
     b->n_cap = n;
     b->slots_cap = slots_cap;
@@ -914,19 +907,18 @@ int pw_push_solve_batch_run(PwPushSolveBatch* b, const int32_t* puzzles, const i
   a.max_rows = static_cast<uint32_t>(max_states_each * PW_PSB_ROWS_PER_STATE);
   // slab of one workgroup: the state store, the states' first rows, cost, best, the rows (12 bytes each, PW_PSB_ROWS_PER_STATE per
   // state of the cap), then tables of 2^16, 2^20, 2^22 ... slots up to >= 2 * max_states, 12 bytes per slot
-  auto pad = [](uint64_t v) { return (v + 255) & ~uint64_t(255); };
   const uint64_t ms = static_cast<uint64_t>(max_states_each), mr = static_cast<uint64_t>(a.max_rows);
-  uint64_t off = pad(ms * 8);
+  uint64_t off = pw_pad256(ms * 8);
   a.srow_off = off;
-  off += pad((ms + 1) * 4);
+  off += pw_pad256((ms + 1) * 4);
   a.cost_off = off;
-  off += pad(ms * 2);
+  off += pw_pad256(ms * 2);
   a.best_off = off;
-  off += pad(ms * 2);
+  off += pw_pad256(ms * 2);
   a.rkey_off = off;
-  off += pad(mr * 8);
+  off += pw_pad256(mr * 8);
   a.rmeta_off = off;
-  off += pad(mr * 4);
+  off += pw_pad256(mr * 4);
   const uint32_t ladder[6] = {1u << 16, 1u << 20, 1u << 22, 1u << 24, 1u << 26, 1u << 29};
   int lv = 0;
   for (int k = 0; k < 6; k++) {
@@ -942,26 +934,10 @@ int pw_push_solve_batch_run(PwPushSolveBatch* b, const int32_t* puzzles, const i
     have = ladder[k];
     lv++;
   }
-  a.slab_bytes = pad(off);
-  // persistent workgroups: pw_search_batch's rule (two per CU or PW_OPT_SEARCH_BATCH_GROUPS_PER_CU, fewer when there are fewer
-  // items or the slabs would not fit a quarter of the free memory); the slabs are the engine's, shared with pw_search_batch
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0) free_b = total_b / 2;
-  int64_t groups = std::min<int64_t>(n, static_cast<int64_t>(e->search_batch_groups_per_cu > 0 ? e->search_batch_groups_per_cu : 2) * e->num_cus);
-  const int64_t avail = static_cast<int64_t>(free_b / 4 + e->search_slab_bytes);
-  groups = std::max<int64_t>(1, std::min<int64_t>(groups, avail / static_cast<int64_t>(a.slab_bytes)));
-  const size_t want = static_cast<size_t>(groups) * static_cast<size_t>(a.slab_bytes) + 256;
-  if (e->search_slab_bytes < want) {  // engine-owned, grown on demand, kept for the next call
-    if (hipStreamSynchronize(st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_push_solve_batch_run: stream error");
-    if (e->d_search_slab) (void)hipFree(e->d_search_slab);
-    e->d_search_slab = nullptr;
-    e->search_slab_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&e->d_search_slab), want) != hipSuccess)
-      return pw_fail(PW_ENOMEM, "pw_push_solve_batch_run: cannot allocate the search slabs");
-    e->search_slab_bytes = want;
-  }
-  a.slab = e->d_search_slab + 256;
-  a.next = reinterpret_cast<uint32_t*>(e->d_search_slab);
+  a.slab_bytes = pw_pad256(off);
+  // persistent workgroups by pw_search_batch's rule; the slabs are the engine's, shared with pw_search_batch
+  int64_t groups = 0;
+  if (int rc = engine_search_slab(e, n, a.slab_bytes, st, "pw_push_solve_batch_run", &groups, &a.slab, &a.next)) return rc;
   a.counters = b->d_counters;
   a.status = b->d_status;
   a.summary = b->d_summary;
@@ -1096,8 +1072,7 @@ int pw_push_solve_batch_query(PwPushSolveBatch* b, const int32_t* puzzle_id, con
   if (n < 1) return pw_fail(PW_EINVAL, "pw_push_solve_batch_query: n must be >= 1");
   if (!puzzle_id) return pw_fail(PW_EINVAL, "pw_push_solve_batch_query: null puzzle_id");
   if (!pos) return pw_fail(PW_EINVAL, "pw_push_solve_batch_query: null pos");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32)
-    return pw_fail(PW_EINVAL, "pw_push_solve_batch_query: npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad("pw_push_solve_batch_query: ", npad)) return rc;
   if (b->n < 1) return pw_fail(PW_EINVAL, "pw_push_solve_batch_query: no run yet (call pw_push_solve_batch_run)");
   if (npad < b->eng->set->max_n)
     return pw_fail(PW_EINVAL, "pw_push_solve_batch_query: npad is smaller than the set's largest number of movables");

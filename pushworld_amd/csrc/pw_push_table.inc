@@ -297,14 +297,14 @@ int pw_push_search_solve(PwPushSearch* s, int64_t info_out[5], void* stream) try
     return pw_fail(code, msg);
   };
   auto device_fail = [&](hipError_t e) {
-    return fail(e == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_push_search_solve: ") + hipGetErrorString(e));
+    return fail(pw_hip_code(e), std::string("pw_push_search_solve: ") + hipGetErrorString(e));
   };
   // ---- the row offsets: the scan of the store's push counts --------------------------------------------------------------------
   const size_t ns = static_cast<size_t>(S);
   size_t scan_bytes = 0;
   hipError_t err = rocprim::exclusive_scan(nullptr, scan_bytes, s->d_t_row_off, s->d_t_row_off, static_cast<int64_t>(0), ns + 1,
                                            rocprim::plus<int64_t>(), st);
-  scan_bytes = std::max<size_t>((scan_bytes + 255) & ~static_cast<size_t>(255), 256);
+  scan_bytes = std::max<size_t>(pw_pad256(scan_bytes), 256);
   if (err == hipSuccess) err = hipMalloc(&scan_mem.p, scan_bytes);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&s->d_t_row_off), (ns + 1) * 8);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&s->d_t_cost), ns * 4);
@@ -464,8 +464,7 @@ int pw_push_search_table_query(PwPushSearch* s, const int32_t* puzzle_id, const 
   if (!s) return pw_fail(PW_EINVAL, "pw_push_search_table_query: null search");
   if (n < 1) return pw_fail(PW_EINVAL, "pw_push_search_table_query: n must be >= 1");
   if (!pos) return pw_fail(PW_EINVAL, "pw_push_search_table_query: null pos");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32)
-    return pw_fail(PW_EINVAL, "pw_push_search_table_query: npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad("pw_push_search_table_query: ", npad)) return rc;
   if (npad < s->eng->set->max_n)
     return pw_fail(PW_EINVAL, "pw_push_search_table_query: npad is smaller than the set's largest number of movables");
   if (!s->t_solved) return pw_fail(PW_EINVAL, "pw_push_search_table_query: no table (call pw_push_search_solve after the search is exhausted)");
@@ -474,7 +473,6 @@ int pw_push_search_table_query(PwPushSearch* s, const int32_t* puzzle_id, const 
   const bool maps = walk != nullptr || action != nullptr;
   const int map_h = std::min(std::max(s->eng->set->max_h, 1), PW_MAX_DIM), map_w = std::min(std::max(s->eng->set->max_w, 1), PW_MAX_DIM);
   const size_t cells = static_cast<size_t>(map_h) * map_w;
-  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   if (n > s->q_cap || (maps && !s->q_maps)) {  // first use or growth: the one synchronisation of the query
     const size_t cap = static_cast<size_t>(std::max(n, s->q_cap));
     const bool with_maps = maps || s->q_maps;
@@ -484,21 +482,21 @@ int pw_push_search_table_query(PwPushSearch* s, const int32_t* puzzle_id, const 
     s->d_q_mem = nullptr;
     s->q_cap = 0;
     s->q_maps = false;
-    const size_t bytes = up(cap * 4) + up(cap) + up(cap * 4) + up(cap * 2) + up((cap + 1) * 8) + (with_maps ? up(cap * cells * 2) : 0);
+    const size_t bytes = pw_pad256(cap * 4) + pw_pad256(cap) + pw_pad256(cap * 4) + pw_pad256(cap * 2) + pw_pad256((cap + 1) * 8) +
+                         (with_maps ? pw_pad256(cap * cells * 2) : 0);
     err = hipMalloc(reinterpret_cast<void**>(&s->d_q_mem), bytes);
-    if (err != hipSuccess)
-      return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_push_search_table_query: ") + hipGetErrorString(err));
+    if (err != hipSuccess) return pw_hip_fail("pw_push_search_table_query", err);
     s->q_cap = static_cast<int32_t>(cap);
     s->q_maps = with_maps;
   }
   const size_t cap = static_cast<size_t>(s->q_cap);
   uint8_t* base = s->d_q_mem;
   int32_t* d_ids = reinterpret_cast<int32_t*>(base);
-  uint8_t* d_eff = base + up(cap * 4);
-  int32_t* d_size = reinterpret_cast<int32_t*>(d_eff + up(cap));
-  int8_t* d_canon = reinterpret_cast<int8_t*>(d_size) + up(cap * 4);
-  int64_t* d_offset = reinterpret_cast<int64_t*>(d_canon + up(cap * 2));
-  uint16_t* d_maps = maps ? reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(d_offset) + up((cap + 1) * 8)) : nullptr;
+  uint8_t* d_eff = base + pw_pad256(cap * 4);
+  int32_t* d_size = reinterpret_cast<int32_t*>(d_eff + pw_pad256(cap));
+  int8_t* d_canon = reinterpret_cast<int8_t*>(d_size) + pw_pad256(cap * 4);
+  int64_t* d_offset = reinterpret_cast<int64_t*>(d_canon + pw_pad256(cap * 2));
+  uint16_t* d_maps = maps ? reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(d_offset) + pw_pad256((cap + 1) * 8)) : nullptr;
   PushQueryArgs q{};
   q.puzzle_id = puzzle_id;
   q.pos = pos;

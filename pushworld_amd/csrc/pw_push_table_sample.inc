@@ -276,26 +276,6 @@ static PushTableDrawSrc push_table_draw_src(PwPushSearch* s) {
   return d;
 }
 
-static int push_table_npad_check(const std::string& f, int32_t npad) {
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, f + ": npad must be 4, 8, 16 or 32");
-  return PW_OK;
-}
-
-// (table_sample_checks of pw_table_sample.inc, in this table's words)
-static int push_table_sample_checks(const std::string& f, int32_t n, int32_t npad, const uint32_t* counter, int32_t lo, int32_t hi,
-                                    const int32_t* lo_n, const int32_t* hi_n, const int8_t* pos, const int32_t* steps,
-                                    const int32_t* out_state, const int32_t* out_cost) {
-  if (n < 1) return pw_fail(PW_EINVAL, f + ": n must be >= 1");
-  if (!pos) return pw_fail(PW_EINVAL, f + ": null pos");
-  if (!steps) return pw_fail(PW_EINVAL, f + ": null steps");
-  if (!counter) return pw_fail(PW_EINVAL, f + ": null counter");
-  if (!out_state || !out_cost) return pw_fail(PW_EINVAL, f + ": null out_state / out_cost");
-  if (int rc = push_table_npad_check(f, npad)) return rc;
-  if ((lo_n == nullptr) != (hi_n == nullptr)) return pw_fail(PW_EINVAL, f + ": the band arrays lo and hi come together");
-  if (!lo_n && (lo < 0 || lo > hi)) return pw_fail(PW_EINVAL, f + ": the cost band needs 0 <= lo <= hi");
-  return PW_OK;
-}
-
 extern "C" {
 
 int pw_push_search_table_index(PwPushSearch* s, void* stream) try {
@@ -316,27 +296,25 @@ int pw_push_search_table_index(PwPushSearch* s, void* stream) try {
       if (p) (void)hipFree(p);
     }
   } work;
-  auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
   uint32_t* none = nullptr;
   int32_t* nonev = nullptr;
   size_t sort_bytes = 0;
   hipError_t err = rocprim::radix_sort_pairs(nullptr, sort_bytes, none, none, nonev, nonev, ns, 0, bits, st);
-  sort_bytes = std::max<size_t>(up(sort_bytes), 256);
+  sort_bytes = std::max<size_t>(pw_pad256(sort_bytes), 256);
   // the workspace: the keys, the sorted keys, the values and the sort's own
-  if (err == hipSuccess) err = hipMalloc(&work.p, 3 * up(ns * 4) + sort_bytes);
+  if (err == hipSuccess) err = hipMalloc(&work.p, 3 * pw_pad256(ns * 4) + sort_bytes);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&s->d_t_states_by_cost), std::max<size_t>(ns * 4, 16));
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&s->d_t_cost_start), std::max<size_t>(words * 4, 16));
   if (err == hipSuccess) err = hipMemsetAsync(s->d_t_cost_start, 0, words * 4, st);
   if (err != hipSuccess) {
-    const std::string msg = f + ": " + hipGetErrorString(err);
     push_table_index_discard(s);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail(f, err);
   }
   uint8_t* base = static_cast<uint8_t*>(work.p);
   uint32_t* key = reinterpret_cast<uint32_t*>(base);
-  uint32_t* key_sorted = reinterpret_cast<uint32_t*>(base + up(ns * 4));
-  int32_t* val = reinterpret_cast<int32_t*>(base + 2 * up(ns * 4));
-  void* sort_tmp = base + 3 * up(ns * 4);
+  uint32_t* key_sorted = reinterpret_cast<uint32_t*>(base + pw_pad256(ns * 4));
+  int32_t* val = reinterpret_cast<int32_t*>(base + 2 * pw_pad256(ns * 4));
+  void* sort_tmp = base + 3 * pw_pad256(ns * 4);
   const dim3 grid(static_cast<unsigned>((S + 255) / 256)), block(256);
   hipLaunchKernelGGL(pw_push_table_index_key_kernel, grid, block, 0, st, s->d_t_cost, S, mc, key, val, s->d_t_cost_start);
   err = rocprim::radix_sort_pairs(sort_tmp, sort_bytes, key, key_sorted, val, s->d_t_states_by_cost, ns, 0, bits, st);
@@ -380,8 +358,8 @@ int pw_push_search_table_sample(PwPushSearch* s, const int32_t* puzzle_id, const
                                 int8_t* pos, int32_t* steps, uint8_t* term, uint8_t* trunc, int32_t* out_state, int32_t* out_cost,
                                 void* stream) try {
   if (!s) return pw_fail(PW_EINVAL, "pw_push_search_table_sample: null search");
-  if (int rc = push_table_sample_checks("pw_push_search_table_sample", n, npad, counter, lo, hi, lo_n, hi_n, pos, steps, out_state,
-                                        out_cost))
+  if (int rc = table_sample_checks("pw_push_search_table_sample", n, npad, counter, lo, hi, lo_n, hi_n, pos, steps, out_state,
+                                   out_cost, "out_state"))
     return rc;
   if (npad < s->N) return pw_fail(PW_EINVAL, "pw_push_search_table_sample: npad is smaller than the puzzle's number of movables");
   if (!s->t_solved)
@@ -426,7 +404,7 @@ int pw_push_search_table_emit(PwPushSearch* s, const int32_t* puzzle_id, const u
   const std::string f("pw_push_search_table_emit");
   if (!s) return pw_fail(PW_EINVAL, f + ": null search");
   if (n < 1) return pw_fail(PW_EINVAL, f + ": n must be >= 1");
-  if (int rc = push_table_npad_check(f, npad)) return rc;
+  if (int rc = pw_check_npad(f + ": ", npad)) return rc;
   if (!plan_from || !plan_action || !plan_state || !plan_len)
     return pw_fail(PW_EINVAL, f + ": null plan_from / plan_action / plan_state / plan_len");
   if (plan_cap < 1) return pw_fail(PW_EINVAL, f + ": plan_cap must be >= 1");

@@ -325,7 +325,7 @@ static int push_unroll_check_args(const PwEngine* e, const int32_t* puzzle_id, i
                                   const uint8_t* push_action, int32_t n, const int64_t* offset, int64_t cap, const char* what) {
   const std::string w = std::string(what) + ": ";
   if (n < 1) return pw_fail(PW_EINVAL, w + "n must be >= 1");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, w + "npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad(w, npad)) return rc;
   if (!puzzle_id) return pw_fail(PW_EINVAL, w + "null puzzle_id");
   if (!push_from) return pw_fail(PW_EINVAL, w + "null push_from");
   if (!push_action) return pw_fail(PW_EINVAL, w + "null push_action");
@@ -377,7 +377,7 @@ int pw_push_unroll_count(PwEngine* e, const int32_t* puzzle_id, const int8_t* po
   hipError_t err = rocprim::exclusive_scan(nullptr, scan_bytes, offset, offset, static_cast<int64_t>(0), count,
                                            rocprim::plus<int64_t>(), st);
   if (err != hipSuccess) return pw_fail(PW_EDEVICE, std::string("pw_push_unroll_count: ") + hipGetErrorString(err));
-  scan_bytes = (scan_bytes + 255) & ~static_cast<size_t>(255);
+  scan_bytes = pw_pad256(scan_bytes);
   if (int rc = replay_workspace(e, scan_bytes, "pw_push_unroll_count")) return rc;
   PushUnrollArgs a{};
   a.puzzle_id = puzzle_id;

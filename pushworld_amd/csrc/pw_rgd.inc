@@ -424,7 +424,7 @@ int pw_rgd_create(PwEngine* e, int32_t puzzle, int32_t fewest_tools, int64_t bud
   size_t bytes = 0;
   auto section = [&](size_t n) {
     const size_t at = bytes;
-    bytes += (n + 255) & ~static_cast<size_t>(255);
+    bytes += pw_pad256(n);
     return at;
   };
   const size_t o_cnt = section(8), o_masks = section(masks.size()), o_map = section(map.size() * 2),
@@ -465,9 +465,8 @@ int pw_rgd_create(PwEngine* e, int32_t puzzle, int32_t fewest_tools, int64_t bud
   if (err == hipSuccess) err = hipMemcpy(r->d_base, host.data(), head, hipMemcpyHostToDevice);
   if (err == hipSuccess && bytes > head) err = hipMemsetAsync(r->d_base + o_dist, 0xFF, bytes - head, nullptr);
   if (err != hipSuccess) {
-    const std::string msg = std::string("pw_rgd_create: ") + hipGetErrorString(err);
     pw_rgd_destroy(r);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_rgd_create", err);
   }
   r->d_exceeded = reinterpret_cast<unsigned long long*>(r->d_base + o_cnt);
   r->d_masks = r->d_base + o_masks;

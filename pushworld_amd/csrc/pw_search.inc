@@ -178,9 +178,8 @@ static int novelty_alloc(int device, int state_size, int width, int height, PwNo
   if (err == hipSuccess && n->pair_bytes) err = hipMalloc(reinterpret_cast<void**>(&n->t.pair), n->pair_bytes);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&n->d_bad), 4);
   if (err != hipSuccess) {
-    const std::string msg = std::string("novelty tables: ") + hipGetErrorString(err);
     pw_novelty_destroy(n);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("novelty tables", err);
   }
   *out = n;
   return PW_OK;
@@ -933,8 +932,7 @@ static int search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_
   const int64_t chunk = e->search_chunk > 0 ? e->search_chunk : (1 << 20);  // PW_OPT_SEARCH_CHUNK (tests: many passes per layer)
   s->chunk = chunk_parents > 0 ? static_cast<int32_t>(chunk_parents)
                                : static_cast<int32_t>(std::min<int64_t>(chunk, std::max<int64_t>(max_states, 1)));
-  uint64_t slots = 1024;
-  while (slots < 2ull * (static_cast<uint64_t>(max_states) + 4ull * s->chunk)) slots <<= 1;
+  const uint64_t slots = std::max<uint64_t>(1024, pw_table_slots(static_cast<uint64_t>(max_states) + 4ull * s->chunk));
   if (slots > (1ull << 31)) {
     delete s;
     return pw_fail(PW_ELIMIT, "visited table would exceed 2^31 slots");
@@ -943,13 +941,10 @@ static int search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_
   s->plan_cap = 1 << 16;
   const int64_t ncand = 4ll * s->chunk;
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
-  auto alloc = [&](void* p, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(p), bytes);
-  };
-  alloc(&s->d_states, static_cast<size_t>(max_states) * s->NW * 4);
-  alloc(&s->d_parent, static_cast<size_t>(max_states) * 4);
-  alloc(&s->d_action, static_cast<size_t>(max_states));
+  PwHipChain c(guard.status());
+  c.alloc(&s->d_states, static_cast<size_t>(max_states) * s->NW * 4);
+  c.alloc(&s->d_parent, static_cast<size_t>(max_states) * 4);
+  c.alloc(&s->d_action, static_cast<size_t>(max_states));
   // exact keys (PW_OPT_SEARCH_KEYS 1) when the state packs into 63 bits (the start state decides in pw_search_begin whether they
   // are used: it must not overlap a wall)
   {
@@ -960,25 +955,24 @@ static int search_create(PwEngine* e, int32_t puzzle, int64_t max_states, int32_
     s->key_bx = fits ? bx : 0;
     s->key_by = fits ? by : 0;
   }
-  alloc(&s->d_table, static_cast<size_t>(slots) * 8);
-  alloc(&s->d_cand_lost, static_cast<size_t>(ncand) * 4);
-  alloc(&s->d_owner, static_cast<size_t>(ncand / 64 + 8) * 8);
-  alloc(&s->d_cand_state, static_cast<size_t>(ncand) * s->NW * 4);
-  alloc(&s->d_cand_hash, static_cast<size_t>(ncand) * 4);
-  alloc(&s->d_cand_slot, static_cast<size_t>(ncand) * 4);
-  alloc(&s->d_cand_goal, static_cast<size_t>(ncand));
-  alloc(&s->d_block_off, static_cast<size_t>(ncand / 256 + 2) * 4);
-  alloc(&s->d_info, 4 * sizeof(unsigned long long));
-  alloc(&s->d_plan, static_cast<size_t>(s->plan_cap) + 16);
+  c.alloc(&s->d_table, static_cast<size_t>(slots) * 8);
+  c.alloc(&s->d_cand_lost, static_cast<size_t>(ncand) * 4);
+  c.alloc(&s->d_owner, static_cast<size_t>(ncand / 64 + 8) * 8);
+  c.alloc(&s->d_cand_state, static_cast<size_t>(ncand) * s->NW * 4);
+  c.alloc(&s->d_cand_hash, static_cast<size_t>(ncand) * 4);
+  c.alloc(&s->d_cand_slot, static_cast<size_t>(ncand) * 4);
+  c.alloc(&s->d_cand_goal, static_cast<size_t>(ncand));
+  c.alloc(&s->d_block_off, static_cast<size_t>(ncand / 256 + 2) * 4);
+  c.alloc(&s->d_info, 4 * sizeof(unsigned long long));
+  c.alloc(&s->d_plan, static_cast<size_t>(s->plan_cap) + 16);
   if (novelty_width > 0) {
-    alloc(&s->d_pruned, static_cast<size_t>(max_states));
-    alloc(&s->d_cand_moved, static_cast<size_t>(ncand) * 4);
-    alloc(&s->d_cand_nov, static_cast<size_t>(ncand));
+    c.alloc(&s->d_pruned, static_cast<size_t>(max_states));
+    c.alloc(&s->d_cand_moved, static_cast<size_t>(ncand) * 4);
+    c.alloc(&s->d_cand_nov, static_cast<size_t>(ncand));
   }
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_search_create: ") + hipGetErrorString(err);
+  if (!c.ok()) {
     pw_search_destroy(s);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_search_create", c.err);
   }
   if (novelty_width > 0) {
     if (int rc = novelty_alloc(e->set->device, h.N, h.W, h.H, &s->nov)) {
@@ -1541,11 +1535,11 @@ extern "C" int pw_search_batch(PwEngine* e, const int32_t* puzzles, int32_t n, i
   a.num_puzzles = e->set->count;
   a.max_states = static_cast<uint32_t>(max_states_each);
   // slab of one workgroup: the state store, then tables of 2^16, 2^20, 2^22, 2^24 ... slots up to >= 2 * max_states
-  uint64_t off = (static_cast<uint64_t>(max_states_each) * 8 + 255) & ~uint64_t(255);
+  uint64_t off = pw_pad256(static_cast<uint64_t>(max_states_each) * 8);
   a.plans = plans;
   a.plan_cap = plan_cap;
   a.link_off = off;
-  if (plans) off += (static_cast<uint64_t>(max_states_each) * 4 + 255) & ~uint64_t(255);
+  if (plans) off += pw_pad256(static_cast<uint64_t>(max_states_each) * 4);
   const uint32_t ladder[6] = {1u << 16, 1u << 20, 1u << 22, 1u << 24, 1u << 26, 1u << 29};
   int lv = 0;
   for (int k = 0; k < 6; k++) {
@@ -1561,24 +1555,8 @@ extern "C" int pw_search_batch(PwEngine* e, const int32_t* puzzles, int32_t n, i
     lv++;
   }
   a.slab_bytes = off;
-  // persistent workgroups: two per CU, fewer when there are fewer puzzles or the slabs would not fit a quarter of the free memory
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0) free_b = total_b / 2;
-  int64_t groups = std::min<int64_t>(n, static_cast<int64_t>(e->search_batch_groups_per_cu > 0 ? e->search_batch_groups_per_cu : 2) * e->num_cus);
-  const int64_t avail = static_cast<int64_t>(free_b / 4 + e->search_slab_bytes);
-  groups = std::max<int64_t>(1, std::min<int64_t>(groups, avail / static_cast<int64_t>(a.slab_bytes)));
-  const size_t want = static_cast<size_t>(groups) * static_cast<size_t>(a.slab_bytes) + 256;
-  if (e->search_slab_bytes < want) {  // engine-owned, grown on demand, kept for the next call
-    if (hipStreamSynchronize(st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_search_batch: stream error");
-    if (e->d_search_slab) (void)hipFree(e->d_search_slab);
-    e->d_search_slab = nullptr;
-    e->search_slab_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&e->d_search_slab), want) != hipSuccess)
-      return pw_fail(PW_ENOMEM, "pw_search_batch: cannot allocate the search slabs");
-    e->search_slab_bytes = want;
-  }
-  a.slab = e->d_search_slab + 256;
-  a.next = reinterpret_cast<uint32_t*>(e->d_search_slab);
+  int64_t groups = 0;
+  if (int rc = engine_search_slab(e, n, a.slab_bytes, st, "pw_search_batch", &groups, &a.slab, &a.next)) return rc;
   a.verdict = verdict;
   a.plan_len = plan_len;
   a.num_states = num_states;

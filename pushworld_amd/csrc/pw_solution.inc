@@ -263,20 +263,16 @@ int pw_search_solve(PwSearch* s, int64_t info[4], void* stream) try {
   hipStream_t st = static_cast<hipStream_t>(stream);
   search_table_discard(s);
   const int64_t total = s->layer_end;
-  hipError_t err = guard.status();
-  auto alloc = [&](void* p, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(p), bytes);
-  };
-  alloc(&s->d_succ, static_cast<size_t>(total) * 16);
-  alloc(&s->d_cost, static_cast<size_t>(total) * 2);
-  alloc(&s->d_acts, static_cast<size_t>(total));
-  alloc(&s->d_solve_counts, static_cast<size_t>(PW_SOLVE_WORDS) * 4);
-  if (s->use_keys) alloc(&s->d_slot_index, static_cast<size_t>(s->table_slots) * 4);
-  if (err == hipSuccess) err = hipMemsetAsync(s->d_solve_counts, 0, static_cast<size_t>(PW_SOLVE_WORDS) * 4, st);
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_search_solve: ") + hipGetErrorString(err);
+  PwHipChain c(guard.status());
+  c.alloc(&s->d_succ, static_cast<size_t>(total) * 16);
+  c.alloc(&s->d_cost, static_cast<size_t>(total) * 2);
+  c.alloc(&s->d_acts, static_cast<size_t>(total));
+  c.alloc(&s->d_solve_counts, static_cast<size_t>(PW_SOLVE_WORDS) * 4);
+  if (s->use_keys) c.alloc(&s->d_slot_index, static_cast<size_t>(s->table_slots) * 4);
+  c.then([&] { return hipMemsetAsync(s->d_solve_counts, 0, static_cast<size_t>(PW_SOLVE_WORDS) * 4, st); });
+  if (!c.ok()) {
     search_table_discard(s);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_search_solve", c.err);
   }
   auto fail = [&](int code, const std::string& msg) {
     search_table_discard(s);
@@ -317,7 +313,7 @@ int pw_search_solve(PwSearch* s, int64_t info[4], void* stream) try {
     for (uint32_t j = 0; j < nb; j++)
       hipLaunchKernelGGL(pw_solve_sweep_kernel, dim3(sblocks), dim3(256), 0, st, s->d_succ, s->d_cost, total, k + j, counts);
     uint32_t host[PW_SOLVE_BATCH + 1];
-    err = hipMemcpyAsync(host, counts + (k - 1), static_cast<size_t>(nb + 1) * 4, hipMemcpyDeviceToHost, st);
+    hipError_t err = hipMemcpyAsync(host, counts + (k - 1), static_cast<size_t>(nb + 1) * 4, hipMemcpyDeviceToHost, st);
     if (err == hipSuccess) err = hipStreamSynchronize(st);
     if (err != hipSuccess) return fail(PW_EDEVICE, std::string("pw_search_solve: ") + hipGetErrorString(err));
     if (k == 1) goals = host[0];
@@ -338,7 +334,7 @@ int pw_search_solve(PwSearch* s, int64_t info[4], void* stream) try {
   }
   ev.record(3, st);
   uint32_t tail[2] = {0, 0};  // missing, dead ends
-  err = hipMemcpyAsync(tail, counts + PW_SOLVE_MISSING, sizeof(tail), hipMemcpyDeviceToHost, st);
+  hipError_t err = hipMemcpyAsync(tail, counts + PW_SOLVE_MISSING, sizeof(tail), hipMemcpyDeviceToHost, st);
   if (err == hipSuccess) err = hipStreamSynchronize(st);
   if (err != hipSuccess) return fail(PW_EDEVICE, std::string("pw_search_solve: ") + hipGetErrorString(err));
   if (tail[0] != 0u)
@@ -395,8 +391,7 @@ int pw_search_table_query(PwSearch* s, const int32_t* puzzle_id, const int8_t* p
   if (!s) return pw_fail(PW_EINVAL, "pw_search_table_query: null search");
   if (n < 1) return pw_fail(PW_EINVAL, "pw_search_table_query: n must be >= 1");
   if (!pos) return pw_fail(PW_EINVAL, "pw_search_table_query: null pos");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32)
-    return pw_fail(PW_EINVAL, "pw_search_table_query: npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad("pw_search_table_query: ", npad)) return rc;
   if (npad < s->N) return pw_fail(PW_EINVAL, "pw_search_table_query: npad is smaller than the puzzle's number of movables");
   if (!s->solved) return pw_fail(PW_EINVAL, "pw_search_table_query: no table (call pw_search_solve after the search is exhausted)");
   PwDeviceGuard guard(s->eng->set->device);

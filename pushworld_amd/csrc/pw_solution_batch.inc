@@ -539,21 +539,17 @@ int pw_solve_batch_create(PwEngine* e, int64_t rows_cap, PwSolveBatch** out) try
   b->eng = e;
   b->rows_cap = rows_cap;
   PwDeviceGuard guard(e->set->device);
-  hipError_t err = guard.status();
-  auto alloc = [&](void* p, size_t bytes) {
-    if (err == hipSuccess && bytes) err = hipMalloc(static_cast<void**>(p), bytes);
-  };
+  PwHipChain c(guard.status());
   const size_t rows = static_cast<size_t>(rows_cap);
-  alloc(&b->d_key, rows * 8);
-  alloc(&b->d_succ, rows * 16);
-  alloc(&b->d_cost, rows * 2);
-  alloc(&b->d_acts, rows);
-  alloc(&b->d_item_of_puzzle, static_cast<size_t>(e->set->count) * 4);
-  alloc(&b->d_counters, 32);
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_solve_batch_create: ") + hipGetErrorString(err);
+  c.alloc_nonzero(&b->d_key, rows * 8);
+  c.alloc_nonzero(&b->d_succ, rows * 16);
+  c.alloc_nonzero(&b->d_cost, rows * 2);
+  c.alloc_nonzero(&b->d_acts, rows);
+  c.alloc_nonzero(&b->d_item_of_puzzle, static_cast<size_t>(e->set->count) * 4);
+  c.alloc_nonzero(&b->d_counters, 32);
+  if (!c.ok()) {
     pw_solve_batch_destroy(b);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_solve_batch_create", c.err);
   }
   *out = b;
   return PW_OK;
@@ -577,19 +573,16 @@ int pw_solve_batch_run(PwSolveBatch* b, const int32_t* puzzles, int32_t n, int64
     b->n = 0;
     const size_t items = static_cast<size_t>(n);
     const int64_t slots_cap = b->rows_cap ? 4 * b->rows_cap + 16 * static_cast<int64_t>(n) : 0;
-    hipError_t err = hipSuccess;
-    auto alloc = [&](void* p, size_t bytes) {
-      if (err == hipSuccess && bytes) err = hipMalloc(static_cast<void**>(p), bytes);
-    };
-    alloc(&b->d_slots, static_cast<size_t>(slots_cap) * 4);
-    alloc(&b->d_status, items);
-    alloc(&b->d_summary, items * 20);
-    alloc(&b->d_row_off, items * 8);
-    alloc(&b->d_slot_off, items * 8);
-    alloc(&b->d_slot_log2, items);
-    if (err != hipSuccess) {
+    PwHipChain c;
+    c.alloc_nonzero(&b->d_slots, static_cast<size_t>(slots_cap) * 4);
+    c.alloc_nonzero(&b->d_status, items);
+    c.alloc_nonzero(&b->d_summary, items * 20);
+    c.alloc_nonzero(&b->d_row_off, items * 8);
+    c.alloc_nonzero(&b->d_slot_off, items * 8);
+    c.alloc_nonzero(&b->d_slot_log2, items);
+    if (!c.ok()) {
       solve_batch_free_items(b);
-      return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, std::string("pw_solve_batch_run: ") + hipGetErrorString(err));
+      return pw_hip_fail("pw_solve_batch_run", c.err);
     }
     b->n_cap = n;
     b->slots_cap = slots_cap;
@@ -605,12 +598,11 @@ int pw_solve_batch_run(PwSolveBatch* b, const int32_t* puzzles, int32_t n, int64
   a.max_states = static_cast<uint32_t>(max_states_each);
   // slab of one workgroup: the state store, succ, cost, then tables of 2^16, 2^20, 2^22 ... slots up to >= 2 * max_states,
   // 12 bytes per slot (the key and the store index of its state)
-  auto pad = [](uint64_t v) { return (v + 255) & ~uint64_t(255); };
-  uint64_t off = pad(static_cast<uint64_t>(max_states_each) * 8);
+  uint64_t off = pw_pad256(static_cast<uint64_t>(max_states_each) * 8);
   a.succ_off = off;
-  off += pad(static_cast<uint64_t>(max_states_each) * 16);
+  off += pw_pad256(static_cast<uint64_t>(max_states_each) * 16);
   a.cost_off = off;
-  off += pad(static_cast<uint64_t>(max_states_each) * 2);
+  off += pw_pad256(static_cast<uint64_t>(max_states_each) * 2);
   const uint32_t ladder[6] = {1u << 16, 1u << 20, 1u << 22, 1u << 24, 1u << 26, 1u << 29};
   int lv = 0;
   for (int k = 0; k < 6; k++) {
@@ -626,25 +618,9 @@ int pw_solve_batch_run(PwSolveBatch* b, const int32_t* puzzles, int32_t n, int64
     lv++;
   }
   a.slab_bytes = off;
-  // persistent workgroups: pw_search_batch's rule (two per CU or PW_OPT_SEARCH_BATCH_GROUPS_PER_CU, fewer when there are fewer
-  // puzzles or the slabs would not fit a quarter of the free memory); the slabs are the engine's, shared with pw_search_batch
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0) free_b = total_b / 2;
-  int64_t groups = std::min<int64_t>(n, static_cast<int64_t>(e->search_batch_groups_per_cu > 0 ? e->search_batch_groups_per_cu : 2) * e->num_cus);
-  const int64_t avail = static_cast<int64_t>(free_b / 4 + e->search_slab_bytes);
-  groups = std::max<int64_t>(1, std::min<int64_t>(groups, avail / static_cast<int64_t>(a.slab_bytes)));
-  const size_t want = static_cast<size_t>(groups) * static_cast<size_t>(a.slab_bytes) + 256;
-  if (e->search_slab_bytes < want) {  // engine-owned, grown on demand, kept for the next call
-    if (hipStreamSynchronize(st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_solve_batch_run: stream error");
-    if (e->d_search_slab) (void)hipFree(e->d_search_slab);
-    e->d_search_slab = nullptr;
-    e->search_slab_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&e->d_search_slab), want) != hipSuccess)
-      return pw_fail(PW_ENOMEM, "pw_solve_batch_run: cannot allocate the search slabs");
-    e->search_slab_bytes = want;
-  }
-  a.slab = e->d_search_slab + 256;
-  a.next = reinterpret_cast<uint32_t*>(e->d_search_slab);
+  // persistent workgroups by pw_search_batch's rule; the slabs are the engine's, shared with pw_search_batch
+  int64_t groups = 0;
+  if (int rc = engine_search_slab(e, n, a.slab_bytes, st, "pw_solve_batch_run", &groups, &a.slab, &a.next)) return rc;
   a.counters = b->d_counters;
   a.status = b->d_status;
   a.summary = b->d_summary;
@@ -746,8 +722,7 @@ int pw_solve_batch_query(PwSolveBatch* b, const int32_t* puzzle_id, const int8_t
   if (n < 1) return pw_fail(PW_EINVAL, "pw_solve_batch_query: n must be >= 1");
   if (!puzzle_id) return pw_fail(PW_EINVAL, "pw_solve_batch_query: null puzzle_id");
   if (!pos) return pw_fail(PW_EINVAL, "pw_solve_batch_query: null pos");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32)
-    return pw_fail(PW_EINVAL, "pw_solve_batch_query: npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad("pw_solve_batch_query: ", npad)) return rc;
   if (b->n < 1) return pw_fail(PW_EINVAL, "pw_solve_batch_query: no run yet (call pw_solve_batch_run)");
   PwDeviceGuard guard(b->eng->set->device);
   SolveBatchQueryArgs a;

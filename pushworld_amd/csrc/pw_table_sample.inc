@@ -322,16 +322,17 @@ static void table_index_launch(const TableSrc& s, int64_t tables, int64_t max_ro
   hipLaunchKernelGGL(pw_table_index_scatter_kernel<kBatch>, grid, block, 0, st, s, static_cast<uint32_t>(chunks));
 }
 
+// out_name: what the entry point calls the drawn index (out_row; the push tables' out_state)
 static int table_sample_checks(const char* fn, int32_t n, int32_t npad, const uint32_t* counter, int32_t lo, int32_t hi,
                                const int32_t* lo_n, const int32_t* hi_n, const int8_t* pos, const int32_t* steps,
-                               const int32_t* out_row, const int32_t* out_cost) {
+                               const int32_t* out_row, const int32_t* out_cost, const char* out_name = "out_row") {
   const std::string f(fn);
   if (n < 1) return pw_fail(PW_EINVAL, f + ": n must be >= 1");
   if (!pos) return pw_fail(PW_EINVAL, f + ": null pos");
   if (!steps) return pw_fail(PW_EINVAL, f + ": null steps");
   if (!counter) return pw_fail(PW_EINVAL, f + ": null counter");
-  if (!out_row || !out_cost) return pw_fail(PW_EINVAL, f + ": null out_row / out_cost");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, f + ": npad must be 4, 8, 16 or 32");
+  if (!out_row || !out_cost) return pw_fail(PW_EINVAL, f + ": null " + out_name + " / out_cost");
+  if (int rc = pw_check_npad(f + ": ", npad)) return rc;
   if ((lo_n == nullptr) != (hi_n == nullptr)) return pw_fail(PW_EINVAL, f + ": the band arrays lo and hi come together");
   if (!lo_n && (lo < 0 || lo > hi)) return pw_fail(PW_EINVAL, f + ": the cost band needs 0 <= lo <= hi");
   return PW_OK;
@@ -367,19 +368,16 @@ int pw_solve_batch_index(PwSolveBatch* b, void* stream) try {
     max_rows = std::max<int64_t>(max_rows, b->h_summary[it * 5]);
   }
   solve_batch_free_index(b);
-  hipError_t err = hipSuccess;
-  auto alloc = [&](void* p, size_t bytes) {
-    if (err == hipSuccess) err = hipMalloc(static_cast<void**>(p), std::max<size_t>(bytes, 16));
-  };
-  alloc(&b->d_rows_by_cost, static_cast<size_t>(b->rows_cap) * 4);
-  alloc(&b->d_cost_start, static_cast<size_t>(words) * 4);
-  alloc(&b->d_cs_off, n * 8);
-  if (err == hipSuccess) err = hipMemsetAsync(b->d_cost_start, 0, std::max<size_t>(static_cast<size_t>(words) * 4, 16), st);
-  if (err == hipSuccess) err = hipMemcpyAsync(b->d_cs_off, b->h_cs_off.data(), n * 8, hipMemcpyHostToDevice, st);
-  if (err != hipSuccess) {
-    const std::string msg = std::string("pw_solve_batch_index: ") + hipGetErrorString(err);
+  PwHipChain c;  // (no allocation of zero bytes: at least 16)
+  const size_t cs_bytes = std::max<size_t>(static_cast<size_t>(words) * 4, 16);
+  c.alloc(&b->d_rows_by_cost, std::max<size_t>(static_cast<size_t>(b->rows_cap) * 4, 16));
+  c.alloc(&b->d_cost_start, cs_bytes);
+  c.alloc(&b->d_cs_off, std::max<size_t>(n * 8, 16));
+  c.then([&] { return hipMemsetAsync(b->d_cost_start, 0, cs_bytes, st); });
+  c.then([&] { return hipMemcpyAsync(b->d_cs_off, b->h_cs_off.data(), n * 8, hipMemcpyHostToDevice, st); });
+  if (!c.ok()) {
     solve_batch_free_index(b);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_solve_batch_index", c.err);
   }
   if (words > 0) {
     TableSrc src = table_src(b);
@@ -463,9 +461,8 @@ int pw_search_table_index(PwSearch* s, void* stream) try {
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&s->d_cost_start), words * 4);
   if (err == hipSuccess) err = hipMemsetAsync(s->d_cost_start, 0, words * 4, st);
   if (err != hipSuccess) {
-    const std::string msg = std::string("pw_search_table_index: ") + hipGetErrorString(err);
     search_index_discard(s);
-    return pw_fail(err == hipErrorOutOfMemory ? PW_ENOMEM : PW_EDEVICE, msg);
+    return pw_hip_fail("pw_search_table_index", err);
   }
   table_index_launch<false>(table_src(s), 1, s->table_states, st);
   if (int rc = check_launch("pw_search_table_index")) {

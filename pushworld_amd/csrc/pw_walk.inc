@@ -352,7 +352,7 @@ static int walk_check_args(const PwEngine* e, const int32_t* puzzle_id, int32_t 
                            int64_t cap, bool maps, int32_t map_h, int32_t map_w, const char* what) {
   const std::string w = std::string(what) + ": ";
   if (n < 1) return pw_fail(PW_EINVAL, w + "n must be >= 1");
-  if (npad != 4 && npad != 8 && npad != 16 && npad != 32) return pw_fail(PW_EINVAL, w + "npad must be 4, 8, 16 or 32");
+  if (int rc = pw_check_npad(w, npad)) return rc;
   if (!puzzle_id) return pw_fail(PW_EINVAL, w + "null puzzle_id");
   if (!offset) return pw_fail(PW_EINVAL, w + "null offset");
   if (cap < 0) return pw_fail(PW_EINVAL, w + "cap must be >= 0");
@@ -407,7 +407,7 @@ int pw_walk_regions(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, in
   hipError_t err = rocprim::exclusive_scan(nullptr, scan_bytes, offset, offset, static_cast<int64_t>(0), count,
                                            rocprim::plus<int64_t>(), st);
   if (err != hipSuccess) return pw_fail(PW_EDEVICE, std::string("pw_walk_regions: ") + hipGetErrorString(err));
-  scan_bytes = (scan_bytes + 255) & ~static_cast<size_t>(255);
+  scan_bytes = pw_pad256(scan_bytes);
   if (int rc = replay_workspace(e, scan_bytes, "pw_walk_regions")) return rc;
   // every entry of every map: 0xFFFF, the kernel overwrites the positions of the regions
   if (walk_map && hipMemsetAsync(walk_map, 0xff, static_cast<size_t>(n) * map_h * map_w * sizeof(uint16_t), st) != hipSuccess)
