@@ -375,6 +375,23 @@ int64_t pw_engine_obs_stride(const PwEngine* e);       /* recommended env stride
 #define PW_OPT_OBS_PADDING_ONCE 53   /* 0 (default) every pw_step_render writes every byte; 1 as described above.  A/B runs: 2 = 1 with the grid of
                                       the full render, the workgroups of padding pages returning at once; 3 = 1 with the list of live pages
                                       (1 takes whichever the tuner measured faster, the list when it never ran) */
+/* Only the CHANGED pages of a retained buffer are written (PW_OPT_OBS_CHANGED_PAGES, on top of PW_OPT_OBS_PADDING_ONCE).  A step moves the
+ * agent and now and then a pushed object; only the pixel rows they leave and enter change (Level-1 pool: 29 % of the live pages).
+ * The engine remembers the positions the retained buffer SHOWS (device memory laid out like pos, allocated with the live-page list; if
+ * that fails the live launch stays).  Every pw_step_render / pw_render whose render goes into the retained buffer of the retained
+ * (puzzle_id, batch) compares its new state with them on the device and leaves per environment the grid rows that differ (the rows a
+ * moved object left and entered; all 64 when a position lies outside 0 .. 63); the launch runs over the list of live pages, and a
+ * workgroup whose page holds none of those rows returns before it loads or stores anything.  A page that stays is rendered as ever.
+ *   - The comparison is against what the buffer shows, not against the state before the step: pw_reset, pw_step / pw_rollout without
+ *     a render, a render into another buffer, or the caller writing pos in between need no care -- the next pw_step_render repaints
+ *     what they changed.  There is no precondition on pos.
+ *   - The first pw_step_render after anything that establishes the retained observation anew, after pw_step_render_delta into the
+ *     buffer, or after this option or PW_OPT_OBS_PADDING_ONCE was set takes the live launch (same bytes) and starts remembering.
+ *   - With the option on EVERY byte of a retained buffer is the library's, not only its padding: a byte a caller writes into a live
+ *     page stays until that page changes or pw_render repairs it.
+ *   - A captured pw_step_render replays the form it was captured in.  The comparison runs on the device, so replays stay right while
+ *     nothing else writes the buffer. */
+#define PW_OPT_OBS_CHANGED_PAGES 58  /* 0 (default) the live launch; 1 as described above */
 #define PW_OPT_OBS_LIVE_PAGES 54     /* read-only: length of the live-page list of the retained observation, 0 when nothing is retained (synchronises
                                       the device when the list was last rebuilt in-stream) */
 #define PW_OPT_RESAMPLE_FENCE 55     /* pw_resample_weighted: 0 (default) the binary search reads the cdf alone, 1 every workgroup that draws first

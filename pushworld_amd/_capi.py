@@ -377,7 +377,8 @@ OPTIONS = {
     "bind_mismatches": 39,     # read-only: environments found with another puzzle id than the one they were bound to
     "obs_padding_once": 53,    # pw_step_render into a retained library-owned buffer of the bound batch renders the live pages only: 0 off, 1 on
                                # (2 / 3: on, with the early-exit / the list form -- A/B runs)
-    "obs_live_pages": 54,      # read-only: length of the live-page list of the retained observation (0: nothing retained)
+    "obs_changed_pages": 58,   # ... and of the live pages only those whose pixel rows differ from what the buffer shows: 0 off, 1 on
+    "obs_live_pages": 54,     # read-only: length of the live-page list of the retained observation (0: nothing retained)
     "resample_fence": 55,      # pw_resample_weighted: 0 the search reads the cdf alone, 1 a sampled fence of the cdf in LDS (A/B runs)
     "stats_lds_puzzles": 56,   # pw_episode_stats: largest set summed per workgroup in LDS, 1 .. 1024 (0 default, 2048 never)
     "stats_groups": 57,        # pw_episode_stats: most workgroups of a launch (0: one per 256 environments)

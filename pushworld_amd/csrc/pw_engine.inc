@@ -929,6 +929,7 @@ void pw_engine_destroy(PwEngine* e) {
   if (e->d_qdesc) (void)hipFree(e->d_qdesc);
   if (e->d_rec) (void)hipFree(e->d_rec);
   if (e->ret.d_live) (void)hipFree(e->ret.d_live);
+  if (e->ret.d_changed) (void)hipFree(e->ret.d_changed);  // (one allocation with d_shown)
   if (e->d_ovl) (void)hipFree(e->d_ovl);
   if (e->d_ovl_dir) (void)hipFree(e->d_ovl_dir);
   if (e->d_push_dir) (void)hipFree(e->d_push_dir);
@@ -1087,7 +1088,7 @@ static void bind_launch(PwEngine* e, hipStream_t st) {
 static void rebind_async(PwEngine* e, const int32_t* puzzle_id, int32_t batch, hipStream_t st) {
   PwBind* b = e->bind;
   if (!b || b->puzzle_id != puzzle_id || b->batch != batch) return;
-  e->ret.valid = false;  // other puzzles, other padding: the next render is a full one
+  e->ret.valid = e->ret.shown_valid = false;  // other puzzles, other padding: the next render is a full one
   if (e->ret.list_pid == puzzle_id && e->ret.list_batch == batch) (void)live_build(e, puzzle_id, batch, st, false);
   bind_launch(e, st);
   b->seg_grid = b->seg_cap;
@@ -1172,6 +1173,24 @@ static bool live_build(PwEngine* e, const int32_t* puzzle_id, int32_t batch, hip
     r.d_count = r.d_blk + blk_cap;
     r.list_cap = n_pages;
   }
+  // the arrays of the changed-page launch live and die with the list (PW_OPT_OBS_CHANGED_PAGES): one allocation, changed [batch]
+  // then shown [batch][N_pad][2].  Without them pw_step_render keeps the live launch.
+  if (r.shown_cap < batch && may_alloc) {
+    if (r.d_changed) (void)hipFree(r.d_changed);
+    r.d_changed = nullptr;
+    r.d_shown = nullptr;
+    r.shown_cap = 0;
+    r.shown_valid = false;
+    const size_t bytes = static_cast<size_t>(batch) * (8 + static_cast<size_t>(e->np) * 2);
+    if (hipMalloc(reinterpret_cast<void**>(&r.d_changed), bytes) == hipSuccess && hipMemsetAsync(r.d_changed, 0, bytes, st) == hipSuccess) {
+      r.d_shown = reinterpret_cast<int8_t*>(r.d_changed + batch);
+      r.shown_cap = batch;
+    } else {
+      (void)hipGetLastError();
+      if (r.d_changed) (void)hipFree(r.d_changed);
+      r.d_changed = nullptr;
+    }
+  }
   LiveArgs a;
   a.hdrs = e->set->d_headers;
   a.puzzle_id = puzzle_id;
@@ -1212,18 +1231,26 @@ static void retained_overwritten(PwEngine* e, const RenderArgs& ra, int32_t batc
   if (!r.valid) return;
   const uintptr_t lo = reinterpret_cast<uintptr_t>(ra.obs), hi = lo + static_cast<uint64_t>(batch) * static_cast<uint64_t>(ra.env_stride);
   const uintptr_t rlo = reinterpret_cast<uintptr_t>(r.obs), rhi = rlo + static_cast<uint64_t>(r.batch) * static_cast<uint64_t>(r.stride);
-  if (lo < rhi && rlo < hi) r.valid = false;
+  if (lo < rhi && rlo < hi) r.valid = r.shown_valid = false;
+}
+
+// a full render of (ra.puzzle_id, batch) into ra.obs establishes (or keeps) the retained observation
+static bool retained_establishes(const PwEngine* e, const RenderArgs& ra, int32_t batch) {
+  const PwRetained& r = e->ret;
+  bool owned = false;
+  for (const PwObsBuf& b : e->obs_bufs)
+    owned = owned || (b.ptr == ra.obs && static_cast<uint64_t>(batch) * static_cast<uint64_t>(ra.env_stride) <= b.bytes);
+  return r.option && owned && live_applies(e, ra.env_stride, batch) && bound_to(e, ra.puzzle_id, batch) && r.list_pid == ra.puzzle_id &&
+         r.list_batch == batch;
 }
 
 // A full render of (ra.puzzle_id, batch) into ra.obs has been launched: it establishes the retained observation where the
 // rule allows one (header, PW_OPT_OBS_PADDING_ONCE), and ends the validity of a retained buffer it wrote other bytes into.
 static void retained_after_full_render(PwEngine* e, const RenderArgs& ra, int32_t batch) {
   PwRetained& r = e->ret;
-  bool owned = false;
-  for (const PwObsBuf& b : e->obs_bufs)
-    owned = owned || (b.ptr == ra.obs && static_cast<uint64_t>(batch) * static_cast<uint64_t>(ra.env_stride) <= b.bytes);
-  if (r.option && owned && live_applies(e, ra.env_stride, batch) && bound_to(e, ra.puzzle_id, batch) &&
-      r.list_pid == ra.puzzle_id && r.list_batch == batch) {
+  if (retained_establishes(e, ra, batch)) {
+    if (!(r.valid && r.obs == ra.obs && r.stride == ra.env_stride && r.batch == batch && r.puzzle_id == ra.puzzle_id))
+      r.shown_valid = false;  // (another buffer than `shown` speaks of; the caller sets it when this render's records filled `shown`)
     r.valid = true;
     r.obs = ra.obs;
     r.stride = ra.env_stride;
@@ -1241,6 +1268,14 @@ static int retained_live_form(const PwEngine* e, const RenderArgs& ra, int32_t b
       !bound_to(e, ra.puzzle_id, batch) || r.list_pid != ra.puzzle_id || r.list_batch != batch || !live_applies(e, ra.env_stride, batch))
     return 0;
   return r.option == 2 ? 2 : (r.option == 3 ? 1 : r.form);
+}
+
+// PW_OPT_OBS_CHANGED_PAGES: the record writers of a call compare its new state with PwRetained::d_shown (and leave it there) exactly
+// when the call's render goes into the retained buffer of the retained (puzzle_id, batch), or establishes it -- so that `shown` is
+// what that buffer shows after every such call, whatever happened to `pos` in between.
+static bool retained_tracks(const PwEngine* e, const RenderArgs& ra, int32_t batch, int live_form) {
+  const PwRetained& r = e->ret;
+  return r.chg_option && r.d_changed && r.shown_cap >= batch && (live_form != 0 || retained_establishes(e, ra, batch));
 }
 
 static void launch_rowpage(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st) {
@@ -1289,11 +1324,14 @@ static void launch_rowpage(PwEngine* e, const RenderArgs& ra, int32_t batch, hip
 }
 
 // rec_ready: the group step kernel of this call already left the page records of (puzzle_id, pos) in e->d_rec
-// live_form: the caller checked (retained_live_form) that only the live pages need rendering: 1 the list, 2 the early exits
-static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready, int live_form) {
+// live_form: the caller checked (retained_live_form) that only the live pages need rendering: 1 the list, 2 the early exits, 3 the
+// list and of it the pages whose rows changed (PwRetained::d_changed, filled by the record writer of this call)
+// track: the records of this call are compared with PwRetained::d_shown (retained_tracks); a pre-pass here does it then
+static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready, int live_form, bool track) {
   const bool paged = page_path(e, ra.env_stride) && !ra.do_step && !ra.skip_movables && ensure_rec(e, batch);
   if (paged && !rec_ready) {
-    PageRecArgs pa{ra.hdrs, ra.puzzle_id, ra.pos, static_cast<PageRec*>(e->d_rec), batch, ra.np, e->set->count};
+    PageRecArgs pa{ra.hdrs, ra.puzzle_id, ra.pos, static_cast<PageRec*>(e->d_rec), batch, ra.np, e->set->count,
+                   track ? e->ret.d_shown : nullptr, track ? e->ret.d_changed : nullptr};
     hipLaunchKernelGGL(pw_page_records_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, pa);
   }
   RenderProfScope prof(e, st);
@@ -1340,8 +1378,9 @@ static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipS
       ca.live = nullptr;
       ca.live_n = nullptr;
       ca.n_live = 0;
+      ca.changed = live_form == 3 ? rt.d_changed : nullptr;
       unsigned grid = page_grid(ca.n_pages, ca.order, ca.run_log2);
-      if (live_form == 1) {
+      if (live_form == 1 || live_form == 3) {
         ca.live = rt.d_live;
         ca.live_n = rt.n_live < 0 ? rt.d_count : nullptr;  // list rebuilt in-stream: the upper bound, the surplus workgroups return
         ca.n_live = rt.n_live < 0 ? ca.n_pages : static_cast<uint32_t>(rt.n_live);
@@ -1707,7 +1746,7 @@ int pw_batch_bind(PwEngine* e, const int32_t* puzzle_id, int32_t batch, int64_t*
   if (batch <= 0 || !puzzle_id) return pw_fail(PW_EINVAL, "pw_batch_bind: puzzle_id must be a device buffer of batch > 0 ids");
   PwDeviceGuard guard(e->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  e->ret.valid = false;  // (established again by the next full render of the new binding into a buffer of pw_obs_alloc)
+  e->ret.valid = e->ret.shown_valid = false;  // (established again by the next full render of the new binding into a buffer of pw_obs_alloc)
   if (!e->d_seg_dir || e->seg_puzzles == 0) {  // nothing to bind to (PW_OPT_STEP_TABLES never): every call stays unbound
     if (hipStreamSynchronize(st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_batch_bind: stream synchronisation failed");
     release_bind(e);
@@ -1786,7 +1825,7 @@ int pw_batch_bind(PwEngine* e, const int32_t* puzzle_id, int32_t batch, int64_t*
 
 int pw_batch_unbind(PwEngine* e) try {
   if (!e) return pw_fail(PW_EINVAL, "null engine");
-  e->ret.valid = false;
+  e->ret.valid = e->ret.shown_valid = false;
   if (!e->bind) return PW_OK;
   // (its resident kernel may be running the binding's segments -- and the synchronisation below would wait for its idle limit)
   if (e->mailbox) return pw_fail(PW_EINVAL, "pw_batch_unbind: this engine has an open mailbox (pw_mailbox_close first)");
@@ -1806,8 +1845,10 @@ int pw_render(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* ob
   RenderArgs ra;
   int rc = fill_render_args(e, puzzle_id, pos, obs, env_stride_bytes, batch, &ra);
   if (rc != PW_OK) return rc;
-  launch_render(e, ra, batch, static_cast<hipStream_t>(stream));
+  const bool track = retained_tracks(e, ra, batch, 0);
+  launch_render(e, ra, batch, static_cast<hipStream_t>(stream), false, 0, track);
   retained_after_full_render(e, ra, batch);  // (every byte is written: the repair path of a retained buffer)
+  if (track) e->ret.shown_valid = true;
   return check_launch("pw_render");
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
@@ -1839,11 +1880,18 @@ int pw_step_render(PwEngine* e, const int32_t* puzzle_id, const uint8_t* actions
     StepArgs s1 = sa;
     attach_binding(e, &s1);
     if (page_path(e, env_stride_bytes) && ensure_rec(e, batch)) s1.rec = static_cast<PageRec*>(e->d_rec);
-    const bool rec_ready = launch_one_step(e, s1, batch, st);
-    // a retained buffer (PW_OPT_OBS_PADDING_ONCE) holds its frame padding already: the pages with anything else only
+    // a retained buffer (PW_OPT_OBS_PADDING_ONCE) holds its frame padding already: the pages with anything else only -- and of
+    // those (PW_OPT_OBS_CHANGED_PAGES) only the ones whose rows differ from the positions the buffer is known to show
     const int live_form = retained_live_form(e, ra, batch);
-    launch_render(e, ra, batch, st, rec_ready, live_form);
+    const bool track = retained_tracks(e, ra, batch, live_form);
+    if (track) {
+      s1.shown = e->ret.d_shown;
+      s1.changed = e->ret.d_changed;
+    }
+    const bool rec_ready = launch_one_step(e, s1, batch, st);
+    launch_render(e, ra, batch, st, rec_ready, (live_form && track && e->ret.shown_valid) ? 3 : live_form, track);
     if (!live_form) retained_after_full_render(e, ra, batch);
+    if (track) e->ret.shown_valid = true;  // (whichever form: the record writer left the new positions in `shown`)
     return check_launch("pw_step_render");
   }
   ra.step = sa;
@@ -1896,6 +1944,7 @@ int pw_step_render_delta(PwEngine* e, const int32_t* puzzle_id, const uint8_t* a
   if (rc != PW_OK) return rc;
   // (the redraw of the retained batch stays inside its puzzles' own rows; that of other ids or another layout need not)
   if (!(e->ret.obs == obs && e->ret.stride == env_stride_bytes && e->ret.batch == batch && e->ret.puzzle_id == puzzle_id)) retained_overwritten(e, ra, batch);
+  else e->ret.shown_valid = false;  // (pixels change here that `shown` is not told about: the next pw_step_render takes the live launch)
   if (e->dirty_cap < batch) {
     if (e->d_dirty) (void)hipFree(e->d_dirty);
     e->d_dirty = nullptr;
@@ -2204,17 +2253,17 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
       return PW_OK;
     case PW_OPT_FUSED_STEP_RENDER:
       e->force_fused = value != 0;
-      e->ret.valid = false;
+      e->ret.valid = e->ret.shown_valid = false;
       return PW_OK;
     case PW_OPT_RENDER_KERNEL:
       if (value < 0 || value > 1) return pw_fail(PW_EINVAL, "PW_OPT_RENDER_KERNEL: 0 automatic, 1 per-environment LDS kernel");
       e->force_lds_render = value != 0;
-      e->ret.valid = false;
+      e->ret.valid = e->ret.shown_valid = false;
       return PW_OK;
     case PW_OPT_PAGE_SLICE_ENVS:
       if (value < 0) return pw_fail(PW_EINVAL, "PW_OPT_PAGE_SLICE_ENVS must be >= 0");
       e->page_slice_envs = value;
-      e->ret.valid = false;
+      e->ret.valid = e->ret.shown_valid = false;
       return PW_OK;
     case PW_OPT_SEARCH_CHUNK:
       if (value < 0) return pw_fail(PW_EINVAL, "PW_OPT_SEARCH_CHUNK must be >= 0");
@@ -2370,7 +2419,12 @@ int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value) try {
       if (value < 0 || value > 3)
         return pw_fail(PW_EINVAL, "PW_OPT_OBS_PADDING_ONCE: 0 off, 1 on (2 / 3: on, with the early-exit / the list form of the live launch)");
       e->ret.option = static_cast<int>(value);
-      e->ret.valid = false;  // (established by the next full render)
+      e->ret.valid = e->ret.shown_valid = false;  // (established by the next full render)
+      return PW_OK;
+    case PW_OPT_OBS_CHANGED_PAGES:
+      if (value != 0 && value != 1) return pw_fail(PW_EINVAL, "PW_OPT_OBS_CHANGED_PAGES: 0 the live launch, 1 the changed pages of it only");
+      e->ret.chg_option = static_cast<int>(value);
+      e->ret.shown_valid = false;  // (the next pw_step_render into the retained buffer takes the live launch and fills `shown`)
       return PW_OK;
     case PW_OPT_RESAMPLE_FENCE:
       if (value != 0 && value != 1) return pw_fail(PW_EINVAL, "PW_OPT_RESAMPLE_FENCE: 0 the search reads the cdf alone, 1 a fence in LDS");
@@ -2468,6 +2522,7 @@ int64_t pw_engine_get_option(const PwEngine* e, int32_t option) try {
     case PW_OPT_TUNED_NS: return e->tuned_ns;
     case PW_OPT_PAGE_LOAD_ALL: return e->page_load_all;
     case PW_OPT_OBS_PADDING_ONCE: return e->ret.option;
+    case PW_OPT_OBS_CHANGED_PAGES: return e->ret.chg_option;
     case PW_OPT_RESAMPLE_FENCE: return e->resample_fence;
     case PW_OPT_STATS_LDS_PUZZLES: return e->stats_lds_puzzles;
     case PW_OPT_STATS_GROUPS: return e->stats_groups;
@@ -2661,7 +2716,16 @@ int pw_engine_tune_render(PwEngine* e, const int32_t* puzzle_id, const int8_t* p
   PwDeviceGuard guard(e->set->device);
   int best = 0;
   rc = tune_render_impl(e, ra, batch, static_cast<hipStream_t>(stream), &best);
-  if (rc == PW_OK) retained_after_full_render(e, ra, batch);
+  if (rc == PW_OK) {
+    retained_after_full_render(e, ra, batch);
+    e->ret.shown_valid = false;
+    if (retained_tracks(e, ra, batch, 0)) {  // `obs` shows `pos`: say so in `shown` (the records are the ones the tuner left)
+      PageRecArgs pa{ra.hdrs, ra.puzzle_id, ra.pos, static_cast<PageRec*>(e->d_rec), batch, ra.np, e->set->count, e->ret.d_shown, e->ret.d_changed};
+      hipLaunchKernelGGL(pw_page_records_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), pa);
+      if (int rc2 = check_launch("pw_engine_tune_render")) return rc2;
+      e->ret.shown_valid = true;
+    }
+  }
   return rc != PW_OK ? rc : best;
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
@@ -2820,7 +2884,7 @@ int pw_obs_free(PwEngine* e, void* obs) try {
     PwDeviceGuard guard(e->set->device);
     (void)hipDeviceSynchronize();  // nothing in flight may still write the buffer
     if (e->ret.obs == obs) {
-      e->ret.valid = false;
+      e->ret.valid = e->ret.shown_valid = false;
       e->ret.obs = nullptr;
     }
     release_obs_buf(e->obs_bufs[i]);

@@ -143,6 +143,14 @@ struct PwRetained {
   int order, run_log2, lds_pad_kb, load_all;
   int form;                  // 1 list, 2 early exit: the faster one in the tuner's measurement (1 when never measured)
   int64_t list_ns, exit_ns;  // nanoseconds per launch of the two forms in that configuration (0: never measured)
+  // the changed-page launch (PW_OPT_OBS_CHANGED_PAGES): what the buffer shows, so that a step renders only the live pages whose
+  // pixel rows differ from it.  Allocated with the list (never on a step path); without them the engine keeps the live launch.
+  int chg_option;            // PW_OPT_OBS_CHANGED_PAGES: 0 off, 1 on
+  int8_t* d_shown;           // [shown_cap][N_pad] int8 pairs, laid out like pos: the positions whose picture `obs` holds
+  uint64_t* d_changed;       // [shown_cap]: bit y = grid row y may show other pixels than `obs` holds (written by every record writer
+                             // of a call that renders into `obs`, read by that call's render)
+  int64_t shown_cap;         // environments the two arrays hold
+  bool shown_valid;          // d_shown holds exactly the positions whose picture `obs` holds (implies valid)
 };
 
 struct PwEngine {

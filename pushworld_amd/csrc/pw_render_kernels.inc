@@ -32,7 +32,7 @@ struct RenderArgs {
   StepArgs step;
 };
 
-static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready = false, int live_form = 0);
+static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready = false, int live_form = 0, bool track = false);
 
 // LDS layout of the render kernels (dynamic):
 //   [0, 16)        8 zero guard entries in front of E
@@ -228,6 +228,9 @@ struct CopyArgs {
   const uint32_t* live_n;    // device-side length of `live` when the host does not know it (list rebuilt in-stream: the grid is
                              // the upper bound n_pages and the workgroups beyond the count return), else NULL
   uint32_t n_live;           // length of `live` as the host knows it (ignored with live_n)
+  // changed-page launch (kLive = 3, PW_OPT_OBS_CHANGED_PAGES): the list form, and a workgroup returns when none of its page's pixel
+  // rows differs from what the buffer holds
+  const uint64_t* changed;   // [batch] bit y: grid row y of the environment may show other pixels than the buffer (pw_shown_rows)
 };
 
 // grid of a page-ordered launch over n indices: orders 1 and 2 permute a rounded-up index range; the surplus workgroups exit
@@ -248,6 +251,8 @@ struct PageRecArgs {
   int32_t batch;
   int32_t np;
   int32_t num_puzzles;
+  int8_t* shown;      // PW_OPT_OBS_CHANGED_PAGES (StepArgs::shown / changed), or both NULL
+  uint64_t* changed;
 };
 
 __global__ __launch_bounds__(256) void pw_page_records_kernel(PageRecArgs a) {
@@ -269,6 +274,8 @@ __global__ __launch_bounds__(256) void pw_page_records_kernel(PageRecArgs a) {
   r.reserved = 0;
   r.rows = rows;
   a.out[env] = r;
+  if (a.changed)
+    pw_shown_update(row, a.shown + static_cast<int64_t>(env) * a.np * 2, a.changed + env, h.N, [&](int j) { return static_cast<int>(h.objtab[j].h); });
 }
 
 // ------------------------------------------------------------------------------------
@@ -510,7 +517,8 @@ __device__ __forceinline__ bool page_tail_head_padding(const PageGeom& g0, const
 // kLive (PW_OPT_OBS_PADDING_ONCE, pw_step_render into a retained buffer whose frame padding is known to be written): 1 = the
 // page order is applied to the index into the list of live pages, and the workgroup renders page live[i]; 2 = the grid of the
 // full render, and the workgroups of padding pages return before they load or store anything (the comparison variant).  The
-// pages that are rendered run the same code either way.
+// pages that are rendered run the same code either way.  3 (PW_OPT_OBS_CHANGED_PAGES) = the list form, and the workgroups of pages
+// none of whose pixel rows changed since the buffer was last written (CopyArgs::changed) return before any vector load or store.
 template <typename T, int kTag = 0, bool kLoadAll = false, int kLive = 0>
 __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyArgs ca) {
   typedef pw_u32x4 u32x4;
@@ -526,7 +534,7 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
   // ---- workgroup-uniform bookkeeping -------------------------------------------------------------
   uint32_t page = blockIdx.x;
   uint32_t n_sweep = ca.n_pages;  // indices the page order permutes
-  if (kLive == 1) {
+  if (kLive == 1 || kLive == 3) {
     n_sweep = ca.n_live;
     if (ca.live_n) {
       n_sweep = *ca.live_n;
@@ -543,7 +551,7 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
     page = ((((j >> sb) << 3) + k) << sb) | (j & ((1u << sb) - 1u));
   }
   if (page >= n_sweep) return;
-  if (kLive == 1) page = ca.live[page];
+  if (kLive == 1 || kLive == 3) page = ca.live[page];
   const uint32_t g0 = page * 256u;  // first 16-byte chunk of the page
   const uint32_t cpe = ca.chunks_per_env;
   // g0 / cpe without an integer division: float estimate (exact to +-1 for g0 < 2^31) + correction
@@ -559,12 +567,15 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
   uint8_t* dst = a.obs + static_cast<int64_t>(g0) * 16 + lane * 16;
   const PageRec r0 = ca.rec[env0];  // ONE scalar load: puzzle, frame geometry, rows with movables
   const PageGeom g = page_geom<ES>(a, r0);
+  uint64_t ch0 = 0ull;  // (kLive = 3: scalar loads next to the record's)
+  if (kLive == 3) ch0 = ca.changed[env0];
 
   if (c_first + 256 <= static_cast<int>(ca.n_chunks)) {
     // ---- 13 of 14 pages: the whole page lies inside one environment's image ----------------------
     const u32x4 zero = u32x4{0u, 0u, 0u, 0u};
     u32x4 v0 = zero, v1 = zero, v2 = zero, v3 = zero;
     if (kLive == 2 && page_chunks_padding(g, c_first, c_first + 256)) return;
+    if (kLive == 3 && page_rows_hit(ch0, (c_first * 16) / ES, (c_first * 16 + 4096) / ES, g.shift, ca.magic_cellrow) == 0ull) return;
     if (!kLoadAll && (c_first + 256 <= g.nz_lo || c_first >= g.nz_hi)) {  // frame padding above / below the puzzle: no loads at all
       PAGE_STORE(v0, dst);
       PAGE_STORE(v1, dst + 1024);
@@ -620,6 +631,13 @@ __global__ __launch_bounds__(64) void pw_render_page_kernel(RenderArgs a, CopyAr
   const PageRec r1 = ca.rec[env1];
   const PageGeom g1 = page_geom<ES>(a, r1);
   if (kLive == 2 && page_tail_head_padding(g, g1, c_first, split, static_cast<int>(ca.n_chunks), has_second)) return;
+  if (kLive == 3) {  // neither environment's changed rows reach the page: it holds what it has to
+    const uint64_t ch1 = ca.changed[env1];
+    const int l0 = (c_first * 16) / ES, l1 = (-split * 16) / ES;
+    if (page_rows_hit(ch0, l0, l0 + 4096 / ES, g.shift, ca.magic_cellrow) == 0ull &&
+        !(has_second && page_rows_hit(ch1, l1, l1 + 4096 / ES, g1.shift, ca.magic_cellrow) != 0ull))
+      return;
+  }
   const int valid0 = static_cast<int>(ca.n_chunks) - c_first;  // local chunks [0, valid0) of env0 carry image bytes
   const uint8_t* src0 = ca.simg + static_cast<int64_t>(r0.pid) * ca.simg_stride + static_cast<int64_t>(c_first) * 16;
   const uint8_t* src1 = ca.simg + static_cast<int64_t>(r1.pid) * ca.simg_stride - static_cast<int64_t>(split) * 16;
@@ -675,6 +693,7 @@ template <typename T, int kTag, bool kLoadAll>
 static void launch_page_form(int live_form, unsigned grid, size_t lds_pad, hipStream_t st, const RenderArgs& rp, const CopyArgs& ca) {
   if (live_form == 1) hipLaunchKernelGGL((pw_render_page_kernel<T, kTag, kLoadAll, 1>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
   else if (live_form == 2) hipLaunchKernelGGL((pw_render_page_kernel<T, kTag, kLoadAll, 2>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
+  else if (live_form == 3) hipLaunchKernelGGL((pw_render_page_kernel<T, kTag, kLoadAll, 3>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
   else hipLaunchKernelGGL((pw_render_page_kernel<T, kTag, kLoadAll, 0>), dim3(grid), dim3(64), lds_pad, st, rp, ca);
 }
 

@@ -435,6 +435,38 @@ __device__ __forceinline__ void seg_run(const RolloutArgs& r, const SegPuzzle& z
     rec.reserved = 0;
     rec.rows = m;
     a.rec[env] = rec;
+    if (a.changed) {  // PW_OPT_OBS_CHANGED_PAGES: the rows in which the new state differs from what the retained buffer shows
+      uint32_t* srow = reinterpret_cast<uint32_t*>(a.shown) + static_cast<int64_t>(env) * (NP / 2);
+      uint32_t S[NP / 2];  // (loaded here, after the step: the single-step launch is bound by its registers)
+      if constexpr (NP == 4) {
+        const uint2 v = *reinterpret_cast<const uint2*>(srow);
+        S[0] = v.x, S[1] = v.y;
+      } else {
+#pragma unroll
+        for (int k = 0; k < NP / 8; k++) {
+          const uint4 v = reinterpret_cast<const uint4*>(srow)[k];
+          S[4 * k] = v.x, S[4 * k + 1] = v.y, S[4 * k + 2] = v.z, S[4 * k + 3] = v.w;
+        }
+      }
+      uint64_t c = 0;
+#pragma unroll
+      for (int k = 0; k < NP / 2; k++) {
+        if (2 * k < z.N && S[k] != P[k]) {
+          c |= pw_shown_rows(S[k], P[k], static_cast<int>((z.obj[2 * k] >> 8) & 0xffu));
+          if (2 * k + 1 < z.N) c |= pw_shown_rows(S[k] >> 16, P[k] >> 16, static_cast<int>((z.obj[2 * k + 1] >> 8) & 0xffu));
+        }
+      }
+      a.changed[env] = c;
+      if (c) {
+        if constexpr (NP == 4) {
+          *reinterpret_cast<uint2*>(srow) = make_uint2(P[0], P[1]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < NP / 8; k++)
+            reinterpret_cast<uint4*>(srow)[k] = make_uint4(P[4 * k], P[4 * k + 1], P[4 * k + 2], P[4 * k + 3]);
+        }
+      }
+    }
   }
   a.term[env] = static_cast<uint8_t>(term);
   a.trunc[env] = static_cast<uint8_t>(trunc);

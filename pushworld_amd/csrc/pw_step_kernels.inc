@@ -160,7 +160,43 @@ struct StepArgs {
   uint32_t* bind_mismatch;       // engine-owned: environments whose puzzle id no longer is the one they were bound to
   int32_t seg_grid;              // workgroups of the segment role at the front of a fused launch (>= the number of segments)
   int32_t mseg_spread;           // pw_step_mseg_kernel / the lane role of pw_step_segm_kernel: 64 >> this environments per wavefront
+  // PW_OPT_OBS_CHANGED_PAGES (looked at only where `rec` is written; both NULL otherwise): the positions the retained observation
+  // buffer shows, laid out like pos, and per environment the grid rows in which the new state differs from them (pw_shown_rows)
+  int8_t* shown;
+  uint64_t* changed;
 };
+
+// Grid rows whose pixels may differ between a movable of height h at the packed position `was` (x | y << 8, int8 each) and the
+// same movable at `now`: its rows before and after; every row when a position lies outside the 64 rows a mask can name (any
+// position is accepted from a caller, include/pushworld_amd.h pw_validate_state).  Zero when the two are equal.
+__device__ __forceinline__ uint64_t pw_shown_rows(uint32_t was, uint32_t now, int h) {
+  if (((was ^ now) & 0xffffu) == 0u) return 0ull;
+  const int y0 = static_cast<int8_t>((was >> 8) & 0xffu), y1 = static_cast<int8_t>((now >> 8) & 0xffu);
+  if (static_cast<unsigned>(y0) >= 64u || static_cast<unsigned>(y1) >= 64u) return ~0ull;
+  const uint64_t m = h >= 64 ? ~0ull : ((1ull << h) - 1ull);
+  return (m << y0) | (m << y1);
+}
+
+// The record writers' part of PW_OPT_OBS_CHANGED_PAGES for a lane that owns a whole environment and has stored its new state:
+// `pos` / `shown` = the environment's rows of np int8 pairs, `height(j)` = height of movable j in cells (j < n <= np).  Leaves
+// the rows that differ from what the retained buffer shows in *changed and, when there are any, the new positions in `shown`.
+// Everything is loaded here, after the step: nothing of it is live across the step.  (The slots beyond n are never compared.)
+template <typename Height>
+__device__ __forceinline__ void pw_shown_update(const int8_t* pos, int8_t* shown, uint64_t* changed, int n, Height height) {
+  const uint32_t* prow = reinterpret_cast<const uint32_t*>(pos);
+  uint32_t* srow = reinterpret_cast<uint32_t*>(shown);
+  uint64_t m = 0;
+  for (int k = 0; 2 * k < n; k++) {
+    const uint32_t s = srow[k], p = prow[k];
+    if (s != p) {
+      m |= pw_shown_rows(s, p, height(2 * k));
+      if (2 * k + 1 < n) m |= pw_shown_rows(s >> 16, p >> 16, height(2 * k + 1));
+    }
+  }
+  *changed = m;
+  if (m)
+    for (int k = 0; 2 * k < n; k++) srow[k] = prow[k];
+}
 
 // Throughput counters (pw_counters): every wavefront adds what its environments did to ONE of 64 slots (64 bytes apart, so
 // the atomics of a launch spread over 64 L2 lines instead of queueing on one address); env-steps always, the other two
@@ -1560,6 +1596,19 @@ __device__ __forceinline__ void step_group_body(const RolloutArgs& r, const int 
       rec.rows = m;
       a.rec[env] = rec;
     }
+    if (a.changed) {  // PW_OPT_OBS_CHANGED_PAGES: every lane compares its own movables with what the retained buffer shows
+      uint16_t* srow = reinterpret_cast<uint16_t*>(a.shown) + static_cast<int64_t>(env) * a.np;
+      uint64_t c = 0;
+      if (lj < N) c = pw_shown_rows(srow[lj], static_cast<uint32_t>(xy), static_cast<int>((ot >> 8) & 0xffu));
+      if (has1) c |= pw_shown_rows(srow[lj1], static_cast<uint32_t>(xy1), static_cast<int>((ot1 >> 8) & 0xffu));
+#pragma unroll
+      for (int o = GS / 2; o > 0; o >>= 1) c |= __shfl_xor(c, o, GS);
+      if (c) {
+        if (lj < N) srow[lj] = static_cast<uint16_t>(xy);
+        if (has1) srow[lj1] = static_cast<uint16_t>(xy1);
+      }
+      if (lj == 0) a.changed[env] = c;
+    }
   }
   if (lj == 0) {
     a.term[env] = static_cast<uint8_t>(term);
@@ -1898,6 +1947,11 @@ __device__ __forceinline__ void step_quad16_body(const StepArgs& a, const int en
     rec.reserved = 0;
     rec.rows = m;
     a.rec[env] = rec;
+    if (a.changed) {  // PW_OPT_OBS_CHANGED_PAGES (from the state as stored above and the puzzle header: no register array is indexed)
+      const PwObjEntry* objtab = a.hdrs[pid].objtab;
+      pw_shown_update(a.pos + static_cast<int64_t>(env) * a.np * 2, a.shown + static_cast<int64_t>(env) * a.np * 2, a.changed + env, N,
+                      [&](int j) { return static_cast<int>(objtab[j].h); });
+    }
   }
   a.term[env] = static_cast<uint8_t>(term);
   a.trunc[env] = static_cast<uint8_t>(trunc);

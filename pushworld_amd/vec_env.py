@@ -199,9 +199,13 @@ class VecPushWorld:
             owned = False
             # a library-owned buffer of a bound batch with a fixed assignment keeps its frame padding: steps render the live pages only
             padding_once = self._bind and not resample and "obs_padding_once" not in (engine_options or {})
+            # ... and of those only the pages whose pixel rows a step changed (with neither key given: the library's choice too)
+            changed_pages = padding_once and "obs_changed_pages" not in (engine_options or {})
             if tune and tune_allocations:
                 if padding_once:
                     self.engine.set_option("obs_padding_once", 1)  # (before the tuner: it measures the live launch too)
+                if changed_pages:
+                    self.engine.set_option("obs_changed_pages", 1)
                 # library-owned buffer: candidates are tuned on the initial states (reset() draws them again)
                 self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, None)
                 try:
@@ -218,6 +222,8 @@ class VecPushWorld:
             if not owned:
                 if padding_once:
                     self.engine.set_option("obs_padding_once", 0)
+                if changed_pages:
+                    self.engine.set_option("obs_changed_pages", 0)
                 self._obs_storage, self.obs = self.engine.alloc_obs(self.num_envs)
                 if tune:
                     self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, None)
