@@ -1653,6 +1653,57 @@ int pw_push_solve_batch_query(PwPushSolveBatch* b, const int32_t* puzzle_id, con
                               int32_t n, int32_t* index, int32_t* cost, int8_t* push_from, uint8_t* push_action, int32_t* walk,
                               int8_t* action, void* stream);
 
+/* Drawing from the batched tables over pushes (csrc/pw_push_batch_sample.inc, K26): pw_push_search_table_index / _sample / _plans
+ * / _emit for a PwPushSolveBatch whose last run stored tables -- the cost index of every stored item, and ONE launch per call for
+ * a mixed batch however many puzzles it holds.  A node's key is its canonical state, so states are read off the keys.
+ *
+ * pw_push_solve_batch_index: the cost index of every stored item, built on demand, idempotent; the next pw_push_solve_batch_run
+ *   and the destroy discard it.  Per stored item with S states and largest finite cost mc:
+ *     states_by_cost int32 [S]       a permutation of the item's state numbers: cost 0, 1, ... mc, then the dead ends
+ *     cost_start     uint32 [mc + 3] bucket c = states_by_cost[cost_start[c] .. cost_start[c + 1]), the dead ends are bucket
+ *                                    mc + 1, cost_start[mc + 2] = S; mc = -1: [0, S].  Empty buckets occur (a store without goal
+ *                                    states has no state of cost 0).
+ *   Inside a bucket the states ascend by their 64-BIT KEY: state numbers inside a layer are the schedule's, the key is not, so
+ *   position p of a bucket holds the same STATE in every run and a draw is a function of (puzzle, start, seed, environment,
+ *   count) as a state.  Allocates (4 bytes per stored state and per bucket, 16 per item; a workspace of 32 bytes per state
+ *   plus the sorts' own is freed on return) and synchronises `stream`.
+ * pw_push_solve_batch_index_read: one item's two arrays into device buffers (either may be NULL), asynchronous.
+ * pw_push_solve_batch_sample: pw_push_search_table_sample's arguments and semantics with puzzle_id required; one thread per
+ *   environment, no allocation, no synchronisation (capturable).  The item is the one pw_push_solve_batch_query answers from
+ *   (a puzzle listed twice: its higher item).  Masked environments and environments whose puzzle has no stored item are left
+ *   ENTIRELY untouched, the counter included.  The band is clamped to 0 .. mc of the environment's own item, dead ends are never
+ *   drawn; an item without a finite cost or an empty band gives out_state = out_cost = -1, nothing else written, the counter
+ *   not advanced.  Otherwise counter[i] += 1, r = mix64(seed ^ PW_TABLE_K_SAMPLE, i, counter[i]), u = floor(r * count / 2^64),
+ *   the state is states_by_cost[cost_start[lo] + u]: pos[i] = its key unpacked (the agent at canon, zeros from the puzzle's N
+ *   to npad - 1; 8- or 16-byte stores), steps = 0, term = trunc = 0 (either may be NULL), out_state = the state within the item
+ *   (what pw_push_solve_batch_query returns for it), out_cost = its cost.
+ * pw_push_solve_batch_plans: pw_push_search_table_plans' arguments with puzzle_id required; no index needed; one thread per
+ *   item.  tie 0: row row_off[state] + best[state]; tie 1: the j-th optimal row in row order, j = floor(mix64(seed ^
+ *   PW_TABLE_K_PLAN, item, t) * k / 2^64) of k.  A goal row ends the plan whatever its succ.  plan_len = the cost; -1 for an
+ *   index outside the item, a dead end or a puzzle without a stored item; -2 for a cost beyond plan_cap (nothing else written).
+ * pw_push_solve_batch_emit: pw_push_search_table_emit's arguments with puzzle_id required; one thread per (item, step).  Row
+ *   offset[i] + t: row_item, row_t, row_state (within the item), row_from, row_action, row_cost = plan_len - t, and row_pos --
+ *   for t = 0 pos[i] (pos NULL: the unpacked key of plan_state[i][0]), for t > 0 the movables of the key of plan_state[i][t]
+ *   with the agent's pair replaced by plan_from[i][t - 1] displaced by plan_action[i][t - 1].  Rows at or beyond rows_cap and
+ *   rows whose plan_state lies outside the item are counted into `dropped`; items of puzzles without a stored item are skipped.
+ * Argument checks (PW_EINVAL before any launch, naming the function): those of the pw_push_search_table_* calls, null
+ * puzzle_id, no run yet, nothing stored (pools of size 0, or no stored item), sample / index_read without an index, npad below
+ * the set's movables. */
+int pw_push_solve_batch_index(PwPushSolveBatch* b, void* stream);
+int pw_push_solve_batch_index_read(PwPushSolveBatch* b, int32_t item, int32_t* states_by_cost, uint32_t* cost_start, void* stream);
+int pw_push_solve_batch_sample(PwPushSolveBatch* b, const int32_t* puzzle_id, const uint8_t* mask, int32_t n, int32_t npad,
+                               uint64_t seed, uint32_t* counter, int32_t lo, int32_t hi, const int32_t* lo_n, const int32_t* hi_n,
+                               int8_t* pos, int32_t* steps, uint8_t* term, uint8_t* trunc, int32_t* out_state, int32_t* out_cost,
+                               void* stream);
+int pw_push_solve_batch_plans(PwPushSolveBatch* b, const int32_t* index, const int32_t* puzzle_id, const uint8_t* mask, int32_t n,
+                              int32_t tie, uint64_t seed, int8_t* plan_from, uint8_t* plan_action, int32_t* plan_state,
+                              int32_t plan_cap, int32_t* plan_len, void* stream);
+int pw_push_solve_batch_emit(PwPushSolveBatch* b, const int32_t* puzzle_id, const uint8_t* mask, int32_t n, int32_t npad,
+                             const int8_t* plan_from, const uint8_t* plan_action, const int32_t* plan_state, int32_t plan_cap,
+                             const int32_t* plan_len, const int8_t* pos, const int64_t* offset, int64_t rows_cap,
+                             int32_t* row_item, int32_t* row_t, int32_t* row_state, int8_t* row_from, uint8_t* row_action,
+                             int32_t* row_cost, int8_t* row_pos, uint32_t* dropped, void* stream);
+
 /* Best-first search over pushes (pw_push_planner_*, K17) of MANY puzzles or live states in ONE launch
  * (csrc/pw_push_plan_batch.inc, K24), in the form of pw_plan_batch: persistent workgroups of one wavefront take items off a
  * device counter and run the whole search of an item -- pop, the floods, the push rows, the closed set, the goal test, RGD, push

@@ -286,6 +286,16 @@ SIGNATURES = {
                                               c_void_p]),
     "pw_push_solve_batch_query": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pw_push_solve_batch_index": (c_int, [c_void_p, c_void_p]),
+    "pw_push_solve_batch_index_read": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pw_push_solve_batch_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_int32,
+                                           c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    "pw_push_solve_batch_plans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_uint64, c_void_p,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pw_push_solve_batch_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "pw_push_planner_create": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int64, POINTER(c_void_p)]),
     "pw_push_planner_destroy": (None, [c_void_p]),
     "pw_push_planner_begin": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -467,6 +467,7 @@ struct PageRec {
 #include "pw_push_table.inc"
 #include "pw_push_table_sample.inc"
 #include "pw_push_solution_batch.inc"
+#include "pw_push_batch_sample.inc"
 #include "pw_push_planner.inc"
 #include "pw_push_plan_batch.inc"
 #include "pw_curriculum.inc"

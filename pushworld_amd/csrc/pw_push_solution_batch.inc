@@ -768,7 +768,27 @@ struct PwPushSolveBatch {
   std::vector<uint8_t> h_status;
   std::vector<int32_t> h_summary;
   std::vector<int64_t> h_state_off, h_row_off;
+  // the cost index of the stored items (pw_push_batch_sample.inc, K26): built on demand, gone with the next run
+  bool index_valid;
+  int32_t* d_states_by_cost;  // the stored items' states one after the other: item i's at h_ix_off[i]
+  uint32_t* d_cost_start;     // ragged: item i's max_cost + 3 words at h_cs_off[i]
+  int64_t* d_ix_off;          // [n] each, -1: nothing stored
+  int64_t* d_cs_off;
+  std::vector<int64_t> h_ix_off, h_cs_off;
+  int32_t index_max_cost;     // the largest max_cost over the stored items (-1: none)
 };
+
+static void push_solve_batch_index_discard(PwPushSolveBatch* b) {
+  void* bufs[] = {b->d_states_by_cost, b->d_cost_start, b->d_ix_off, b->d_cs_off};
+  for (void* p : bufs)
+    if (p) (void)hipFree(p);
+  b->d_states_by_cost = nullptr;
+  b->d_cost_start = nullptr;
+  b->d_ix_off = nullptr;
+  b->d_cs_off = nullptr;
+  b->index_valid = false;
+  b->index_max_cost = -1;
+}
 
 static int push_solve_batch_host_copies(PwPushSolveBatch* b, hipStream_t st, const char* fn) {
   if (b->host_valid) return PW_OK;
@@ -817,6 +837,7 @@ void pw_push_solve_batch_destroy(PwPushSolveBatch* b) {
   if (!b) return;
   PwDeviceGuard guard(b->eng->set->device);
   push_solve_batch_free_items(b);
+  push_solve_batch_index_discard(b);
   void* bufs[] = {b->d_key, b->d_srow, b->d_cost, b->d_best, b->d_succ, b->d_from, b->d_action, b->d_flags, b->d_item_of_puzzle, b->d_counters};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
@@ -872,6 +893,7 @@ int pw_push_solve_batch_run(PwPushSolveBatch* b, const int32_t* puzzles, const i
   PwDeviceGuard guard(e->set->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   b->host_valid = false;
+  if (b->index_valid || b->d_states_by_cost) push_solve_batch_index_discard(b);  // (the index is of the last run's tables)
   if (n > b->n_cap) {  // the per-item arrays and the lookup pool (4 slots per state + 16 per item always hold what the states hold)
     if (hipStreamSynchronize(st) != hipSuccess) return pw_fail(PW_EDEVICE, "pw_push_solve_batch_run: stream error");
     push_solve_batch_free_items(b);

@@ -1976,6 +1976,84 @@ def encode_push_choice(push_from: torch.Tensor, push_action: torch.Tensor, map_h
     return torch.where(inside, (a * int(map_h) + y) * int(map_w) + x, torch.full_like(a, -1))
 
 
+def _push_plans_call(table, ids_optional: bool, index, puzzle_id, mask, tie, seed, plan_cap, out) -> PushPlans:
+    """The checks and the one launch of ``PushSolutionTable.plans`` / ``PushSolutionTableBatch.plans``."""
+    device = table.device
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1:
+        raise ValueError("index must be an int32 tensor [n] (store indices, as query returns them)")
+    n = int(index.shape[0])
+    if n < 1 or n >= 1 << 31:
+        raise ValueError("index must hold 1 .. 2^31 - 1 items")
+    _dev_tensor("index", index, torch.int32, (n,), device)
+    _dev_tensor("puzzle_id", puzzle_id, torch.int32, (n,), device, optional=ids_optional)
+    _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
+    if tie not in TABLE_TIES:
+        raise ValueError("tie must be 'lowest' or 'uniform'")
+    plan_cap = int(plan_cap)
+    if not 1 <= plan_cap <= _capi.PLAN_MAX_ACTIONS:
+        raise ValueError(f"plan_cap must be in 1 .. {_capi.PLAN_MAX_ACTIONS}")
+    out = _push_plans_outputs(out, n, plan_cap, device)
+    table._plans_launch(index, puzzle_id, mask, n, TABLE_TIES[tie], seed, out.push_from, out.push_action, out.state, plan_cap,
+                        out.length)
+    return out
+
+
+def _push_rows_call(table, ids_optional: bool, plans, pos, puzzle_id, mask, rows_cap, offset, out) -> PushRows:
+    """The checks and the one launch of ``PushSolutionTable.demonstration_rows`` / ``PushSolutionTableBatch.demonstration_rows``."""
+    device = table.device
+    if not isinstance(plans, (tuple, list)) or len(plans) != 4 or not isinstance(plans[3], torch.Tensor) \
+            or plans[3].dim() != 1 or not isinstance(plans[1], torch.Tensor) or plans[1].dim() != 2:
+        raise ValueError("plans must be the PushPlans of a plans call")
+    n, plan_cap = int(plans[3].shape[0]), int(plans[1].shape[1])
+    if n < 1 or plan_cap < 1:
+        raise ValueError("plans must hold at least one item and one step")
+    plans = _push_plans_outputs(plans, n, plan_cap, device)
+    _dev_tensor("pos", pos, torch.int8, (n, table.npad, 2), device, optional=True)
+    _dev_tensor("puzzle_id", puzzle_id, torch.int32, (n,), device, optional=ids_optional)
+    _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
+    if offset is None:
+        lens = plans.length.clamp(min=0).to(torch.int64)
+        if mask is not None:
+            lens = lens * (mask != 0)
+        if puzzle_id is not None:
+            lens = lens * table.covers(puzzle_id)
+        offset = torch.zeros((n + 1,), dtype=torch.int64, device=device)
+        torch.cumsum(lens, 0, out=offset[1:])
+    _dev_tensor("offset", offset, torch.int64, (n + 1,), device)
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 9 or not isinstance(out[0], torch.Tensor) or out[0].dim() != 1:
+            raise ValueError("out must be the PushRows of an earlier call")
+        cap = int(out[0].shape[0])
+        rows_cap = cap if rows_cap is None else int(rows_cap)
+        if rows_cap > cap:
+            raise ValueError("rows_cap must not exceed the rows of out")
+    elif rows_cap is None:
+        table._live()
+        rows_cap = int(offset[n].cpu())  # the one wait: the number of rows
+    rows_cap = int(rows_cap)
+    if rows_cap < 0:
+        raise ValueError("rows_cap must be >= 0")
+    if out is None:
+        cap = rows_cap
+        out = PushRows(torch.full((cap,), -1, dtype=torch.int32, device=device),
+                       torch.full((cap,), -1, dtype=torch.int32, device=device),
+                       torch.full((cap,), -1, dtype=torch.int32, device=device),
+                       torch.zeros((cap, 2), dtype=torch.int8, device=device),
+                       torch.full((cap,), PUSH_NONE, dtype=torch.uint8, device=device),
+                       torch.full((cap,), -1, dtype=torch.int32, device=device),
+                       torch.zeros((cap, table.npad, 2), dtype=torch.int8, device=device),
+                       torch.zeros((1,), dtype=torch.int32, device=device).view(torch.uint32), cap)
+    for name, t, dtype, shape in zip(PushRows._fields[:8], out,
+                                     (torch.int32, torch.int32, torch.int32, torch.int8, torch.uint8, torch.int32, torch.int8,
+                                      (torch.uint32, torch.int32)),
+                                     ((cap,), (cap,), (cap,), (cap, 2), (cap,), (cap,), (cap, table.npad, 2), (1,))):
+        _dev_tensor(f"out: {name}", t, dtype, shape, device)
+    out = PushRows(*out)
+    table._emit_launch(puzzle_id, mask, n, table.npad, plans.push_from, plans.push_action, plans.state, plan_cap, plans.length, pos,
+                       offset, rows_cap, out.item, out.t, out.state, out.push_from, out.push_action, out.cost, out.pos, out.dropped)
+    return out
+
+
 class PushSolutionTable:
     """The exact cost-to-go IN PUSHES of every canonical state reachable in one puzzle: a ``PushBreadthFirstSearch`` with
     ``stop_at_goal=False`` run to exhaustion, then ``pw_push_search_solve``.  State i of the search has the push rows
@@ -2160,24 +2238,17 @@ class PushSolutionTable:
         among its optimal rows (f(``seed``, item, step)).  ``length`` is the state's cost; ``PLANS_NONE`` -1 for an index
         outside the table, a dead end or an item of another puzzle, ``PLANS_CUT`` -2 for a plan longer than ``plan_cap``
         (nothing else written in both cases).  Masked items keep what ``out`` -- the ``PushPlans`` of an earlier call -- held."""
-        device = self.device
-        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1:
-            raise ValueError("index must be an int32 tensor [n] (store indices, as query returns them)")
-        n = int(index.shape[0])
-        if n < 1 or n >= 1 << 31:
-            raise ValueError("index must hold 1 .. 2^31 - 1 items")
-        _dev_tensor("index", index, torch.int32, (n,), device)
-        _dev_tensor("puzzle_id", puzzle_id, torch.int32, (n,), device, optional=True)
-        _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
-        if tie not in TABLE_TIES:
-            raise ValueError("tie must be 'lowest' or 'uniform'")
-        plan_cap = int(plan_cap)
-        if not 1 <= plan_cap <= _capi.PLAN_MAX_ACTIONS:
-            raise ValueError(f"plan_cap must be in 1 .. {_capi.PLAN_MAX_ACTIONS}")
-        out = _push_plans_outputs(out, n, plan_cap, device)
-        self._handle().table_plans(index, puzzle_id, mask, n, TABLE_TIES[tie], seed, out.push_from, out.push_action, out.state,
-                                   plan_cap, out.length)
-        return out
+        return _push_plans_call(self, True, index, puzzle_id, mask, tie, seed, plan_cap, out)
+
+    # (what ``_push_plans_call`` / ``_push_rows_call`` launch)
+    def _live(self) -> None:
+        self._handle()
+
+    def _plans_launch(self, *args) -> None:
+        self._handle().table_plans(*args)
+
+    def _emit_launch(self, *args) -> None:
+        self._handle().table_emit(*args)
 
     def demonstration_rows(self, plans: PushPlans, pos: Optional[torch.Tensor] = None, puzzle_id: Optional[torch.Tensor] = None,
                            mask: Optional[torch.Tensor] = None, rows_cap: Optional[int] = None,
@@ -2190,59 +2261,7 @@ class PushSolutionTable:
         table's puzzle, length > 0).  ``rows_cap`` None sizes the rows from ``offset[n]`` -- the one host wait; rows at or
         beyond a given ``rows_cap`` are dropped and counted in ``dropped``.  ``out``: the ``PushRows`` of an earlier call or
         of another table of the same batch, filled in place (``rows_cap`` defaults to its rows and must not exceed them)."""
-        device = self.device
-        if not isinstance(plans, (tuple, list)) or len(plans) != 4 or not isinstance(plans[3], torch.Tensor) \
-                or plans[3].dim() != 1 or not isinstance(plans[1], torch.Tensor) or plans[1].dim() != 2:
-            raise ValueError("plans must be the PushPlans of a plans call")
-        n, plan_cap = int(plans[3].shape[0]), int(plans[1].shape[1])
-        if n < 1 or plan_cap < 1:
-            raise ValueError("plans must hold at least one item and one step")
-        plans = _push_plans_outputs(plans, n, plan_cap, device)
-        _dev_tensor("pos", pos, torch.int8, (n, self.npad, 2), device, optional=True)
-        _dev_tensor("puzzle_id", puzzle_id, torch.int32, (n,), device, optional=True)
-        _dev_tensor("mask", mask, (torch.uint8, torch.bool), (n,), device, optional=True)
-        if offset is None:
-            lens = plans.length.clamp(min=0).to(torch.int64)
-            if mask is not None:
-                lens = lens * (mask != 0)
-            if puzzle_id is not None:
-                lens = lens * (puzzle_id == self.puzzle_index)
-            offset = torch.zeros((n + 1,), dtype=torch.int64, device=device)
-            torch.cumsum(lens, 0, out=offset[1:])
-        _dev_tensor("offset", offset, torch.int64, (n + 1,), device)
-        if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 9 or not isinstance(out[0], torch.Tensor) or out[0].dim() != 1:
-                raise ValueError("out must be the PushRows of an earlier call")
-            cap = int(out[0].shape[0])
-            rows_cap = cap if rows_cap is None else int(rows_cap)
-            if rows_cap > cap:
-                raise ValueError("rows_cap must not exceed the rows of out")
-        elif rows_cap is None:
-            self._handle()
-            rows_cap = int(offset[n].cpu())  # the one wait: the number of rows
-        rows_cap = int(rows_cap)
-        if rows_cap < 0:
-            raise ValueError("rows_cap must be >= 0")
-        if out is None:
-            cap = rows_cap
-            out = PushRows(torch.full((cap,), -1, dtype=torch.int32, device=device),
-                           torch.full((cap,), -1, dtype=torch.int32, device=device),
-                           torch.full((cap,), -1, dtype=torch.int32, device=device),
-                           torch.zeros((cap, 2), dtype=torch.int8, device=device),
-                           torch.full((cap,), PUSH_NONE, dtype=torch.uint8, device=device),
-                           torch.full((cap,), -1, dtype=torch.int32, device=device),
-                           torch.zeros((cap, self.npad, 2), dtype=torch.int8, device=device),
-                           torch.zeros((1,), dtype=torch.int32, device=device).view(torch.uint32), cap)
-        for name, t, dtype, shape in zip(PushRows._fields[:8], out,
-                                         (torch.int32, torch.int32, torch.int32, torch.int8, torch.uint8, torch.int32, torch.int8,
-                                          (torch.uint32, torch.int32)),
-                                         ((cap,), (cap,), (cap,), (cap, 2), (cap,), (cap,), (cap, self.npad, 2), (1,))):
-            _dev_tensor(f"out: {name}", t, dtype, shape, device)
-        out = PushRows(*out)
-        self._handle().table_emit(puzzle_id, mask, n, self.npad, plans.push_from, plans.push_action, plans.state, plan_cap,
-                                  plans.length, pos, offset, rows_cap, out.item, out.t, out.state, out.push_from, out.push_action,
-                                  out.cost, out.pos, out.dropped)
-        return out
+        return _push_rows_call(self, True, plans, pos, puzzle_id, mask, rows_cap, offset, out)
 
     def primitive_plans(self, pos: torch.Tensor, puzzle_id: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                         tie: str = "lowest", seed: int = 0, plan_cap: int = 1024, push_cap: int = 256):
@@ -2323,8 +2342,10 @@ class PushSolutionTableBatch:
     is found by state (``keys(i)`` / ``states(i)`` / ``query``), never by a number across runs.
     Device memory: 24 bytes per entry of the state pool, 8 per row, see ``pw_push_solve_batch_create``."""
 
+    indexed = False  # (a batch without a cost index: ``build_index`` / ``index=True``)
+
     def __init__(self, source, puzzles: Optional[Sequence[int]] = None, starts=None, max_states_each: int = 1 << 16,
-                 states: Optional[int] = None, rows: Optional[int] = None):
+                 states: Optional[int] = None, rows: Optional[int] = None, index: bool = False):
         engine = source if isinstance(source, _capi.Engine) else getattr(source, "engine", None)
         if not isinstance(engine, _capi.Engine):
             raise ValueError("source must be a VecPushWorld or an _capi.Engine")
@@ -2369,11 +2390,14 @@ class PushSolutionTableBatch:
             states, rows = self.states_needed, self.rows_needed
             self.close()
         self._run(int(states), int(rows))
+        if index:
+            self.build_index()
 
     def _stream(self):
         return self.engine._stream()
 
     def _run(self, states: int, rows: int) -> None:
+        self.indexed, self.max_cost_stored = False, -1
         h = ctypes.c_void_p()
         _capi.check(_capi.lib.pw_push_solve_batch_create(self.engine.handle, int(states), int(rows), ctypes.byref(h)))
         self.handle = h
@@ -2476,6 +2500,86 @@ class PushSolutionTableBatch:
                                                         _capi._ptr(out.walk) if actions else None,
                                                         _capi._ptr(out.action) if actions else None, self._stream()))
         return out
+
+    # ---- drawing from the batch (pw_push_solve_batch_index / _sample / _plans / _emit) ---------------------------
+    def _live(self):
+        if getattr(self, "handle", None) is None:
+            raise ValueError("the batch is closed")
+        return self.handle
+
+    def build_index(self):
+        """Builds the cost index of every stored item (``pw_push_solve_batch_index``: it allocates and waits once; a second call
+        does nothing) and returns ``self``.  ``indexed`` says it is there; ``max_cost_stored`` is the largest ``max_cost`` over
+        the stored items as a host int (-1: none has a finite cost).  ``sample`` needs the index, and ``VecPushWorld``'s
+        ``reset_from_push_tables`` / ``optimal_push_demonstrations`` / ``fewest_push_plans`` take indexed batches only."""
+        h = self._live()
+        _capi.check(_capi.lib.pw_push_solve_batch_index(h, self._stream()))
+        if self._counts is None:
+            self._counts = (self.status.cpu().numpy(), self.summary[:, :2].cpu().numpy())
+        stored = self._counts[0] == TABLE_BUILT
+        costs = self.summary[:, 4].cpu().numpy()[stored]
+        self.max_cost_stored = int(costs.max()) if costs.size else -1
+        self.indexed = True
+        return self
+
+    def cost_index(self, item: int):
+        """``(states_by_cost int32 [count], cost_start uint32 [max_cost + 3])`` of a stored item, on the device: its STATES
+        grouped by cost-to-go, the dead ends last (bucket ``max_cost + 1``), in ascending KEY inside a bucket -- state numbers
+        inside a layer are the schedule's, the key is not, so ``keys(item)[states_by_cost]`` is the same in every run.  Builds
+        the index when it is missing (``build_index``)."""
+        item, count, _ = self._item(item)
+        self.build_index()
+        states = torch.empty((count,), dtype=torch.int32, device=self.device)
+        start = torch.empty((int(self.summary[item, 4].cpu()) + 3,), dtype=torch.uint32, device=self.device)
+        _capi.check(_capi.lib.pw_push_solve_batch_index_read(self.handle, item, _capi._ptr(states), _capi._ptr(start),
+                                                             self._stream()))
+        return states, start
+
+    def _entry(self, what: str):
+        """(function, handle, stream) of ``_sample_call``'s launch."""
+        return _capi.lib.pw_push_solve_batch_sample, self._live(), self._stream()
+
+    def sample(self, puzzle_id: torch.Tensor, pos: torch.Tensor, steps: torch.Tensor,
+               terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None, cost=(1, None),
+               mask: Optional[torch.Tensor] = None, seed: int = 0, counter: Optional[torch.Tensor] = None, out=None):
+        """``PushSolutionTable.sample`` for a mixed batch in ONE launch (``pw_push_solve_batch_sample``; capturable with
+        ``counter`` and ``out`` given): every environment draws from the stored item of its own puzzle, the band clamped to
+        that item's ``0 .. max_cost``.  ``pos`` gets the canonical state (the agent at the canon of its walk region).  Returns
+        ``(state, cost)`` int32 [n]: the state within the item, as ``query`` numbers it, and its cost; -1 / -1 where the item
+        has no solvable state or the band holds none.  The STATE drawn is a function of (puzzle, start, ``seed``, environment,
+        ``counter``) whatever the launch that built the tables; only its number depends on that.  Masked environments and
+        environments whose puzzle has no stored table here keep everything they held, the counter included.  Needs the cost
+        index (``build_index``): ``ValueError`` without it."""
+        return _sample_call(self, False, puzzle_id, pos, steps, terminated, truncated, cost, mask, seed, counter, out)
+
+    def plans(self, index: torch.Tensor, puzzle_id: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+              tie: str = "lowest", seed: int = 0, plan_cap: int = 256, out=None) -> PushPlans:
+        """``PushSolutionTable.plans`` for a mixed batch in ONE launch (``pw_push_solve_batch_plans``, no index needed):
+        ``index`` int32 [n] are states within each item's puzzle (``query``'s ``index``), ``puzzle_id`` int32 [n] is required.
+        ``length`` is ``PLANS_NONE`` also for a puzzle without a stored table here."""
+        return _push_plans_call(self, False, index, puzzle_id, mask, tie, seed, plan_cap, out)
+
+    def _plans_launch(self, index, puzzle_id, mask, n, tie, seed, plan_from, plan_action, plan_state, plan_cap, plan_len) -> None:
+        p = _capi._ptr
+        _capi.check(_capi.lib.pw_push_solve_batch_plans(self._live(), p(index), p(puzzle_id), p(mask), int(n), int(tie),
+                                                        int(seed) & 0xFFFFFFFFFFFFFFFF, p(plan_from), p(plan_action),
+                                                        p(plan_state), int(plan_cap), p(plan_len), self._stream()))
+
+    def demonstration_rows(self, plans: PushPlans, pos: Optional[torch.Tensor] = None, puzzle_id: Optional[torch.Tensor] = None,
+                           mask: Optional[torch.Tensor] = None, rows_cap: Optional[int] = None,
+                           offset: Optional[torch.Tensor] = None, out: Optional[PushRows] = None) -> PushRows:
+        """``PushSolutionTable.demonstration_rows`` for a mixed batch in ONE launch (``pw_push_solve_batch_emit``):
+        ``puzzle_id`` int32 [n] is required; ``state`` is numbered within the item; with ``pos`` None row 0 holds the node's
+        canonical state.  Items whose puzzle has no stored table here write nothing."""
+        return _push_rows_call(self, False, plans, pos, puzzle_id, mask, rows_cap, offset, out)
+
+    def _emit_launch(self, puzzle_id, mask, n, npad, plan_from, plan_action, plan_state, plan_cap, plan_len, pos, offset, rows_cap,
+                     row_item, row_t, row_state, row_from, row_action, row_cost, row_pos, dropped) -> None:
+        p = _capi._ptr
+        _capi.check(_capi.lib.pw_push_solve_batch_emit(self._live(), p(puzzle_id), p(mask), int(n), int(npad), p(plan_from),
+                                                       p(plan_action), p(plan_state), int(plan_cap), p(plan_len), p(pos), p(offset),
+                                                       int(rows_cap), p(row_item), p(row_t), p(row_state), p(row_from),
+                                                       p(row_action), p(row_cost), p(row_pos), p(dropped), self._stream()))
 
     def covers(self, puzzle_id: torch.Tensor) -> torch.Tensor:
         """bool [n] on the device: the items of ``puzzle_id`` whose puzzle has a stored table here."""

@@ -718,7 +718,8 @@ class VecPushWorld:
     def push_tables(self, puzzles=None, **kw):
         """A ``search.PushSolutionTableBatch``: the cost-to-go tables in pushes of the small puzzles of this batch's set
         (``puzzles``: set indices, None = all), built in one launch and queried in one (``push_cost_to_go``).  ``kw``: ``starts``,
-        ``max_states_each``, ``states``, ``rows``."""
+        ``max_states_each``, ``states``, ``rows`` and ``index`` -- True builds the cost index (``build_index``) that
+        ``reset_from_push_tables``, ``optimal_push_demonstrations`` and ``fewest_push_plans`` ask of a batch."""
         from .search import PushSolutionTableBatch
 
         return PushSolutionTableBatch(self, puzzles, **kw)
@@ -861,14 +862,20 @@ class VecPushWorld:
         tables = list(tables)
         for table in tables:
             if isinstance(table, PushSolutionTableBatch):
-                raise ValueError("PushSolutionTableBatch is not supported here yet (sampling, plans and demonstrations need a "
-                                 "cost index on the batch): pass push_table()s; push_cost_to_go / push_expert_actions take batches")
+                if not table.indexed:  # (the index allocates and waits: it is asked for, never built behind a call)
+                    raise ValueError("PushSolutionTableBatch is not supported here yet (sampling, plans and demonstrations need a "
+                                     "cost index on the batch): pass push_table()s; push_cost_to_go / push_expert_actions take batches")
+                if table.engine is not self.engine:
+                    raise ValueError("the tables must be made on this environment (VecPushWorld.push_tables)")
+                continue
             if table.search._engine is not self.engine:
                 raise ValueError("the tables must be made on this environment (VecPushWorld.push_table)")
         return tables
 
     def reset_from_push_tables(self, tables, cost=(1, None), mask: Optional[torch.Tensor] = None, seed: Optional[int] = None):
-        """``reset_from_tables`` with a list of ``push_table``s: every (masked) environment whose puzzle has a table in
+        """``reset_from_tables`` with a list of ``push_table``s and / or INDEXED ``push_tables`` batches (``index=True`` or
+        ``build_index()``; a batch costs ONE sample launch however many puzzles it holds and draws canonical states, the agent
+        at the canon of its walk region; a batch without an index is refused): every (masked) environment whose puzzle has a table in
         ``tables`` starts from a canonical state drawn uniformly among the states of its puzzle with a cost-to-go IN PUSHES
         in ``cost`` = ``(lo, hi)`` (``hi`` None: up to each table's own largest cost; two int32 tensors [B]: a band per
         environment), the agent where the search's push left it.  The band is clamped to each table's costs and dead ends
@@ -905,7 +912,8 @@ class VecPushWorld:
 
     def optimal_push_demonstrations(self, tables, tie: str = "lowest", seed: int = 0, observation: Optional[str] = "own",
                                     mask: Optional[torch.Tensor] = None, plan_cap: int = 256, masks: bool = False):
-        """Fewest-pushes demonstrations in the push-level action space, read off ``push_table``s: from every (unmasked)
+        """Fewest-pushes demonstrations in the push-level action space, read off ``push_table``s and / or indexed
+        ``push_tables`` batches (one plans and one emit launch per batch, whatever it holds): from every (unmasked)
         environment's current state one ``push_cost_to_go`` over ``tables``, one plans launch per table (``tie`` "lowest":
         each node's best row, "uniform": drawn among its optimal rows with ``seed``), a ``cumsum``, ONE host wait for the
         number of rows T, one emit launch per table -- every push of every plan becomes one row, without a flood or a step
@@ -961,12 +969,14 @@ class VecPushWorld:
         """The front half of ``optimal_push_demonstrations``: ``(T, rows, plans, offset)`` -- the query, one plans launch per
         table, the ``cumsum``, the one wait for the number of rows T and one emit launch per table.  ``tables`` are this
         environment's own, ``mask`` uint8 on the device or None."""
-        from .search import PushRows, _push_plans_outputs
+        from .search import PushRows, PushSolutionTableBatch, _push_plans_outputs
 
         B, dev = self.num_envs, self.device
         q = self.push_cost_to_go(tables, mask=mask)
-        # (no plan is longer than a table's largest cost: the buffers need no more columns; a cost beyond plan_cap is cut as ever)
-        width = max(1, min(int(plan_cap), max([int(t.max_cost) for t in tables] + [1])))
+        # (no plan is longer than a table's largest cost: the buffers need no more columns; a cost beyond plan_cap is cut as ever;
+        # a batch's largest cost is the host value its index build left)
+        costs = [int(t.max_cost_stored if isinstance(t, PushSolutionTableBatch) else t.max_cost) for t in tables]
+        width = max(1, min(int(plan_cap), max(costs + [1])))
         plans = _push_plans_outputs(None, B, width, dev)
         owns = []
         for table in tables:  # (a table answers for its own puzzles only: the others keep what another table wrote)
@@ -992,7 +1002,7 @@ class VecPushWorld:
     def fewest_push_plans(self, tables, tie: str = "lowest", seed: int = 0, mask: Optional[torch.Tensor] = None,
                           plan_cap: int = 1024, push_cap: int = 256):
         """Fewest-pushes plans IN PRIMITIVE ACTIONS from every (unmasked) environment's current state, read off
-        ``push_table``s: ``optimal_push_demonstrations``' pipeline up to its rows (without a render; plans of at most
+        ``push_table``s and / or indexed ``push_tables`` batches: ``optimal_push_demonstrations``' pipeline up to its rows (without a render; plans of at most
         ``push_cap`` pushes), then ``search.push_rows_to_plans`` -- one count launch, one write launch and one gather over the
         rows.  Two host waits: the number of rows and the number of actions.
 
