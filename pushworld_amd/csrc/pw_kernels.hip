@@ -465,6 +465,7 @@ struct PageRec {
 #include "pw_push_unroll.inc"
 #include "pw_push_search.inc"
 #include "pw_push_table.inc"
+#include "pw_push_draw.inc"
 #include "pw_push_table_sample.inc"
 #include "pw_push_solution_batch.inc"
 #include "pw_push_batch_sample.inc"

@@ -11,6 +11,8 @@
 // The kernels are written once, against a TABLE VIEW: where succ / cost / acts and the index of the table of an item live, its
 // first row, and how a row decodes into a state.  kBatch = true resolves the view per item from the puzzle id (K13: rows of
 // a pool, the state is the 64-bit key), kBatch = false is the one table of a search (K12: the state is the store's row).
+// The draws over pushes (pw_push_draw.inc and its users, K20 / K26) share the stream constants, the three state helpers, the scan
+// kernel and table_sample_checks of this file.
 
 #define PW_TABLE_K_SAMPLE 0xA0761D6478BD642Full  // seed ^ this: the stream of the sample draws (include/pushworld_amd.h)
 #define PW_TABLE_K_PLAN 0xE7037ED1A0B428DBull    // seed ^ this: the stream of the tie breaks of the plans
@@ -83,25 +85,47 @@ __device__ __forceinline__ bool table_view_of_env(const TableSrc& s, const int32
   return table_view_of_item<false>(s, 0, v);
 }
 
-// row -> state in the engine's layout: 16 words of two movables each (x, y int8 pairs), zeros from movable n_mov on
+// The three state helpers of every draw (K14 here, K20 / K26 in pw_push_draw.inc).  A state in the engine's layout is 16 words of
+// two movables each (x, y int8 pairs), zeros from movable n_mov on.
+// store words -> state: `nw` words at src, two movables per word
+__device__ __forceinline__ void table_store_state(const uint32_t* src, int nw, int n_mov, uint32_t (&w)[16]) {
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    uint32_t word = 0u;
+    if (k < nw && 2 * k < n_mov) {
+      word = src[k];
+      if (2 * k + 1 >= n_mov) word &= 0xffffu;
+    }
+    w[k] = word;
+  }
+}
+
+// 64-bit key -> state (the key holds zeros beyond the puzzle's movables)
+__device__ __forceinline__ void table_key_state(uint64_t key, uint32_t (&w)[16]) {
+  uint32_t P[4];
+  pw_bs_unpack(key, P);
+#pragma unroll
+  for (int k = 0; k < 16; k++) w[k] = k < 4 ? P[k] : 0u;
+}
+
+// state -> npad pairs at dst, with 8-byte (npad 4) or 16-byte stores
+__device__ __forceinline__ void table_write_state(int8_t* dst, int32_t npad, const uint32_t (&w)[16]) {
+  if (npad == 4) {
+    *reinterpret_cast<uint2*>(dst) = make_uint2(w[0], w[1]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      if (8 * q < npad) reinterpret_cast<uint4*>(dst)[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  }
+}
+
+// row -> state
 template <bool kBatch>
 __device__ __forceinline__ void table_row_state(const TableSrc& s, const TableView& v, int64_t row, uint32_t (&w)[16]) {
-#pragma unroll
-  for (int k = 0; k < 16; k++) w[k] = 0u;
-  if (kBatch) {
-    uint32_t P[4];
-    pw_bs_unpack(s.key[v.base + row], P);  // (the key holds zeros beyond the puzzle's movables)
-#pragma unroll
-    for (int k = 0; k < 4; k++) w[k] = P[k];
-  } else {
-    const uint32_t* src = s.states + row * s.nw;
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-      if (k < s.nw) {
-        const uint32_t word = src[k];
-        w[k] = 2 * k + 1 < v.n_mov ? word : (2 * k < v.n_mov ? (word & 0xffffu) : 0u);
-      }
-  }
+  if (kBatch)
+    table_key_state(s.key[v.base + row], w);
+  else
+    table_store_state(s.states + row * s.nw, s.nw, v.n_mov, w);
 }
 
 // ---- cost index ---------------------------------------------------------------------------------------------------------------
@@ -122,17 +146,21 @@ __global__ __launch_bounds__(256) void pw_table_index_count_kernel(TableSrc s, u
   }
 }
 
-// one workgroup per table
-template <bool kBatch>
-__global__ __launch_bounds__(256) void pw_table_index_scan_kernel(TableSrc s) {
+// The scan of every cost index (K14 both forms, K20, K26): one workgroup per table, in place and inclusive.  The pooled tables of a
+// batch: table g's words start at cs_off[g] (< 0: nothing stored or indexed there) and are max_cost[g * stride] + 3 of them.  The one
+// table of a search: cs_off and max_cost are NULL, the words start at 0 and are max_cost_one + 3.
+__global__ __launch_bounds__(256) void pw_table_index_scan_kernel(uint32_t* cost_start, const int64_t* cs_off, const int32_t* max_cost,
+                                                                   int32_t stride, int32_t max_cost_one) {
   __shared__ uint32_t part[256];
-  TableView v;
-  if (!table_view_of_item<kBatch>(s, static_cast<int32_t>(blockIdx.x), v)) return;  // (workgroup-uniform)
-  const uint32_t m = static_cast<uint32_t>(v.max_cost) + 3u, tid = threadIdx.x;
+  const int64_t off = cs_off ? cs_off[blockIdx.x] : 0;
+  if (off < 0) return;  // (workgroup-uniform)
+  uint32_t* cs = cost_start + off;
+  const int32_t mc = max_cost ? max_cost[static_cast<int64_t>(blockIdx.x) * stride] : max_cost_one;
+  const uint32_t m = static_cast<uint32_t>(mc) + 3u, tid = threadIdx.x;
   uint32_t carry = 0;
   for (uint32_t c0 = 0; c0 < m; c0 += 256u) {
     const uint32_t k = c0 + tid;
-    part[tid] = k < m ? v.cs[k] : 0u;
+    part[tid] = k < m ? cs[k] : 0u;
     __syncthreads();
     for (uint32_t d = 1; d < 256u; d <<= 1) {
       const uint32_t t = tid >= d ? part[tid - d] : 0u;
@@ -140,7 +168,7 @@ __global__ __launch_bounds__(256) void pw_table_index_scan_kernel(TableSrc s) {
       part[tid] += t;
       __syncthreads();
     }
-    if (k < m) v.cs[k] = part[tid] + carry;
+    if (k < m) cs[k] = part[tid] + carry;
     carry += part[255];
     __syncthreads();  // (part is rewritten by the next round)
   }
@@ -211,14 +239,7 @@ __global__ __launch_bounds__(256) void pw_table_sample_kernel(TableSampleArgs a)
   const int64_t row = a.src.rows_by_cost[v.base + first + u];
   uint32_t w[16];
   table_row_state<kBatch>(a.src, v, row, w);
-  int8_t* dst = a.pos + i * a.npad * 2;
-  if (a.npad == 4) {
-    *reinterpret_cast<uint2*>(dst) = make_uint2(w[0], w[1]);
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (8 * q < a.npad) reinterpret_cast<uint4*>(dst)[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-  }
+  table_write_state(a.pos + i * a.npad * 2, a.npad, w);
   a.steps[i] = 0;
   if (a.term) a.term[i] = 0;
   if (a.trunc) a.trunc[i] = 0;
@@ -318,7 +339,8 @@ static void table_index_launch(const TableSrc& s, int64_t tables, int64_t max_ro
   while (chunks > 1 && tables * chunks > (1ll << 30)) chunks /= 2;
   const dim3 grid(static_cast<unsigned>(tables * chunks)), block(256);
   hipLaunchKernelGGL(pw_table_index_count_kernel<kBatch>, grid, block, 0, st, s, static_cast<uint32_t>(chunks));
-  hipLaunchKernelGGL(pw_table_index_scan_kernel<kBatch>, dim3(static_cast<unsigned>(tables)), block, 0, st, s);
+  hipLaunchKernelGGL(pw_table_index_scan_kernel, dim3(static_cast<unsigned>(tables)), block, 0, st, s.cost_start, s.cs_off,
+                     kBatch ? s.summary + 3 : nullptr, 5, s.max_cost);
   hipLaunchKernelGGL(pw_table_index_scatter_kernel<kBatch>, grid, block, 0, st, s, static_cast<uint32_t>(chunks));
 }
 

@@ -33,26 +33,33 @@ SENT = 77  # what every output holds before a launch
 _SHARED = {}
 
 
-def _vec():
-    if "vec" not in _SHARED:
+# a puzzle with more movables, appended as puzzle 6 (never an item), pads the set to 8, 16 or 32
+PAD_EXTRA = {4: None, 8: 4, 16: 10, 32: deep_puzzles.POCKETS_EXTRA}
+
+
+def _vec(npad=4):
+    if ("vec", npad) not in _SHARED:
         texts = [PT.case(name)[0] for name in NAMES["A"][:5]] + [deep_puzzles.corridor(7)]
+        if PAD_EXTRA[npad]:
+            texts.append(deep_puzzles.pockets(PAD_EXTRA[npad]))
         vec = VecPushWorld([PushWorldPuzzle(text=x) for x in texts], 8, observation=None, max_steps=None)
-        assert vec.num_objects_padded == 4
-        _SHARED["vec"] = vec
-    return _SHARED["vec"]
+        assert vec.num_objects_padded == npad
+        _SHARED[("vec", npad)] = vec
+    return _SHARED[("vec", npad)]
 
 
-def _batch(order="A", groups_per_cu=0):
-    """The indexed batch of the six cases, built once per (order, workgroups per CU) and never changed by a test."""
-    key = ("batch", order, groups_per_cu)
+def _batch(order="A", groups_per_cu=0, npad=4):
+    """The indexed batch of the six cases, built once per (order, workgroups per CU, npad) and never changed by a test."""
+    key = ("batch", order, groups_per_cu, npad)
     if key not in _SHARED:
-        vec = _vec()
+        vec = _vec(npad)
         vec.engine.set_option("search_batch_groups_per_cu", groups_per_cu)
         try:
             batch = vec.push_tables(PUZZLES, starts=[PT.case(n)[2] for n in NAMES[order]], max_states_each=2048, index=True)
         finally:
             vec.engine.set_option("search_batch_groups_per_cu", 0)
         assert batch.indexed and batch.status.cpu().tolist() == [TABLE_BUILT] * 6 and batch.max_cost_stored == 8
+        assert batch.npad == npad
         _SHARED[key] = batch
     return _SHARED[key]
 
@@ -385,9 +392,7 @@ def _check_rows(rows, want, maps, npad, cap=None):
     assert (pos[:T] == _state_pos([r.pos for _, r in want], npad)).all()  # (zeros from the puzzle's movables on)
 
 
-@pytest.mark.parametrize("order", ["A", "B"])
-def test_emit(order, tie="uniform", seed=5):
-    batch = _batch(order, 0)
+def _check_emit(batch, order, tie="uniform", seed=5):
     dev, npad = batch.device, batch.npad
     # restated states with a plan, of every answering item; live: other cells of their regions
     chosen = []
@@ -458,6 +463,21 @@ def test_emit(order, tie="uniform", seed=5):
     skipped[int(offset[first])] = True
     skipped[int(offset[other]):int(offset[other + 1])] = True
     assert bool((got.t[skipped] == SENT).all()) and bool((got.t[~skipped] != SENT).all())
+
+
+@pytest.mark.parametrize("order", ["A", "B"])
+def test_emit(order):
+    _check_emit(_batch(order, 0), order)
+
+
+@pytest.mark.parametrize("npad", [8, 16, 32])
+def test_sample_and_emit_padded(npad):
+    """The same six cases in a set padded to 8, 16 and 32 (the 16-byte stores of the state writer, the live state's words beyond
+    the key's four, zeros from a puzzle's movables on): the sample and the rows against the restatement, as at npad 4."""
+    batch = _batch("B", 0, npad)
+    _, drawn = _check_sample(batch, "B", (1, None), 21)
+    assert drawn.sum() > 300
+    _check_emit(batch, "B")
 
 
 # ---- 5. end to end on generated puzzles -------------------------------------------------------------------------------------------

@@ -133,6 +133,7 @@ NPAD_ENTRY_POINTS = [
     ("pw_push_search_table_emit", "pw_push_search_table_emit: "),
     ("pw_push_solve_batch_run", "pw_push_solve_batch_run: "),
     ("pw_push_solve_batch_query", "pw_push_solve_batch_query: "),
+    ("pw_push_solve_batch_emit", "pw_push_solve_batch_emit: "),
     ("pw_push_plan_batch_run", "pw_push_plan_batch_run: "),
     ("pw_push_plan_batch_run_states", "pw_push_plan_batch_run_states: "),
     ("pw_push_plan_batch_read_states", "pw_push_plan_batch_read_states: "),

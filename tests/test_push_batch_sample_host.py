@@ -134,13 +134,26 @@ def test_header_signatures_and_the_unit():
     with open(os.path.join(ROOT, "pushworld_amd", "csrc", "pw_kernels.hip")) as f:
         unit = f.read()
     mine = unit.index('#include "pw_push_batch_sample.inc"')
+    draw = unit.index('#include "pw_push_draw.inc"')
     assert unit.index('#include "pw_push_solution_batch.inc"') < mine and unit.index('#include "pw_push_table_sample.inc"') < mine
-    assert "pw_push_batch_sample.inc" in build.HEADERS
-    with open(os.path.join(ROOT, "pushworld_amd", "csrc", "pw_push_batch_sample.inc")) as f:
-        inc = f.read()
-    code = "\n".join(line.split("//")[0] for line in inc.splitlines())
-    assert "printf" not in code and "assert(" not in code and "asm" not in code
-    assert code.count("__global__") == 6  # key, keep, scan, sample, plans, emit
+    # the draws both push tables share: after the helpers and the scan of the move-level draws, before its two users
+    assert unit.index('#include "pw_table_sample.inc"') < unit.index('#include "pw_push_table.inc"') < draw
+    assert draw < unit.index('#include "pw_push_table_sample.inc"')
+    # the one scan, sample, plans and emit are in the shared files; key and keep stay here, K20's key kernel there
+    kernels = {"pw_table_sample.inc": 5, "pw_push_draw.inc": 3, "pw_push_table_sample.inc": 1, "pw_push_batch_sample.inc": 2}
+    names = []
+    for name, count in kernels.items():
+        assert name in build.HEADERS
+        with open(os.path.join(ROOT, "pushworld_amd", "csrc", name)) as f:
+            inc = f.read()
+        code = "\n".join(line.split("//")[0] for line in inc.splitlines())
+        assert "printf" not in code and "assert(" not in code and "asm" not in code, name
+        assert code.count("__global__") == count, name
+        names += re.findall(r"__global__ __launch_bounds__\(256\) void (\w+)\(", code)
+    assert sorted(names) == sorted([
+        "pw_table_index_count_kernel", "pw_table_index_scan_kernel", "pw_table_index_scatter_kernel", "pw_table_sample_kernel",
+        "pw_table_plans_kernel", "pw_push_sample_kernel", "pw_push_plans_kernel", "pw_push_emit_kernel",
+        "pw_push_table_index_key_kernel", "pw_push_batch_index_key_kernel", "pw_push_batch_index_keep_kernel"])
 
 
 # ---- the C ABI: checks that return before any launch -----------------------------------------------------------------------------

@@ -277,9 +277,12 @@ def test_header_and_signatures():
     with open(os.path.join(ROOT, "pushworld_amd", "csrc", "pw_kernels.hip")) as f:
         unit = f.read()
     assert unit.index('#include "pw_push_table.inc"') < unit.index('#include "pw_push_table_sample.inc"')
+    # the kernels of the draws are pw_push_draw.inc's, which needs the helpers and the scan of pw_table_sample.inc
+    assert unit.index('#include "pw_table_sample.inc"') < unit.index('#include "pw_push_draw.inc"')
+    assert unit.index('#include "pw_push_draw.inc"') < unit.index('#include "pw_push_table_sample.inc"')
     from pushworld_amd import build
 
-    assert "pw_push_table_sample.inc" in build.HEADERS
+    assert "pw_push_table_sample.inc" in build.HEADERS and "pw_push_draw.inc" in build.HEADERS
     assert _capi.ABI_VERSION == 4 and lib.pw_abi_version() == 4
     assert (search.TABLE_K_SAMPLE, search.TABLE_K_PLAN) == (K_SAMPLE, K_PLAN)
 
