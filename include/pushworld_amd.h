@@ -568,6 +568,66 @@ int pw_curriculum_update(PwEngine* e, int32_t mode, const int64_t* stats, const 
 int pw_resample_weighted(PwEngine* e, int32_t* puzzle_id, const uint8_t* terminated, const uint8_t* truncated,
                          const uint64_t* cdf, uint64_t seed, uint32_t* episode, int32_t batch, void* stream);
 
+/* The level below the single puzzle: start-state pools.  A pool holds S start states of the P puzzles of the
+ * engine's set -- pool_pos int8 [S][npad][2] in the engine's state layout, a puzzle and pool_level int32 [S] (>= 0; the cost-to-go
+ * for states that come from a table) -- grouped once, by the caller, by (puzzle, level):
+ *     order     int32  [S]   the entries sorted by (puzzle, level), ascending entry index inside a group
+ *     max_level int32  [P]   the largest level of a puzzle's entries, -1 for a puzzle without entries
+ *     lvl_off   int64  [P]   where a puzzle's words start in `start`
+ *     start     uint32 [start_words]   puzzle p owns max_level[p] + 2 words at lvl_off[p]; the entries of level l of puzzle p are
+ *                            order[start[lvl_off[p] + l] .. start[lvl_off[p] + l + 1] - 1]  (a level without entries: empty)
+ * Integer arithmetic only: every result is exact and independent of launch geometry.  The three launches run on `stream`,
+ * allocate nothing, never synchronise and can be captured.  Every argument error returns PW_EINVAL with the function's name and
+ * the offending argument in pw_last_error, before anything is read through a pointer.
+ *
+ * pw_start_pool_arm: pending[i] = (terminated[i] | truncated[i]) != 0 -- exactly the environments that the next step with
+ * PW_STEP_AUTORESET will reset (the 0xFF flags of a refused action included).  Called BEFORE that step; the draw behind the step
+ * takes `pending` as its mask.
+ *
+ * pw_start_pool_draw: one start state for every environment i < n.  mix64 is pw_mix64; the two streams are
+ * PW_START_POOL_K_DRAW and PW_START_POOL_K_KEEP, distinct from PW_TABLE_K_SAMPLE / PW_TABLE_K_PLAN.
+ *   1. mask != NULL and mask[i] == 0: nothing is written for i at all.
+ *   2. p = puzzle_id[i].  p outside 0 .. P - 1, max_level[p] < 0 (or words of p that do not lie inside `start`):
+ *      out_entry[i] = out_level[i] = -1, nothing else is written, the counter is not advanced.
+ *   3. (lo, hi) = (lo_n[i], hi_n[i]) when lo_n / hi_n are given (both or neither), else band[p][0..1] when band (int32 [P][2]) is
+ *      given, else the scalars lo, hi.  Then hi < 0 becomes max_level[p], then hi = max(hi, lo), then both are clamped to
+ *      0 .. max_level[p].
+ *   4. first = start[lvl_off[p] + lo], end = start[lvl_off[p] + hi + 1].  end <= first or end > S: the band is empty -- outs -1,
+ *      the state untouched, the counter not advanced.
+ *   5. ctr = ++counter[i]   (uint32, wraps).
+ *   6. keep_q16 > 0 and (mix64(seed ^ PW_START_POOL_K_KEEP, i, ctr) >> 48) < keep_q16: the environment keeps the state it has
+ *      (behind an autoreset: its puzzle's initial state), outs -1.  keep_q16 is in 0 .. 65536; 65536 keeps always.
+ *   7. otherwise u = mulhi64(mix64(seed ^ PW_START_POOL_K_DRAW, i, ctr), end - first), entry = order[first + u]; an entry outside
+ *      0 .. S - 1 (a corrupt pool) gives outs -1 and nothing else.  The npad pairs of pool_pos[entry] are copied to pos[i],
+ *      steps[i] = 0, terminated[i] = truncated[i] = 0 (where the pointers are given), out_entry[i] = entry,
+ *      out_level[i] = pool_level[entry].
+ * npad is the engine's; n == 0 is a no-op.
+ *
+ * pw_start_pool_update_bands: one band int32 [P][2] = (lo, hi) per puzzle moves with the success rate of a statistics block
+ * (pw_episode_stats).  Per puzzle p with max_level[p] >= 0 (the others: nothing happens), with n = EPISODES and s = SOLVED of
+ * stats[p] - base[p] (a negative difference counts as 0, s is clamped to n):
+ *     n < min_episodes: nothing is written and base[p] stays -- the record keeps growing.  Otherwise
+ *     k = max(0, bit_length(n) - 20);  n' = n >> k;  s' = s >> k                      (as pw_curriculum_update shifts them)
+ *     hi = band[p][1];  hi < 0 means max_level[p]
+ *     s' * 65536 >= up_q16 * n':         hi = min(hi + step, max_level[p])
+ *     else s' * 65536 < down_q16 * n':   hi = max(hi - step, min(hi_min, max_level[p]))
+ *     width > 0:  lo = max(lo_min, hi - width + 1);   width == 0: lo stays
+ *     band[p] = (lo, hi);  base[p][0..3] = stats[p][0..3];  delta[p] (int8 [P], may be NULL) = +1 / -1 / 0: how hi moved.
+ * Refused: up_q16 < down_q16, a threshold above 65536, step < 1, min_episodes < 1, width < 0. */
+#define PW_START_POOL_K_DRAW 0x8EBC6AF09C88C6E3ull
+#define PW_START_POOL_K_KEEP 0x589965CC75374CC3ull
+int pw_start_pool_arm(PwEngine* e, const uint8_t* terminated, const uint8_t* truncated, uint8_t* pending, int32_t n,
+                      void* stream);
+int pw_start_pool_draw(PwEngine* e, const int8_t* pool_pos, const int32_t* pool_level, const int32_t* order,
+                       const uint32_t* start, int64_t start_words, const int64_t* lvl_off, const int32_t* max_level,
+                       int32_t num_entries, const int32_t* puzzle_id, const uint8_t* mask, int32_t n, uint64_t seed,
+                       uint32_t* counter, uint32_t keep_q16, int32_t lo, int32_t hi, const int32_t* band, const int32_t* lo_n,
+                       const int32_t* hi_n, int8_t* pos, int32_t* steps, uint8_t* terminated, uint8_t* truncated,
+                       int32_t* out_entry, int32_t* out_level, void* stream);
+int pw_start_pool_update_bands(PwEngine* e, const int32_t* max_level, const int64_t* stats, int64_t* base, int32_t* band,
+                               int8_t* delta, int32_t min_episodes, uint32_t up_q16, uint32_t down_q16, int32_t step,
+                               int32_t width, int32_t hi_min, int32_t lo_min, void* stream);
+
 /* gym_env.py:188-226 step() without the observation:
  *   pos <- get_next_state(pos, action)                 puzzle.py:348-394
  *   terminated <- is_goal_state                        puzzle.py:409-411
@@ -667,6 +727,13 @@ int pw_mailbox_close(PwMailbox* m);
  * obs: device buffer, env e at obs + e * env_stride_bytes (multiple of 16, base 16 B aligned). */
 int pw_render(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* obs,
               int64_t env_stride_bytes, int32_t batch, void* stream);
+/* pw_render_retained: the same observation, for a state that something other than this engine's pw_step_render left (DESIGN.md
+ * K27: a start-state draw behind a state-only step).  Into the engine's retained buffer of the retained (puzzle_id, batch)
+ * (PW_OPT_OBS_PADDING_ONCE) it writes the live pages only, and with PW_OPT_OBS_CHANGED_PAGES of those only the pages whose pixel
+ * rows differ from what the buffer shows -- pw_step_render's render half, with a record pre-pass in place of the step kernel's
+ * records.  Into any other buffer, or with the options off, it is pw_render.  Same bytes as pw_render either way. */
+int pw_render_retained(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* obs,
+                       int64_t env_stride_bytes, int32_t batch, void* stream);
 
 /* pw_step followed by pw_render of the new state on the same stream (PW_OPT_FUSED_STEP_RENDER selects a
  * single launch that runs the step inside the per-environment render workgroups; slower, kept for tests). */

@@ -132,6 +132,7 @@ SIGNATURES = {
     "pw_engine_set_step_signal": (c_int, [c_void_p, c_void_p]),
     "pw_engine_set_step_host_copy": (c_int, [c_void_p, c_void_p]),
     "pw_render": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "pw_render_retained": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "pw_step_render": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -319,6 +320,13 @@ SIGNATURES = {
                                      c_void_p]),
     "pw_resample_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_int32,
                                      c_void_p]),
+    "pw_start_pool_arm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pw_start_pool_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32,
+                                   c_void_p, c_void_p, c_int32, ctypes.c_uint64, c_void_p, ctypes.c_uint32, c_int32, c_int32,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "pw_start_pool_update_bands": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                           ctypes.c_uint32, ctypes.c_uint32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 # pw_episode_stats: the columns of a statistics block; pw_curriculum_update: its modes (include/pushworld_amd.h)
@@ -1056,6 +1064,124 @@ class Engine:
                 check(rc)
         return call
 
+    # start-state pools (pw_start_pool_arm / _draw / _update_bands).  `pool` is anything with the grouped tensors
+    # of ``start_pool.StartPool``: pos, level, order, start, lvl_off, max_level (and num_entries, band for the calls that use them).
+    def _start_pool_args(self, fn, pool):
+        P, npad = len(self.pset), int(self.np)
+        S = _tensor_arg(fn, "pool.pos", pool.pos, torch.int8, (None, npad, 2))[0]
+        _tensor_arg(fn, "pool.level", pool.level, torch.int32, (S,))
+        _tensor_arg(fn, "pool.order", pool.order, torch.int32, (S,))
+        W = _tensor_arg(fn, "pool.start", pool.start, torch.uint32, (None,))[0]
+        _tensor_arg(fn, "pool.lvl_off", pool.lvl_off, torch.int64, (P,))
+        _tensor_arg(fn, "pool.max_level", pool.max_level, torch.int32, (P,))
+        if S < 1 or S >= 1 << 31:
+            raise ValueError(f"{fn}: pool.pos must hold 1 .. 2^31 - 1 entries")
+        return S, W
+
+    def start_pool_arm(self, terminated, truncated, pending):
+        """``pw_start_pool_arm``: ``pending[i] = (terminated[i] | truncated[i]) != 0``, the environments the next autoreset
+        step will reset."""
+        B = _tensor_arg("pw_start_pool_arm", "terminated", terminated, torch.uint8, (None,))[0]
+        _tensor_arg("pw_start_pool_arm", "truncated", truncated, torch.uint8, (B,))
+        _tensor_arg("pw_start_pool_arm", "pending", pending, torch.uint8, (B,))
+        check(lib.pw_start_pool_arm(self.handle, _ptr(terminated), _ptr(truncated), _ptr(pending), B, self._stream()))
+
+    def bind_start_pool_arm(self, terminated, truncated, pending):
+        """Returns ``call()`` == ``start_pool_arm(...)`` on the current stream (the arguments are checked once, here)."""
+        B = _tensor_arg("pw_start_pool_arm", "terminated", terminated, torch.uint8, (None,))[0]
+        _tensor_arg("pw_start_pool_arm", "truncated", truncated, torch.uint8, (B,))
+        _tensor_arg("pw_start_pool_arm", "pending", pending, torch.uint8, (B,))
+        fn, h, dev = lib.pw_start_pool_arm, self.handle, self.device.index
+        keep = (terminated, truncated, pending)
+        a = [_ptr(t) for t in keep]
+
+        def call(_keep=keep):
+            rc = fn(h, a[0], a[1], a[2], B, _raw_stream(dev))
+            if rc:
+                check(rc)
+        return call
+
+    def _start_pool_draw_args(self, pool, puzzle_id, pos, steps, terminated, truncated, counter, out_entry, out_level, mask,
+                              band, lo_n, hi_n, keep_q16, lo, hi):
+        fn = "pw_start_pool_draw"
+        S, W = self._start_pool_args(fn, pool)
+        P, npad = len(self.pset), int(self.np)
+        B = _tensor_arg(fn, "puzzle_id", puzzle_id, torch.int32, (None,))[0]
+        _tensor_arg(fn, "pos", pos, torch.int8, (B, npad, 2))
+        _tensor_arg(fn, "steps", steps, torch.int32, (B,))
+        if terminated is not None:
+            _tensor_arg(fn, "terminated", terminated, torch.uint8, (B,))
+        if truncated is not None:
+            _tensor_arg(fn, "truncated", truncated, torch.uint8, (B,))
+        _tensor_arg(fn, "counter", counter, torch.uint32, (B,))
+        _tensor_arg(fn, "out_entry", out_entry, torch.int32, (B,))
+        _tensor_arg(fn, "out_level", out_level, torch.int32, (B,))
+        if mask is not None:
+            _tensor_arg(fn, "mask", mask, torch.uint8, (B,))
+        if band is not None:
+            _tensor_arg(fn, "band", band, torch.int32, (P, 2))
+        if (lo_n is None) != (hi_n is None):
+            raise ValueError(f"{fn}: lo_n and hi_n go together")
+        if lo_n is not None:
+            _tensor_arg(fn, "lo_n", lo_n, torch.int32, (B,))
+            _tensor_arg(fn, "hi_n", hi_n, torch.int32, (B,))
+        if isinstance(keep_q16, bool) or not isinstance(keep_q16, int) or not 0 <= keep_q16 <= 65536:
+            raise ValueError(f"{fn}: keep_q16 must be an integer in 0 .. 65536")
+        for name, v in (("lo", lo), ("hi", hi)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -(1 << 31) <= int(v) < 1 << 31:
+                raise ValueError(f"{fn}: {name} must be an int32")
+        keep = (pool.pos, pool.level, pool.order, pool.start, pool.lvl_off, pool.max_level, puzzle_id, mask, counter, band,
+                lo_n, hi_n, pos, steps, terminated, truncated, out_entry, out_level)
+        return S, W, B, keep
+
+    def start_pool_draw(self, pool, puzzle_id, pos, steps, terminated, truncated, seed, counter, out_entry, out_level,
+                        mask=None, band=None, lo_n=None, hi_n=None, keep_q16=0, lo=0, hi=-1):
+        """``pw_start_pool_draw``: one launch on the current stream, no wait.  The band of an environment is ``lo_n`` / ``hi_n``
+        (int32 ``[B]``) when given, else ``band`` (int32 ``[P, 2]``) when given, else the scalars ``lo`` / ``hi``."""
+        S, W, B, k = self._start_pool_draw_args(pool, puzzle_id, pos, steps, terminated, truncated, counter, out_entry,
+                                                out_level, mask, band, lo_n, hi_n, keep_q16, lo, hi)
+        check(lib.pw_start_pool_draw(self.handle, _ptr(k[0]), _ptr(k[1]), _ptr(k[2]), _ptr(k[3]), W, _ptr(k[4]), _ptr(k[5]), S,
+                                     _ptr(k[6]), _ptr(k[7]), B, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(k[8]), keep_q16, int(lo),
+                                     int(hi), _ptr(k[9]), _ptr(k[10]), _ptr(k[11]), _ptr(k[12]), _ptr(k[13]), _ptr(k[14]),
+                                     _ptr(k[15]), _ptr(k[16]), _ptr(k[17]), self._stream()))
+
+    def bind_start_pool_draw(self, pool, puzzle_id, pos, steps, terminated, truncated, counter, out_entry, out_level, mask=None,
+                             band=None, lo_n=None, hi_n=None, keep_q16=0, lo=0, hi=-1):
+        """Returns ``call(seed)`` == ``start_pool_draw(...)`` on the current stream (the arguments are checked once, here)."""
+        S, W, B, keep = self._start_pool_draw_args(pool, puzzle_id, pos, steps, terminated, truncated, counter, out_entry,
+                                                   out_level, mask, band, lo_n, hi_n, keep_q16, lo, hi)
+        fn, h, dev, lo, hi = lib.pw_start_pool_draw, self.handle, self.device.index, int(lo), int(hi)
+        a = [_ptr(t) for t in keep]
+
+        def call(seed, _keep=keep):
+            rc = fn(h, a[0], a[1], a[2], a[3], W, a[4], a[5], S, a[6], a[7], B, seed & 0xFFFFFFFFFFFFFFFF, a[8], keep_q16, lo, hi,
+                    a[9], a[10], a[11], a[12], a[13], a[14], a[15], a[16], a[17], _raw_stream(dev))
+            if rc:
+                check(rc)
+        return call
+
+    def start_pool_update_bands(self, max_level, stats, base, band, delta=None, min_episodes=32, up_q16=52429, down_q16=13107,
+                                step=1, width=0, hi_min=1, lo_min=1):
+        """``pw_start_pool_update_bands``: one launch on the current stream; ``band`` int32 ``[P, 2]`` and ``base`` int64
+        ``[P, 4]`` are updated in place, ``delta`` (int8 ``[P]``, optional) says how every ``hi`` moved."""
+        fn, P = "pw_start_pool_update_bands", len(self.pset)
+        _tensor_arg(fn, "max_level", max_level, torch.int32, (P,))
+        _tensor_arg(fn, "stats", stats, torch.int64, (P, EPISODE_STATS))
+        _tensor_arg(fn, "base", base, torch.int64, (P, EPISODE_STATS))
+        _tensor_arg(fn, "band", band, torch.int32, (P, 2))
+        if delta is not None:
+            _tensor_arg(fn, "delta", delta, torch.int8, (P,))
+        for name, v, lo, hi in (("min_episodes", min_episodes, 1, (1 << 31) - 1), ("up_q16", up_q16, 0, 65536),
+                                ("down_q16", down_q16, 0, 65536), ("step", step, 1, (1 << 31) - 1),
+                                ("width", width, 0, (1 << 31) - 1), ("hi_min", hi_min, -(1 << 31), (1 << 31) - 1),
+                                ("lo_min", lo_min, -(1 << 31), (1 << 31) - 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"{fn}: {name} must be an integer in {lo} .. {hi}")
+        if up_q16 < down_q16:
+            raise ValueError(f"{fn}: up_q16 must not be below down_q16")
+        check(lib.pw_start_pool_update_bands(self.handle, _ptr(max_level), _ptr(stats), _ptr(base), _ptr(band), _ptr(delta),
+                                             min_episodes, up_q16, down_q16, step, width, hi_min, lo_min, self._stream()))
+
     def set_step_signal(self, word) -> None:
         """``pw_engine_set_step_signal``: ``word`` = a pinned int64 / uint64 tensor of one element, or None."""
         check(lib.pw_engine_set_step_signal(self.handle, None if word is None else c_void_p(word.data_ptr())))
@@ -1261,9 +1387,11 @@ class Engine:
         """``pw_mailbox_open``: the resident step kernel over these arrays (see :class:`Mailbox`)."""
         return Mailbox(self, puzzle_id, pos, steps, reward, dgoals, terminated, truncated, flags, ring, idle_ms)
 
-    def render(self, puzzle_id, pos, obs_storage):
-        check(lib.pw_render(self.handle, _ptr(puzzle_id), _ptr(pos), _ptr(obs_storage), self.obs_stride,
-                            pos.shape[0], self._stream()))
+    def render(self, puzzle_id, pos, obs_storage, retained=False):
+        """``pw_render``; ``retained``: ``pw_render_retained`` -- into the engine's retained buffer only the live pages that
+        differ from what the buffer shows are written (the same bytes; any other buffer gets the full render)."""
+        fn = lib.pw_render_retained if retained else lib.pw_render
+        check(fn(self.handle, _ptr(puzzle_id), _ptr(pos), _ptr(obs_storage), self.obs_stride, pos.shape[0], self._stream()))
 
     def step_render(self, puzzle_id, actions, pos, steps, reward, dgoals, terminated, truncated, obs_storage,
                     flags=0):

@@ -1854,6 +1854,29 @@ int pw_render(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* ob
   return pw_current_exception();  // nothing C++ leaves the C ABI
 }
 
+// pw_render for a state that something other than a step of this engine's pw_step_render left (K27: a start-state draw behind a
+// state-only step): pw_step_render's render half with the record pre-pass in place of the step kernel's records.  Into the
+// retained buffer of the retained (puzzle_id, batch) it writes the live pages only, and with PW_OPT_OBS_CHANGED_PAGES of those
+// the pages whose rows differ from what the buffer shows; into any other buffer it is pw_render.
+int pw_render_retained(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos, void* obs, int64_t env_stride_bytes,
+                       int32_t batch, void* stream) try {
+  if (!e) return pw_fail(PW_EINVAL, "pw_render_retained: null engine");
+  if (batch <= 0) return PW_OK;
+  PwDeviceGuard guard(e->set->device);
+  RenderArgs ra;
+  int rc = fill_render_args(e, puzzle_id, pos, obs, env_stride_bytes, batch, &ra);
+  if (rc != PW_OK) return rc;
+  const int live_form = retained_live_form(e, ra, batch);
+  const bool track = retained_tracks(e, ra, batch, live_form);
+  launch_render(e, ra, batch, static_cast<hipStream_t>(stream), false, (live_form && track && e->ret.shown_valid) ? 3 : live_form,
+                track);
+  if (!live_form) retained_after_full_render(e, ra, batch);
+  if (track) e->ret.shown_valid = true;  // (whichever form: the pre-pass left the new positions in `shown`)
+  return check_launch("pw_render_retained");
+} catch (...) {
+  return pw_current_exception();  // nothing C++ leaves the C ABI
+}
+
 // Step + observation.  With the page-ordered render the step kernel and the render kernel are two
 // launches on the caller's stream (splitting the batch over two streams to hide the 26 us step
 // kernel behind the render of the other half measured 2 % SLOWER); otherwise ONE launch: wave 0

@@ -80,6 +80,22 @@ class VecPushWorld:
             (``pw_resample_weighted``) instead of uniformly: a mode name ("uniform", "failure", "frontier", "given") or a
             ``curriculum.Curriculum``.  Implies ``episode_stats``, needs ``resample=True``.  ``self.curriculum.update()``
             refreshes the weights (one launch, no wait); until the first update the draw is uniform.
+        start_pool: a ``start_pool.StartPool``: every new episode starts from a state of its puzzle drawn on the
+            device from the pool -- in ``reset`` (all / masked environments, behind the initial states) and inside autoreset:
+            ``step`` / ``step_push`` / ``step_push_mask`` become [resample] -> ``pw_start_pool_arm`` -> the step launch (state
+            only) -> ``pw_start_pool_draw`` for the environments that step reset -> [statistics] -> render.  The fused
+            ``pw_step_render`` and ``pw_step_render_delta`` are NOT taken on this path (``fused`` and ``incremental`` are
+            ignored): the draw has to come between the step and the render, which is ``pw_render_retained`` -- a retained
+            buffer still gets only its changed pages, behind a record pre-pass that the fused call does not need.  With ``resample`` a finished environment draws from the pool of its NEW puzzle.  Needs ``autoreset``; the
+            pool must be of a set of this size and state layout on this device.  Environments whose puzzle has no entry (or
+            none in the band) start from the initial state.  ``start_entry`` / ``start_level`` (int32 [B]) hold the pool
+            entry and the level every environment started from (-1 / -1: the initial state), ``start_draws`` counts the draws
+            per environment -- a draw is a function of (seed, environment, count), ``reset(seed=...)`` restarts the counts.
+            ``rollout`` and ``mailbox`` are refused while a pool is set.
+        start_band: "pool" (the pool's own ``band`` tensor, (lo, hi) per puzzle: ``set_band`` / ``update_bands`` move it
+            without touching this object), ``(lo, hi)`` ints (``hi`` None: up to each puzzle's largest level) or two int32
+            device tensors [B], read by every draw.
+        start_keep_initial: the share of new episodes that start from the puzzle's initial state all the same.
     """
 
     # statistics per puzzle and the weighted draw (K25): off unless the constructor was asked for them
@@ -87,6 +103,10 @@ class VecPushWorld:
     curriculum = None
     _call_stats = None
     _call_resample_weighted = None
+    # start-state pools (K27): off unless the constructor was given one
+    start_pool = None
+    _call_pool_arm = None
+    _call_pool_draw = None
 
     def __init__(self, puzzles: Sequence[Union[str, PushWorldPuzzle]], num_envs: int,
                  puzzle_ids: Optional[Sequence[int]] = None, max_steps: Optional[int] = None,
@@ -95,8 +115,11 @@ class VecPushWorld:
                  autoreset: bool = False, fused: bool = True, resample=False, seed: int = 0,
                  incremental: bool = False, engine_options: Optional[dict] = None, tune: Optional[bool] = None,
                  tune_allocations: Optional[int] = None, bind: Optional[bool] = None, episode_stats: bool = False,
-                 curriculum=None):
+                 curriculum=None, start_pool=None, start_band="pool", start_keep_initial: float = 0.0):
         # (the new options' refusals come first: nothing has been parsed or allocated yet)
+        from .start_pool import check_start_options
+
+        start = check_start_options(start_pool, start_band, start_keep_initial, autoreset)
         if curriculum is not None:
             if isinstance(curriculum, str) and curriculum not in _capi.CURRICULUM_MODES:
                 raise ValueError(f"curriculum must be one of {', '.join(_capi.CURRICULUM_MODES)} or a Curriculum, "
@@ -268,6 +291,37 @@ class VecPushWorld:
             if self.curriculum is not None:
                 self._call_resample_weighted = self.engine.bind_resample_weighted(
                     self.puzzle_id, self.episode, self.curriculum.cdf, self.terminated, self.truncated)
+        # start-state pools (K27): nothing is allocated or launched unless a pool was given
+        if start is not None:
+            self._bind_start_pool(start_pool, start_band, *start)
+
+    def _bind_start_pool(self, pool, band, kind, lo, hi, keep_q16) -> None:
+        """The tensors and the ready launch calls of the pool path."""
+        B, dev = self.num_envs, self.device
+        if pool.num_puzzles != self.num_puzzles or pool.npad != int(self.engine.np) or pool.device != dev:
+            raise ValueError(f"the start pool covers {pool.num_puzzles} puzzles with npad {pool.npad} on {pool.device}, "
+                             f"this environment {self.num_puzzles} with npad {int(self.engine.np)} on {dev}")
+        lo_n = hi_n = None
+        if kind == "env":
+            from .search import _dev_tensor
+
+            lo_n = _dev_tensor("start_band: lo", lo, torch.int32, (B,), dev)
+            hi_n = _dev_tensor("start_band: hi", hi, torch.int32, (B,), dev)
+            lo, hi = 0, -1
+        self.start_pool = pool
+        self.start_seed = self.seed
+        self.start_pending = torch.zeros((B,), dtype=torch.uint8, device=dev)
+        self.start_entry = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self.start_level = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        # (uint32 counter bits over an int32 allocation, like `episode`)
+        self.start_draws = torch.zeros((B,), dtype=torch.int32, device=dev).view(torch.uint32)
+        self._start_kw = dict(band=pool.band if kind == "pool" else None, lo_n=lo_n, hi_n=hi_n, keep_q16=keep_q16, lo=lo, hi=hi)
+        self._call_pool_arm = self.engine.bind_start_pool_arm(self.terminated, self.truncated, self.start_pending)
+        self._call_pool_draw = self.engine.bind_start_pool_draw(
+            pool, self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, self.start_draws, self.start_entry,
+            self.start_level, mask=self.start_pending, **self._start_kw)
+        if pool.stats is None:
+            pool.stats = self.stats  # the default record of pool.update_bands
 
     # --------------------------------------------------------------------------------
     @property
@@ -289,6 +343,19 @@ class VecPushWorld:
             self.seed = int(seed)
             self.episode.zero_()
         self._reset_states(mask)
+        if self.start_pool is not None:
+            # the (masked) environments draw their start state, as reset_from_tables does behind the initial states
+            if seed is not None:
+                self.start_seed = int(seed)
+                self.start_draws.view(torch.int32).zero_()
+            if mask is None:
+                self.start_entry.fill_(-1), self.start_level.fill_(-1)
+            else:
+                self.start_entry.masked_fill_(mask.bool(), -1), self.start_level.masked_fill_(mask.bool(), -1)
+            self.engine.start_pool_draw(self.start_pool, self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated,
+                                        self.start_seed, self.start_draws, self.start_entry, self.start_level, mask=mask,
+                                        **self._start_kw)
+            self._obs_current = False
         if self.obs is not None:
             self._render()
         return self.obs
@@ -304,11 +371,13 @@ class VecPushWorld:
         if self._bind and (self.bound_info is None or self.resample or mask is None):
             self.bound_info = self.engine.bind(self.puzzle_id)  # (reads the segment count back: later launches have the exact grid)
 
-    def _render(self) -> None:
+    def _render(self, retained: bool = False) -> None:
+        """``retained`` (the pool path): ``pw_render_retained`` -- a retained buffer gets only the pages that differ from what
+        it shows; the same bytes."""
         if self.observation == "cells":
             self.engine.render_cells(self.puzzle_id, self.pos, self.obs)
         else:
-            self.engine.render(self.puzzle_id, self.pos, self._obs_storage)
+            self.engine.render(self.puzzle_id, self.pos, self._obs_storage, retained=retained)
         self._obs_current = True
 
     def step(self, actions: torch.Tensor):
@@ -331,6 +400,19 @@ class VecPushWorld:
             # finished environments draw the puzzle their autoreset (inside this step) starts from
             self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
                                  self.sample_table)
+        if self._call_pool_draw is not None:
+            # the pool path: the environments this step resets are noted before it and draw their start state behind it; the
+            # render follows the draw (never the fused calls; pw_render_retained: a retained buffer gets the pages that differ
+            # from what it shows)
+            self._call_pool_arm()
+            self._call_step(actions.data_ptr())
+            self._call_pool_draw(self.start_seed)
+            if self._call_stats is not None:
+                self._call_stats()
+            if self.obs is None:
+                return None, self.reward, self.terminated, self.truncated
+            self._render(retained=True)
+            return self.obs, self.reward, self.terminated, self.truncated
         if self.obs is None:
             self._call_step(actions.data_ptr())  # one ctypes call with ready arguments: the launch is host bound
             if self._call_stats is not None:
@@ -373,6 +455,8 @@ class VecPushWorld:
         Returns ``(reward, terminated, truncated)`` of the last step, or, with ``history=True``,
         the per-step tensors of shape [T, B].
         """
+        if self.start_pool is not None:
+            raise ValueError("rollout() is not available with a start_pool: the resets inside the launch draw nothing; use step()")
         if self.stats is not None:
             raise RuntimeError("rollout() is not available while statistics per puzzle are kept (episode_stats / curriculum): "
                                "the steps inside the launch cannot be observed; use step()")
@@ -401,6 +485,8 @@ class VecPushWorld:
         ``observation=None`` (this object's ``pos`` / ``steps`` / ``reward`` / ... tensors are kept up to date); state only, up to
         65 536 environments; ``step`` / ``rollout`` / ``reset`` of this object fail while it is open.  Bad
         actions are flagged 0xFF in ``terminated`` / ``truncated`` and counted (``counters()['bad_actions']``) as in ``step``."""
+        if self.start_pool is not None:
+            raise ValueError("mailbox() is not available with a start_pool: the resident kernel's resets draw nothing; use step()")
         if self.stats is not None:
             raise RuntimeError("mailbox() is not available while statistics per puzzle are kept (episode_stats / curriculum): "
                                "the resident kernel's steps are not counted; use step()")
@@ -565,13 +651,17 @@ class VecPushWorld:
             # finished environments draw the puzzle their autoreset (inside this step) starts from
             self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
                                  self.sample_table)
+        if self._call_pool_draw is not None:
+            self._call_pool_arm()  # (K27: the environments this call resets draw their start state behind it)
         self.engine.step_push(self.puzzle_id, push_from, push_action, self.pos, self.steps, self.reward, self.dgoals,
                               self.terminated, self.truncated, self.push_moves_taken, self.push_status, self.flags)
+        if self._call_pool_draw is not None:
+            self._call_pool_draw(self.start_seed)
         if self._call_stats is not None:
             self._call_stats()
         self._obs_current = False
         if self.obs is not None:
-            self._render()
+            self._render(retained=self._call_pool_draw is not None)
         return self.obs, self.reward, self.terminated, self.truncated, self.push_moves_taken, self.push_status
 
     def _push_choice(self, push_from, push_action, choice):
@@ -625,16 +715,24 @@ class VecPushWorld:
             # finished environments draw the puzzle their autoreset (inside this step) starts from
             self.engine.resample(self.puzzle_id, self.episode, self.seed, self.terminated, self.truncated,
                                  self.sample_table)
+        if self._call_pool_draw is not None:
+            self._call_pool_arm()  # (K27: the environments this call resets draw their start state behind it)
         self.engine.step_push_mask(self.puzzle_id, push_from, push_action, self.pos, self.steps, self.reward, self.dgoals,
                                    self.terminated, self.truncated, self.push_moves_taken, self.push_status,
                                    self.push_view_mask, self.push_view_count, self.push_walk_map, self.push_region_size,
                                    self._push_view_pos, self._push_view_id,
                                    self.flags | (_capi.PUSH_END_STUCK if end_stuck else 0))
+        if self._call_pool_draw is not None:
+            self._call_pool_draw(self.start_seed)
         if self._call_stats is not None:
             self._call_stats()
+        if self._call_pool_draw is not None:
+            # the draw made the views of the drawn environments stale: the observe call rebuilds exactly those, so the mask
+            # returned describes the drawn states (the stuck rule sees a drawn state at the next call)
+            self.observe_pushes()
         self._obs_current = False
         if self.obs is not None:
-            self._render()
+            self._render(retained=self._call_pool_draw is not None)
         return PushStep(self.obs, self.reward, self.terminated, self.truncated, self.push_moves_taken, self.push_status,
                         self.push_view_mask, self.push_view_count)
 
@@ -777,7 +875,8 @@ class VecPushWorld:
 
         ``self.start_row`` / ``self.start_cost`` (int32 [B]) hold the table row and the cost-to-go every environment started
         from (-1 / -1 without a table); ``self.table_draws`` counts the draws per environment -- a draw is a function of
-        (seed, environment, count), ``seed`` restarts the counts.  Autoreset inside ``step`` does not draw from tables: step
+        (seed, environment, count), ``seed`` restarts the counts.  Autoreset inside ``step`` does not draw from tables: put their
+        states into a ``start_pool.StartPool`` (``StartPool.from_tables``) and pass ``start_pool=`` to the constructor, or step
         with ``autoreset=False`` and call ``reset_from_tables(tables, mask=terminated | truncated)``."""
         tables = self._own_tables(tables)
         if mask is not None:

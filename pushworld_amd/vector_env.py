@@ -21,6 +21,7 @@ from .config import PUZZLE_EXTENSION
 from .puzzle import DEFAULT_BORDER_WIDTH, DEFAULT_PIXELS_PER_CELL, NUM_ACTIONS, PushWorldPuzzle
 from ._single_env import pool_frame
 from .utils.filesystem import iter_files_with_extension
+from .start_pool import check_start_options
 from .vec_env import VecPushWorld
 
 
@@ -66,13 +67,24 @@ def _load_pool(puzzle_path, standard_padding: bool):
 class _VectorCore:
     def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int], border_width: int, pixels_per_cell: int,
                  standard_padding: bool, observation: str, seed: int, sample_table, device: Optional[int],
-                 to_numpy: bool, incremental: bool = True, curriculum=None, curriculum_update_every: Optional[int] = None):
+                 to_numpy: bool, incremental: bool = True, curriculum=None, curriculum_update_every: Optional[int] = None,
+                 start_pool=None, start_band="pool", start_keep_initial: float = 0.0, start_update_every=None):
         if curriculum_update_every is not None:
             if curriculum is None:
                 raise ValueError("curriculum_update_every needs a curriculum")
             if isinstance(curriculum_update_every, bool) or not isinstance(curriculum_update_every, int) \
                     or curriculum_update_every < 1:
                 raise ValueError("curriculum_update_every must be None or an integer >= 1")
+        update_kw = {}
+        if start_update_every is not None:
+            if start_pool is None:
+                raise ValueError("start_update_every needs a start_pool")
+            if isinstance(start_update_every, dict):  # {"every": k, ...}: the other entries are update_bands' arguments
+                update_kw = dict(start_update_every)
+                start_update_every = update_kw.pop("every", None)
+            if isinstance(start_update_every, bool) or not isinstance(start_update_every, int) or start_update_every < 1:
+                raise ValueError("start_update_every must be None, an integer >= 1 or a dict with such an 'every'")
+        check_start_options(start_pool, start_band, start_keep_initial, True)
         if border_width < 1:
             raise ValueError("border_width must be >= 1")
         if pixels_per_cell < 3:
@@ -84,7 +96,13 @@ class _VectorCore:
         self.vec = VecPushWorld(puzzles, num_envs, max_steps=max_steps, border_width=border_width,
                                 pixels_per_cell=pixels_per_cell, observation=observation, pad_cells=pad,
                                 device=device, autoreset=True, resample=True if sample_table is None else sample_table,
-                                seed=seed, incremental=incremental and not cells, curriculum=curriculum)
+                                seed=seed, incremental=incremental and not cells, curriculum=curriculum,
+                                episode_stats=start_update_every is not None, start_pool=start_pool, start_band=start_band,
+                                start_keep_initial=start_keep_initial)
+        # ... and after every `start_update_every`-th step the bands of the start pool move with the statistics (K27)
+        self.start_update_every = start_update_every
+        self._start_update_kw = update_kw
+        self._steps_to_start_update = start_update_every
         # steps counted on the host (no wait): after every `curriculum_update_every`-th step the weights are made anew from the
         # statistics that step left, so the draws of the following step are the first to use them
         self.curriculum_update_every = curriculum_update_every
@@ -107,6 +125,12 @@ class _VectorCore:
         return self.vec.puzzles
 
     @property
+    def start_pool(self):
+        """The ``start_pool.StartPool`` new episodes draw their start state from (None: the puzzle's initial state).
+        ``vec.start_entry`` / ``vec.start_level`` hold what every environment started from."""
+        return self.vec.start_pool
+
+    @property
     def curriculum(self):
         """The ``curriculum.Curriculum`` the puzzles are drawn by (None: uniformly or from the sample table)."""
         return self.vec.curriculum
@@ -115,12 +139,24 @@ class _VectorCore:
         """``VecPushWorld.puzzle_stats``: the statistics per puzzle kept on the device (needs ``curriculum``).  Waits."""
         return self.vec.puzzle_stats()
 
+    def _start_info(self, info: dict) -> dict:
+        """With a start pool: ``start_entry`` / ``start_level`` int32 [B], the pool entry and the level every environment's
+        episode started from (-1 / -1: the puzzle's initial state).  Without one ``info`` is as it was."""
+        if self.vec.start_pool is not None:
+            info["start_entry"], info["start_level"] = self._out(self.vec.start_entry), self._out(self.vec.start_level)
+        return info
+
     def _count_step(self) -> None:
         if self._steps_to_update is not None:
             self._steps_to_update -= 1
             if self._steps_to_update == 0:
                 self.vec.curriculum.update()
                 self._steps_to_update = self.curriculum_update_every
+        if self._steps_to_start_update is not None:
+            self._steps_to_start_update -= 1
+            if self._steps_to_start_update == 0:
+                self.vec.start_pool.update_bands(self.vec.stats, **self._start_update_kw)
+                self._steps_to_start_update = self.start_update_every
 
     @property
     def puzzle_ids(self) -> torch.Tensor:
@@ -194,6 +230,13 @@ class PushWorldVectorEnv(_VectorCore):
             ("uniform", "failure", "frontier", "given") or a ``curriculum.Curriculum``; not together with ``sample_table``.
             ``puzzle_stats()`` reads the statistics, ``curriculum.update()`` refreshes the weights.
         curriculum_update_every: refresh the weights after every that many steps (counted on the host: no wait).
+        start_pool, start_band, start_keep_initial: ``VecPushWorld``'s: new episodes start from states drawn
+            on the device from a ``start_pool.StartPool`` of a set of these puzzles (``StartPool.from_tables`` on any
+            ``VecPushWorld`` over the same puzzles).  ``info["start_entry"]`` / ``info["start_level"]`` (with a pool only; also
+            ``vec.start_entry`` / ``vec.start_level``, which the dm_env forms read there) hold what every episode started from.
+        start_update_every: move the pool's bands with the statistics per puzzle (``StartPool.update_bands``, one launch) after
+            every that many steps, counted on the host; a dict ``{"every": k, "min_episodes": ..., "up": ..., ...}`` passes
+            ``update_bands``' arguments.  Turns the statistics on (``puzzle_stats()``).
         to_numpy: return host numpy arrays (and python-side checks) instead of device tensors.
     """
 
@@ -204,10 +247,12 @@ class PushWorldVectorEnv(_VectorCore):
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
                  device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
-                 curriculum_update_every: Optional[int] = None):
+                 curriculum_update_every: Optional[int] = None, start_pool=None, start_band="pool",
+                 start_keep_initial: float = 0.0, start_update_every=None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
                          observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
-                         curriculum_update_every=curriculum_update_every)
+                         curriculum_update_every=curriculum_update_every, start_pool=start_pool, start_band=start_band,
+                         start_keep_initial=start_keep_initial, start_update_every=start_update_every)
         self.single_action_space = _compat.make_discrete(NUM_ACTIONS)
         self.single_observation_space = _compat.make_box(0, self._obs_high, self._obs_shape, self._obs_dtype)
         self.action_space = _BatchSpace(_compat.Discrete(NUM_ACTIONS), num_envs)
@@ -224,7 +269,7 @@ class PushWorldVectorEnv(_VectorCore):
     def _info(self) -> dict:
         """``puzzle_state``: int8 [B, NP, 2] (x, y) positions, agent first, zero beyond a puzzle's movables
         (the batched form of the reference's ``info["puzzle_state"]``, gym_env.py:186,226)."""
-        return {"puzzle_id": self._out(self.vec.puzzle_id), "puzzle_state": self._out(self.vec.pos)}
+        return self._start_info({"puzzle_id": self._out(self.vec.puzzle_id), "puzzle_state": self._out(self.vec.pos)})
 
     def step_async(self, actions) -> None:
         self._launch(actions)
@@ -265,10 +310,12 @@ class PushWorldDmVectorEnv(_VectorCore):
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
                  device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
-                 curriculum_update_every: Optional[int] = None):
+                 curriculum_update_every: Optional[int] = None, start_pool=None, start_band="pool",
+                 start_keep_initial: float = 0.0, start_update_every=None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
                          observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
-                         curriculum_update_every=curriculum_update_every)
+                         curriculum_update_every=curriculum_update_every, start_pool=start_pool, start_band=start_band,
+                         start_keep_initial=start_keep_initial, start_update_every=start_update_every)
         self._action_spec = _compat.make_discrete_array(NUM_ACTIONS, int, "action")
         self._observation_spec = _compat.make_bounded_array(self._obs_shape, self._obs_dtype, "board", 0,
                                                             self._obs_high)
@@ -407,10 +454,12 @@ class PushWorldPushVectorEnv(_PushCore):
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
                  device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
-                 curriculum_update_every: Optional[int] = None):
+                 curriculum_update_every: Optional[int] = None, start_pool=None, start_band="pool",
+                 start_keep_initial: float = 0.0, start_update_every=None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
                          observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
-                         curriculum_update_every=curriculum_update_every)
+                         curriculum_update_every=curriculum_update_every, start_pool=start_pool, start_band=start_band,
+                         start_keep_initial=start_keep_initial, start_update_every=start_update_every)
         self.single_action_space, self.action_space = push_action_spaces(self.map_h, self.map_w, num_envs)
         self.single_observation_space = _compat.make_box(0, self._obs_high, self._obs_shape, self._obs_dtype)
         self.observation_space = _BatchSpace(_compat.Box(0, self._obs_high, self._obs_shape, self._obs_dtype),
@@ -426,10 +475,10 @@ class PushWorldPushVectorEnv(_PushCore):
 
     def _info(self, moves, status) -> dict:
         v = self.vec
-        return {"action_mask": self._out(self._action_mask()), "push_mask": self._out(v.push_view_mask),
-                "num_pushes": self._out(v.push_view_count), "moves": self._out(moves), "status": self._out(status),
-                "stuck": self._out((v.push_view_count == 0) & (v.terminated == 0)),
-                "puzzle_id": self._out(v.puzzle_id), "puzzle_state": self._out(v.pos)}
+        return self._start_info({"action_mask": self._out(self._action_mask()), "push_mask": self._out(v.push_view_mask),
+                                 "num_pushes": self._out(v.push_view_count), "moves": self._out(moves),
+                                 "status": self._out(status), "stuck": self._out((v.push_view_count == 0) & (v.terminated == 0)),
+                                 "puzzle_id": self._out(v.puzzle_id), "puzzle_state": self._out(v.pos)})
 
     def step_async(self, actions) -> None:
         self._launch(actions)
@@ -460,10 +509,12 @@ class PushWorldPushDmVectorEnv(_PushCore):
                  border_width: int = DEFAULT_BORDER_WIDTH, pixels_per_cell: int = DEFAULT_PIXELS_PER_CELL,
                  standard_padding: bool = False, observation: str = "float32", seed: int = 0, sample_table=None,
                  device: Optional[int] = None, to_numpy: bool = False, curriculum=None,
-                 curriculum_update_every: Optional[int] = None):
+                 curriculum_update_every: Optional[int] = None, start_pool=None, start_band="pool",
+                 start_keep_initial: float = 0.0, start_update_every=None):
         super().__init__(puzzle_path, num_envs, max_steps, border_width, pixels_per_cell, standard_padding,
                          observation, seed, sample_table, device, to_numpy, curriculum=curriculum,
-                         curriculum_update_every=curriculum_update_every)
+                         curriculum_update_every=curriculum_update_every, start_pool=start_pool, start_band=start_band,
+                         start_keep_initial=start_keep_initial, start_update_every=start_update_every)
         self._action_spec = _compat.make_discrete_array(self.num_choices, int, "action")
         self._observation_spec = {
             "board": _compat.make_bounded_array(self._obs_shape, self._obs_dtype, "board", 0, self._obs_high),
