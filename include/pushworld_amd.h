@@ -1838,6 +1838,65 @@ int pw_push_plan_batch_read_links(PwPushPlanBatch* b, int32_t item, int64_t firs
 int pw_push_plan_batch_cancel(PwPushPlanBatch* b);
 void pw_push_plan_batch_destroy(PwPushPlanBatch* b);
 
+/* Cost-to-go guidance inside the step (csrc/pw_guide.inc, K28): ONE launch behind a step launch (and behind pw_start_pool_draw,
+ * in front of pw_episode_stats) leaves per environment the exact cost-to-go of the state the step left, its optimal / safe
+ * action bits, whether it is a dead end and the potential-shaped reward; it counts guided / optimal / dead-entering / unknown
+ * steps per puzzle and, asked to, truncates an environment that has just entered a dead end.  One lane per environment, no
+ * allocation, no synchronisation, capturable.  The integers are exact and independent of launch geometry and atomic order; the
+ * shaped reward is made of individually rounded double operations (no fused multiply-add), so it is too.  Every argument error
+ * returns PW_EINVAL with the function's name and the offending argument in pw_last_error, before anything is read through a
+ * pointer.
+ *
+ * The source of the lookup -- exactly one of:
+ *   tables   a PwSolveBatch of this engine with a run (the fused form): the kernel looks (puzzle_id[i], pos[i]) up itself.  Its
+ *            answer (c, a) is pw_solve_batch_query's cost and acts -- the first N movables of the row only, -2 / 0 for a movable
+ *            outside 0 .. 15 or outside the grid and for a state the table does not hold, -1 for a dead end -- and -2 / 0 also
+ *            for a puzzle without a stored table and for an id outside 0 .. P - 1.
+ *   cost_in  device int32 [n], with acts_in device uint8 [n] or NULL (the applied form): (c, a) = (cost_in[i], acts_in[i] or 0),
+ *            what the query launches of any table kind wrote into buffers that held -2 / 0.  The kernel stores cost_in[i] = -2
+ *            and acts_in[i] = 0 behind its read, so that the next call's queries start clean.
+ * Environment state: puzzle_id int32 [n], pos int8 [n][npad][2], reward double [n] (read only, may be NULL without shaped),
+ * terminated uint8 [n] (read only), truncated uint8 [n] (read and written), mask uint8 [n] or NULL.
+ * Guide state, [n] each: cost int32 (in / out), acts uint8 (out), seen uint8 (in / out: the environment's flags as the previous
+ * guide call left them), dead uint8 (out), shaped double (out, may be NULL).
+ * Parameters: dead_cost int32 [P] (may be NULL without shaped), gamma, scale, counts int64 [P][PW_GUIDE_COUNTS] (may be NULL).
+ *
+ * The rule for environment i < n, with p = puzzle_id[i] and (c, a) the lookup of the state as the step left it:
+ *   0. mask != NULL and mask[i] == 0: nothing is written for i at all (cost_in / acts_in included).
+ *   1. PW_GUIDE_REFRESH (behind a reset or anything else that moved the environment outside a step): cost[i] = c, acts[i] = a,
+ *      dead[i] = (c == -1), seen[i] = (terminated[i] | truncated[i]) != 0.  Nothing else is written or counted.
+ *   Otherwise:
+ *   2. fresh = PW_GUIDE_AUTORESET and seen[i] != 0 -- the step that just ran reset this environment (the 0xFF flags of a refused
+ *      action set seen too: exactly the set a PW_STEP_AUTORESET step resets); refused = terminated[i] == 0xFF;
+ *      c_prev = cost[i].
+ *   3. cut: PW_GUIDE_END_DEAD, c == -1, terminated[i] == 0, truncated[i] == 0 and not fresh: truncated[i] = 1 and
+ *      episodes_ended of pw_counters advances by one (PW_PUSH_END_STUCK's rule).  A fresh state is never cut: a puzzle that is
+ *      dead at its start is cut after its first step.
+ *   4. shaped != NULL: F = 0 when fresh, refused, c == -2 or c_prev == -2; otherwise, with
+ *      phi(x) = -(scale * (double)(x == -1 ? dead_cost[p] : x)), F = gamma * phi(c) - phi(c_prev), every operation rounded to
+ *      double on its own.  shaped[i] = reward[i] + F.  reward is never written.  (dead_cost of an id outside the set counts 0.)
+ *   5. counts != NULL, 0 <= p < P, not fresh, not refused; guided = c != -2 and c_prev != -2:
+ *        counts[p][PW_GUIDE_GUIDED]       += 1 when guided
+ *        counts[p][PW_GUIDE_OPTIMAL]      += 1 when guided, c_prev > 0 and c == c_prev - 1
+ *        counts[p][PW_GUIDE_DEAD_ENTERED] += 1 when guided, c == -1 and c_prev >= 0
+ *        counts[p][PW_GUIDE_UNKNOWN]      += 1 when c == -2
+ *   6. cost[i] = c, acts[i] = a, dead[i] = (c == -1), seen[i] = (terminated[i] | truncated[i] after the cut) != 0.
+ * n == 0 is a no-op.  Refused: a null engine; both sources or neither; acts_in without cost_in; a null puzzle_id, pos,
+ * terminated, truncated, cost, acts, seen or dead; shaped without reward or dead_cost; npad not 4 / 8 / 16 / 32; n < 0; flag
+ * bits other than the three; tables of another engine or without a run. */
+#define PW_GUIDE_AUTORESET 1u /* the step ran with PW_STEP_AUTORESET (the same bit) */
+#define PW_GUIDE_END_DEAD 2u
+#define PW_GUIDE_REFRESH 4u
+#define PW_GUIDE_COUNTS 4 /* GUIDED, OPTIMAL, DEAD_ENTERED, UNKNOWN */
+#define PW_GUIDE_GUIDED 0
+#define PW_GUIDE_OPTIMAL 1
+#define PW_GUIDE_DEAD_ENTERED 2
+#define PW_GUIDE_UNKNOWN 3
+int pw_guide_step(PwEngine* e, PwSolveBatch* tables, int32_t* cost_in, uint8_t* acts_in, const int32_t* puzzle_id,
+                  const int8_t* pos, int32_t npad, const double* reward, const uint8_t* terminated, uint8_t* truncated,
+                  const uint8_t* mask, int32_t n, int32_t* cost, uint8_t* acts, uint8_t* seen, uint8_t* dead, double* shaped,
+                  const int32_t* dead_cost, double gamma, double scale, int64_t* counts, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

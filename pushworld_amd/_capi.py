@@ -327,12 +327,20 @@ SIGNATURES = {
                                    c_void_p]),
     "pw_start_pool_update_bands": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                            ctypes.c_uint32, ctypes.c_uint32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "pw_guide_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
+                              ctypes.c_double, c_void_p, ctypes.c_uint32, c_void_p]),
 }
 
 # pw_episode_stats: the columns of a statistics block; pw_curriculum_update: its modes (include/pushworld_amd.h)
 EPISODE_STATS = 4
 STATS_EPISODES, STATS_SOLVED, STATS_STEPS, STATS_SOLVED_STEPS = 0, 1, 2, 3
 CURRICULUM_MODES = {"uniform": 0, "failure": 1, "frontier": 2, "given": 3}
+
+# pw_guide_step: its flags and the columns of a counts block (include/pushworld_amd.h)
+GUIDE_AUTORESET, GUIDE_END_DEAD, GUIDE_REFRESH = 1, 2, 4
+GUIDE_COUNTS = 4
+GUIDE_GUIDED, GUIDE_OPTIMAL, GUIDE_DEAD_ENTERED, GUIDE_UNKNOWN = 0, 1, 2, 3
 
 # pw_plan_replay_check verdicts and the `include` choices (include/pushworld_amd.h)
 REPLAY_VALID, REPLAY_NOT_GOAL, REPLAY_EARLY, REPLAY_NONE, REPLAY_CUT, REPLAY_SKIPPED = 1, 0, 2, -1, -2, -3
@@ -1060,6 +1068,67 @@ class Engine:
 
         def call(seed, _keep=keep):
             rc = fn(h, a[0], a[1], a[2], a[3], seed & 0xFFFFFFFFFFFFFFFF, a[4], B, _raw_stream(dev))
+            if rc:
+                check(rc)
+        return call
+
+    # cost-to-go guidance behind the step (pw_guide_step)
+    def _guide_args(self, tables, cost_in, acts_in, puzzle_id, pos, reward, terminated, truncated, mask, cost, acts, seen, dead,
+                    shaped, dead_cost, gamma, scale, counts, flags):
+        """The checked argument list of ``pw_guide_step`` up to the stream; ``tables`` is a ``pw_solve_batch`` handle or None."""
+        fn, P, npad = "pw_guide_step", len(self.pset), int(self.np)
+        if (tables is None) == (cost_in is None):
+            raise ValueError(f"{fn}: pass exactly one source, tables or cost_in")
+        B = _tensor_arg(fn, "puzzle_id", puzzle_id, torch.int32, (None,))[0]
+        _tensor_arg(fn, "pos", pos, torch.int8, (B, npad, 2))
+        if cost_in is not None:
+            _tensor_arg(fn, "cost_in", cost_in, torch.int32, (B,))
+        if acts_in is not None:
+            if cost_in is None:
+                raise ValueError(f"{fn}: acts_in goes with cost_in")
+            _tensor_arg(fn, "acts_in", acts_in, torch.uint8, (B,))
+        if reward is not None or shaped is not None:
+            _tensor_arg(fn, "reward", reward, torch.float64, (B,))
+        _tensor_arg(fn, "terminated", terminated, torch.uint8, (B,))
+        _tensor_arg(fn, "truncated", truncated, torch.uint8, (B,))
+        if mask is not None:
+            _tensor_arg(fn, "mask", mask, torch.uint8, (B,))
+        _tensor_arg(fn, "cost", cost, torch.int32, (B,))
+        _tensor_arg(fn, "acts", acts, torch.uint8, (B,))
+        _tensor_arg(fn, "seen", seen, torch.uint8, (B,))
+        _tensor_arg(fn, "dead", dead, torch.uint8, (B,))
+        if shaped is not None:
+            _tensor_arg(fn, "shaped", shaped, torch.float64, (B,))
+        if dead_cost is not None or shaped is not None:
+            _tensor_arg(fn, "dead_cost", dead_cost, torch.int32, (P,))
+        if counts is not None:
+            _tensor_arg(fn, "counts", counts, torch.int64, (P, GUIDE_COUNTS))
+        flags = int(flags)
+        if flags & ~(GUIDE_AUTORESET | GUIDE_END_DEAD | GUIDE_REFRESH) or flags < 0:
+            raise ValueError(f"{fn}: unknown flags (GUIDE_AUTORESET / GUIDE_END_DEAD / GUIDE_REFRESH)")
+        keep = (cost_in, acts_in, puzzle_id, pos, reward, terminated, truncated, mask, cost, acts, seen, dead, shaped, dead_cost,
+                counts)
+        p = [_ptr(t) for t in keep]
+        return keep, [tables, p[0], p[1], p[2], p[3], npad, p[4], p[5], p[6], p[7], B, p[8], p[9], p[10], p[11], p[12], p[13],
+                      float(gamma), float(scale), p[14], flags]
+
+    def guide_step(self, tables, cost_in, acts_in, puzzle_id, pos, reward, terminated, truncated, mask, cost, acts, seen, dead,
+                   shaped, dead_cost, gamma, scale, counts, flags):
+        """``pw_guide_step``: one launch on the current stream, no wait.  ``tables`` is the handle of a ``SolutionTableBatch``
+        (the fused form) or None with ``cost_in`` (and ``acts_in``) holding what table queries wrote (the applied form)."""
+        _, args = self._guide_args(tables, cost_in, acts_in, puzzle_id, pos, reward, terminated, truncated, mask, cost, acts,
+                                   seen, dead, shaped, dead_cost, gamma, scale, counts, flags)
+        check(lib.pw_guide_step(self.handle, *args, self._stream()))
+
+    def bind_guide_step(self, tables, cost_in, acts_in, puzzle_id, pos, reward, terminated, truncated, mask, cost, acts, seen,
+                        dead, shaped, dead_cost, gamma, scale, counts, flags):
+        """Returns ``call()`` == ``guide_step(...)`` on the current stream (the arguments are checked once, here)."""
+        keep, args = self._guide_args(tables, cost_in, acts_in, puzzle_id, pos, reward, terminated, truncated, mask, cost, acts,
+                                      seen, dead, shaped, dead_cost, gamma, scale, counts, flags)
+        fn, h, dev = lib.pw_guide_step, self.handle, self.device.index
+
+        def call(_keep=keep):
+            rc = fn(h, *args, _raw_stream(dev))
             if rc:
                 check(rc)
         return call

@@ -473,4 +473,5 @@ struct PageRec {
 #include "pw_push_plan_batch.inc"
 #include "pw_curriculum.inc"
 #include "pw_start_pool.inc"
+#include "pw_guide.inc"
 #include "pw_generate.inc"

@@ -107,6 +107,9 @@ class VecPushWorld:
     start_pool = None
     _call_pool_arm = None
     _call_pool_draw = None
+    # cost-to-go guidance (K28): off unless set_guide was called
+    guide = None
+    _call_guide = None
 
     def __init__(self, puzzles: Sequence[Union[str, PushWorldPuzzle]], num_envs: int,
                  puzzle_ids: Optional[Sequence[int]] = None, max_steps: Optional[int] = None,
@@ -333,6 +336,8 @@ class VecPushWorld:
         self.puzzle_id.copy_(torch.as_tensor(np.asarray(puzzle_ids), dtype=torch.int32))
         if self._bind and self.bound_info is not None:
             self.bound_info = self.engine.bind(self.puzzle_id)
+        if self.guide is not None:
+            self.guide.refresh()
 
     def reset(self, mask: Optional[torch.Tensor] = None, seed: Optional[int] = None):
         """gym_env.py:150-186 for every (masked) environment; returns the observation tensor.
@@ -356,6 +361,8 @@ class VecPushWorld:
                                         self.start_seed, self.start_draws, self.start_entry, self.start_level, mask=mask,
                                         **self._start_kw)
             self._obs_current = False
+        if self.guide is not None:
+            self.guide.refresh(mask)
         if self.obs is not None:
             self._render()
         return self.obs
@@ -407,6 +414,8 @@ class VecPushWorld:
             self._call_pool_arm()
             self._call_step(actions.data_ptr())
             self._call_pool_draw(self.start_seed)
+            if self._call_guide is not None:
+                self._call_guide()  # (K28: a drawn start state already carries its cost)
             if self._call_stats is not None:
                 self._call_stats()
             if self.obs is None:
@@ -415,6 +424,8 @@ class VecPushWorld:
             return self.obs, self.reward, self.terminated, self.truncated
         if self.obs is None:
             self._call_step(actions.data_ptr())  # one ctypes call with ready arguments: the launch is host bound
+            if self._call_guide is not None:
+                self._call_guide()
             if self._call_stats is not None:
                 self._call_stats()
             return None, self.reward, self.terminated, self.truncated
@@ -427,6 +438,8 @@ class VecPushWorld:
         else:
             self._call_step(actions.data_ptr())
             self.engine.render(self.puzzle_id, self.pos, self._obs_storage)
+        if self._call_guide is not None:
+            self._call_guide()  # (K28, behind the fused render too: the render reads no flags)
         if self._call_stats is not None:
             self._call_stats()  # the episodes this step ended, per puzzle
         self._obs_current = True
@@ -439,6 +452,55 @@ class VecPushWorld:
 
     def counters_reset(self) -> None:
         self.engine.counters_reset()
+
+    def set_guide(self, tables_or_guide, **kw):
+        """Cost-to-go guidance inside the step (``guide.ValueGuide``): one ``pw_guide_step`` launch follows the
+        step launch (and the pool draw) of ``step`` / ``step_push`` / ``step_push_mask``, in front of the statistics and the
+        render -- [resample] -> [arm] -> step -> [draw] -> guide -> [stats] -> render -- and keeps ``self.cost`` (int32 [B]: the
+        exact cost-to-go of every environment's state, -1 at a dead end, -2 unknown), ``self.dead`` (uint8 [B]),
+        ``self.shaped_reward`` (float64 [B]) and ``self.guide.acts`` / ``optimal_actions`` / ``safe_actions`` current.
+        ``tables_or_guide``: one ``solution_tables`` batch (the fused form), a list of tables of one level (the applied form:
+        their own queries, then the launch), a ready ``ValueGuide`` made on this environment, or None, which removes the guide.
+        ``kw``: ``gamma``, ``scale``, ``dead_cost``, ``end_dead``, ``shaping``, ``counts`` of ``ValueGuide``.  ``end_dead``
+        (needs ``autoreset``) truncates an environment that has just entered a dead end: ``pw_episode_stats`` counts it in the
+        same call as ended and unsolved, the next call's autoreset (and pool draw) restarts it.  ``reset``,
+        ``reset_from_tables``, ``reset_from_push_tables``, ``set_states`` and ``set_puzzle_ids`` refresh the guide for the
+        environments they touch; ``rollout`` and ``mailbox`` are refused while a guide is set.  A method and not a constructor
+        argument because tables are made on the environment's own engine.  Returns the ``ValueGuide`` (None when removed)."""
+        from .guide import ValueGuide
+
+        if tables_or_guide is None:
+            if kw:
+                raise ValueError("set_guide(None) removes the guide and takes no options")
+            self.guide = self._call_guide = None
+            return None
+        if isinstance(tables_or_guide, ValueGuide):
+            if kw:
+                raise ValueError("a ready ValueGuide carries its own options")
+            if tables_or_guide.vec is not self:
+                raise ValueError("the guide must be made on this environment (ValueGuide(vec, tables))")
+            guide = tables_or_guide
+        else:
+            guide = ValueGuide(self, tables_or_guide, **kw)
+        self.guide, self._call_guide = guide, guide.step
+        if self._has_reset:
+            guide.refresh()
+        return guide
+
+    @property
+    def cost(self):
+        """int32 [B]: the guide's cost-to-go of every environment's current state (None without a guide)."""
+        return None if self.guide is None else self.guide.cost
+
+    @property
+    def dead(self):
+        """uint8 [B]: 1 where the guide knows the state to be a dead end (None without a guide)."""
+        return None if self.guide is None else self.guide.dead
+
+    @property
+    def shaped_reward(self):
+        """float64 [B]: the last step's reward plus the guide's potential term (None without a guide or its shaping)."""
+        return None if self.guide is None else self.guide.shaped
 
     def puzzle_stats(self):
         """The statistics per puzzle kept on the device (``episode_stats=True`` / ``curriculum=...``): a
@@ -457,6 +519,9 @@ class VecPushWorld:
         """
         if self.start_pool is not None:
             raise ValueError("rollout() is not available with a start_pool: the resets inside the launch draw nothing; use step()")
+        if self.guide is not None:
+            raise RuntimeError("rollout() is not available while a guide is set (set_guide): the steps inside the launch "
+                               "cannot be looked up; use step()")
         if self.stats is not None:
             raise RuntimeError("rollout() is not available while statistics per puzzle are kept (episode_stats / curriculum): "
                                "the steps inside the launch cannot be observed; use step()")
@@ -487,6 +552,9 @@ class VecPushWorld:
         actions are flagged 0xFF in ``terminated`` / ``truncated`` and counted (``counters()['bad_actions']``) as in ``step``."""
         if self.start_pool is not None:
             raise ValueError("mailbox() is not available with a start_pool: the resident kernel's resets draw nothing; use step()")
+        if self.guide is not None:
+            raise RuntimeError("mailbox() is not available while a guide is set (set_guide): the resident kernel's steps "
+                               "are not looked up; use step()")
         if self.stats is not None:
             raise RuntimeError("mailbox() is not available while statistics per puzzle are kept (episode_stats / curriculum): "
                                "the resident kernel's steps are not counted; use step()")
@@ -657,6 +725,8 @@ class VecPushWorld:
                               self.terminated, self.truncated, self.push_moves_taken, self.push_status, self.flags)
         if self._call_pool_draw is not None:
             self._call_pool_draw(self.start_seed)
+        if self._call_guide is not None:
+            self._call_guide()
         if self._call_stats is not None:
             self._call_stats()
         self._obs_current = False
@@ -724,6 +794,8 @@ class VecPushWorld:
                                    self.flags | (_capi.PUSH_END_STUCK if end_stuck else 0))
         if self._call_pool_draw is not None:
             self._call_pool_draw(self.start_seed)
+        if self._call_guide is not None:
+            self._call_guide()
         if self._call_stats is not None:
             self._call_stats()
         if self._call_pool_draw is not None:
@@ -898,6 +970,8 @@ class VecPushWorld:
         for table in tables:
             table.sample(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, cost=cost, mask=mask,
                          seed=self.table_seed, counter=self.table_draws, out=(self.start_row, self.start_cost))
+        if self.guide is not None:
+            self.guide.refresh(mask)
         self._obs_current = False
         if self.obs is not None:
             self._render()
@@ -1004,6 +1078,8 @@ class VecPushWorld:
         for table in tables:
             table.sample(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, cost=cost, mask=mask,
                          seed=self.table_seed, counter=self.table_draws, out=(self.start_row, self.start_cost))
+        if self.guide is not None:
+            self.guide.refresh(mask)
         self._obs_current = False
         if self.obs is not None:
             self._render()
@@ -1135,3 +1211,5 @@ class VecPushWorld:
         self.pos.copy_(torch.as_tensor(np.asarray(pos), dtype=torch.int8))
         self._has_reset = True
         self._obs_current = False
+        if self.guide is not None:
+            self.guide.refresh()

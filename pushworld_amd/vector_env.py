@@ -65,6 +65,8 @@ def _load_pool(puzzle_path, standard_padding: bool):
 
 
 class _VectorCore:
+    use_shaped_reward = False  # set_guide(..., use_shaped_reward=True): the returned reward is the guide's shaped one
+
     def __init__(self, puzzle_path, num_envs: int, max_steps: Optional[int], border_width: int, pixels_per_cell: int,
                  standard_padding: bool, observation: str, seed: int, sample_table, device: Optional[int],
                  to_numpy: bool, incremental: bool = True, curriculum=None, curriculum_update_every: Optional[int] = None,
@@ -145,6 +147,35 @@ class _VectorCore:
         if self.vec.start_pool is not None:
             info["start_entry"], info["start_level"] = self._out(self.vec.start_entry), self._out(self.vec.start_level)
         return info
+
+    def set_guide(self, tables_or_guide, use_shaped_reward: bool = False, **kw):
+        """``VecPushWorld.set_guide``: exact cost-to-go guidance kept current inside every step.  Make the
+        tables on this environment's own engine (``env.vec.solution_tables()`` and the like).  With a guide ``info`` (the
+        dm_env forms: ``TimeStep.observation``, a dict with the observation batch under ``"board"``) gains ``cost_to_go`` int32
+        [B] (-1 dead end, -2 unknown), ``guide_actions`` uint8 [B] (bits 0..3 optimal, 4..7 safe), ``dead_end`` uint8 [B] and
+        ``shaped_reward`` float64 [B]; ``use_shaped_reward`` returns the shaped reward as the step's reward.  None removes
+        the guide.  Returns the ``guide.ValueGuide``."""
+        if use_shaped_reward and (tables_or_guide is None or kw.get("shaping") is False):
+            raise ValueError("use_shaped_reward needs a guide with shaping")
+        guide = self.vec.set_guide(tables_or_guide, **kw)
+        if use_shaped_reward and guide.shaped is None:
+            self.vec.set_guide(None)
+            raise ValueError("use_shaped_reward needs a guide with shaping")
+        self.use_shaped_reward = bool(use_shaped_reward) and guide is not None
+        return guide
+
+    def _guide_info(self, info: dict) -> dict:
+        """With a guide: ``cost_to_go``, ``guide_actions``, ``dead_end``, ``shaped_reward``.  Without one ``info`` is as it was."""
+        g = self.vec.guide
+        if g is not None:
+            info["cost_to_go"], info["guide_actions"] = self._out(g.cost), self._out(g.acts)
+            info["dead_end"] = self._out(g.dead)
+            info["shaped_reward"] = None if g.shaped is None else self._out(g.shaped)
+        return info
+
+    def _reward(self, reward):
+        """The reward a step returns: the guide's shaped one when ``use_shaped_reward`` is on."""
+        return self.vec.guide.shaped if self.use_shaped_reward and self.vec.guide is not None else reward
 
     def _count_step(self) -> None:
         if self._steps_to_update is not None:
@@ -269,13 +300,15 @@ class PushWorldVectorEnv(_VectorCore):
     def _info(self) -> dict:
         """``puzzle_state``: int8 [B, NP, 2] (x, y) positions, agent first, zero beyond a puzzle's movables
         (the batched form of the reference's ``info["puzzle_state"]``, gym_env.py:186,226)."""
-        return self._start_info({"puzzle_id": self._out(self.vec.puzzle_id), "puzzle_state": self._out(self.vec.pos)})
+        return self._guide_info(self._start_info({"puzzle_id": self._out(self.vec.puzzle_id),
+                                                  "puzzle_state": self._out(self.vec.pos)}))
 
     def step_async(self, actions) -> None:
         self._launch(actions)
 
     def step_wait(self):
         obs, reward, terminated, truncated = self._collect()
+        reward = self._reward(reward)
         info = self._info()
         if self.to_numpy:
             return (obs.cpu().numpy(), reward.cpu().numpy(), terminated.cpu().numpy().astype(bool),
@@ -328,7 +361,9 @@ class PushWorldDmVectorEnv(_VectorCore):
         return self._observation_spec
 
     def _timestep(self, step_type, reward, discount, obs):
-        return _compat.TimeStep(self._out(step_type), self._out(reward), self._out(discount), self._out(obs))
+        # (with a guide the observation is a dict: the batch under "board" next to the guide's four entries)
+        observation = self._out(obs) if self.vec.guide is None else self._guide_info({"board": self._out(obs)})
+        return _compat.TimeStep(self._out(step_type), self._out(reward), self._out(discount), observation)
 
     def reset(self, seed: Optional[int] = None):
         self._pending = False
@@ -350,7 +385,7 @@ class PushWorldDmVectorEnv(_VectorCore):
                                 torch.where(done, int(_compat.StepType.LAST), int(_compat.StepType.MID))).to(torch.int32)
         discount = torch.where(done & ~first, 0.0, 1.0).to(torch.float64)
         self._was_done = done & ~first
-        return self._timestep(step_type, reward, discount, obs)
+        return self._timestep(step_type, self._reward(reward), discount, obs)
 
 
 # ---------------------------------------------------------------------------------------------------------- push mode
@@ -475,21 +510,23 @@ class PushWorldPushVectorEnv(_PushCore):
 
     def _info(self, moves, status) -> dict:
         v = self.vec
-        return self._start_info({"action_mask": self._out(self._action_mask()), "push_mask": self._out(v.push_view_mask),
+        info = self._start_info({"action_mask": self._out(self._action_mask()), "push_mask": self._out(v.push_view_mask),
                                  "num_pushes": self._out(v.push_view_count), "moves": self._out(moves),
                                  "status": self._out(status), "stuck": self._out((v.push_view_count == 0) & (v.terminated == 0)),
                                  "puzzle_id": self._out(v.puzzle_id), "puzzle_state": self._out(v.pos)})
+        return self._guide_info(info)
 
     def step_async(self, actions) -> None:
         self._launch(actions)
 
     def step_wait(self):
         s = self._collect()
+        reward = self._reward(s.reward)
         info = self._info(s.moves, s.status)
         if self.to_numpy:
-            return (s.obs.cpu().numpy(), s.reward.cpu().numpy(), s.terminated.cpu().numpy().astype(bool),
+            return (s.obs.cpu().numpy(), reward.cpu().numpy(), s.terminated.cpu().numpy().astype(bool),
                     s.truncated.cpu().numpy().astype(bool), info)
-        return s.obs, s.reward, s.terminated, s.truncated, info
+        return s.obs, reward, s.terminated, s.truncated, info
 
     def step(self, actions):
         """One macro step per environment -> ``(obs, reward f64[B], terminated, truncated, info)``."""
@@ -529,7 +566,7 @@ class PushWorldPushDmVectorEnv(_PushCore):
         return self._observation_spec
 
     def _timestep(self, step_type, reward, discount, obs):
-        observation = {"board": self._out(obs), "action_mask": self._out(self._action_mask())}
+        observation = self._guide_info({"board": self._out(obs), "action_mask": self._out(self._action_mask())})
         return _compat.TimeStep(self._out(step_type), self._out(reward), self._out(discount), observation)
 
     def reset(self, seed: Optional[int] = None):
@@ -555,4 +592,4 @@ class PushWorldPushDmVectorEnv(_PushCore):
         # (a reset clears the flags, but the stuck rule may set truncated again in the same call -- an initial state without a
         # push move: the next call resets that environment once more, so it is FIRST again)
         self._was_done = done
-        return self._timestep(step_type, s.reward, discount, s.obs)
+        return self._timestep(step_type, self._reward(s.reward), discount, s.obs)
