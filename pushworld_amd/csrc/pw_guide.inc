@@ -16,16 +16,8 @@
 #define PW_GUIDE_FLAGS (PW_GUIDE_AUTORESET | PW_GUIDE_END_DEAD | PW_GUIDE_REFRESH)
 
 struct GuideArgs {
-  // the fused lookup (pw_solve_batch_query_kernel's arguments), used when cost_in is NULL
-  const PwPuzzleHeader* hdrs;
-  const int32_t* item_of_puzzle;
-  const int64_t* row_off;
-  const int64_t* slot_off;
-  const uint8_t* slot_log2;
-  const unsigned long long* pool_key;
-  const uint16_t* pool_cost;
-  const uint8_t* pool_acts;
-  const uint32_t* pool_slots;
+  // the fused lookup, used when cost_in is NULL (num_puzzles is always set)
+  SolveBatchTables t;
   // the applied form
   int32_t* cost_in;
   uint8_t* acts_in;  // or NULL
@@ -36,7 +28,7 @@ struct GuideArgs {
   const uint8_t* term;
   uint8_t* trunc;
   const uint8_t* mask;   // or NULL
-  int32_t npad, n, num_puzzles;
+  int32_t npad, n;
   // the guide
   int32_t* cost;
   uint8_t* acts;
@@ -49,54 +41,6 @@ struct GuideArgs {
   unsigned long long* counters;  // the engine's pw_counters slots
   uint32_t flags;
 };
-
-// pw_solve_batch_query_kernel's answer for (pid, pos row): cost -2 / acts 0 also for an id outside the set and a puzzle without a
-// stored table
-__device__ __forceinline__ void guide_lookup(const GuideArgs& a, int64_t i, int32_t pid, int32_t& cost, uint32_t& acts) {
-  cost = -2;
-  acts = 0u;
-  if (pid < 0 || pid >= a.num_puzzles) return;
-  const int32_t item = a.item_of_puzzle[pid];
-  if (item < 0) return;
-  const PwPuzzleHeader* h = a.hdrs + pid;
-  const int N = h->N, W = h->W, H = h->H;
-  uint32_t P[4] = {0u, 0u, 0u, 0u};
-  const int8_t* row = a.pos + i * a.npad * 2;
-  if (a.npad >= 8) {
-    const uint4 v = *reinterpret_cast<const uint4*>(row);
-    P[0] = v.x, P[1] = v.y, P[2] = v.z, P[3] = v.w;
-  } else {
-    const uint2 v = *reinterpret_cast<const uint2*>(row);
-    P[0] = v.x, P[1] = v.y;
-  }
-  // the first N movables only: a pos row may hold anything beyond them.  Every coordinate in 0 .. 15 and inside W x H.
-  bool inside = N <= a.npad;
-#pragma unroll
-  for (int j = 0; j < 8; j++)
-    if (j < N) {
-      const uint32_t xy = (P[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-      const int x = static_cast<int8_t>(xy & 0xffu), y = static_cast<int8_t>(xy >> 8);
-      inside = inside && x >= 0 && x < W && x < 16 && y >= 0 && y < H && y < 16;
-    }
-  if (!inside) return;
-  // (the three per-item words are independent of each other: one level of the chain)
-  const int64_t base = a.row_off[item];
-  const uint32_t* slots = a.pool_slots + a.slot_off[item];
-  const uint32_t smask = (1u << a.slot_log2[item]) - 1u;
-  const uint64_t key = pw_bs_pack(P) & pw_sb_keep(N);
-  uint32_t sl = pw_bs_hash(key) & smask;
-  for (uint32_t walked = 0; walked <= smask; walked++) {
-    const uint32_t r = slots[sl];
-    if (r == PW_SB_NOROW) return;
-    if (a.pool_key[base + r] == key) {  // a hit is confirmed against the stored key
-      const uint32_t c = a.pool_cost[base + r];
-      cost = c == PW_SOLVE_INF ? -1 : static_cast<int32_t>(c);
-      acts = a.pool_acts[base + r];
-      return;
-    }
-    sl = (sl + 1u) & smask;
-  }
-}
 
 // reward + F, F = gamma * phi(c) - phi(c_prev), phi(x) = -(scale * x), a dead end worth `dc`; F = 0 when `flat`.  Every operation
 // is rounded on its own: contraction is switched off HERE -- hipcc contracts by default, and __dmul_rn / __dadd_rn are the plain
@@ -143,7 +87,11 @@ __global__ __launch_bounds__(PW_GUIDE_THREADS) void pw_guide_step_kernel(GuideAr
       a.cost_in[i] = -2;  // behind the read: the next call's queries start clean
       if (a.acts_in) a.acts_in[i] = 0;
     } else {
-      guide_lookup(a, i, p, c, acts);
+      // pw_solve_batch_query's answer: cost -2 / acts 0 also for an id outside the set and a puzzle without a stored table
+      int64_t base;
+      const int64_t row = pw_sb_lookup(a.t, p, a.pos + i * a.npad * 2, a.npad, base);
+      c = pw_sb_row_cost(a.t, base, row);
+      acts = pw_sb_row_acts(a.t, base, row);
     }
   }
   const bool refresh = (a.flags & PW_GUIDE_REFRESH) != 0u;
@@ -160,11 +108,11 @@ __global__ __launch_bounds__(PW_GUIDE_THREADS) void pw_guide_step_kernel(GuideAr
     if (m != 0ull && lane == 0)
       atomicAdd(a.counters + (blockIdx.x & (PW_COUNTER_SLOTS - 1)) * 8u + 1, static_cast<unsigned long long>(__popcll(m)));
     if (live && a.shaped) {
-      const int32_t dc = (p >= 0 && p < a.num_puzzles) ? a.dead_cost[p] : 0;
+      const int32_t dc = (p >= 0 && p < a.t.num_puzzles) ? a.dead_cost[p] : 0;
       a.shaped[i] = guide_shaped(a.reward[i], a.gamma, a.scale, c, c_prev, dc, fresh || refused || c == -2 || c_prev == -2);
     }
     if (a.counts) {
-      const bool counted = live && p >= 0 && p < a.num_puzzles && !fresh && !refused;
+      const bool counted = live && p >= 0 && p < a.t.num_puzzles && !fresh && !refused;
       const bool guided = counted && c != -2 && c_prev != -2;
       // the counted lanes of a wavefront share a puzzle (bound batches are contiguous per puzzle): one add per column
       const unsigned long long cm = __ballot(counted);
@@ -218,17 +166,8 @@ int pw_guide_step(PwEngine* e, PwSolveBatch* tables, int32_t* cost_in, uint8_t* 
   if (n == 0) return PW_OK;
   PwDeviceGuard guard(e->set->device);
   GuideArgs a{};
-  if (tables) {
-    a.hdrs = e->set->d_headers;
-    a.item_of_puzzle = tables->d_item_of_puzzle;
-    a.row_off = tables->d_row_off;
-    a.slot_off = tables->d_slot_off;
-    a.slot_log2 = tables->d_slot_log2;
-    a.pool_key = tables->d_key;
-    a.pool_cost = tables->d_cost;
-    a.pool_acts = tables->d_acts;
-    a.pool_slots = tables->d_slots;
-  }
+  if (tables) a.t = solve_batch_tables(tables);
+  a.t.num_puzzles = e->set->count;  // (also without tables: the range test of the counts)
   a.cost_in = cost_in;
   a.acts_in = acts_in;
   a.puzzle_id = puzzle_id;
@@ -239,7 +178,6 @@ int pw_guide_step(PwEngine* e, PwSolveBatch* tables, int32_t* cost_in, uint8_t* 
   a.mask = mask;
   a.npad = npad;
   a.n = n;
-  a.num_puzzles = e->set->count;
   a.cost = cost;
   a.acts = acts;
   a.seen = seen;

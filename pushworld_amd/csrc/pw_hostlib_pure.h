@@ -16,6 +16,26 @@ inline uint64_t pw_table_slots(uint64_t max_states) {
   return slots;
 }
 
+// The ladder of a batched search's closed set (csrc/pw_batch_set.inc): the set starts with `lds_slots` slots in LDS and climbs
+// tables of 2^16, 2^20, 2^22 ... slots in the workgroup's slab, laid out from byte offset `off`, until one holds 2 * max_states
+// (max_states <= 2^28).  Entries beyond the last level are 0.  Returns the offset behind the last table.
+inline uint64_t pw_bs_ladder(uint64_t max_states, uint32_t lds_slots, uint32_t bytes_per_slot, uint64_t off,
+                             uint32_t (&level_slots)[6], uint64_t (&level_off)[6]) {
+  const uint32_t ladder[6] = {1u << 16, 1u << 20, 1u << 22, 1u << 24, 1u << 26, 1u << 29};
+  for (int k = 0; k < 6; k++) {
+    level_slots[k] = 0u;
+    level_off[k] = 0;
+  }
+  uint64_t have = lds_slots;
+  for (int k = 0; k < 6 && have < 2ull * max_states; k++) {
+    level_slots[k] = ladder[k];
+    level_off[k] = off;
+    off += static_cast<uint64_t>(ladder[k]) * bytes_per_slot;
+    have = ladder[k];
+  }
+  return off;
+}
+
 // a time limit in seconds as wall-clock ticks of a kernel: 0 = no limit, at least 1 otherwise, ~0 where the product leaves
 // 64 bits (+inf included)
 inline unsigned long long pw_deadline_ticks(double time_limit, uint32_t clock_khz) {

@@ -451,6 +451,7 @@ struct PageRec {
 #include "pw_engine.inc"
 #include "pw_cells.inc"
 #include "pw_mailbox.inc"
+#include "pw_batch_set.inc"
 #include "pw_search.inc"
 #include "pw_solution.inc"
 #include "pw_solution_batch.inc"

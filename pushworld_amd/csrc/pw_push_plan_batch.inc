@@ -189,28 +189,13 @@ __global__ __launch_bounds__(64) void pw_push_plan_batch_kernel(PpbArgs a) {
     const RgdEvalArgs& ra = it.rgd;
     const int pid = it.pid;
     const PwPuzzleHeader* h = a.hdrs + pid;
-    const int N = h->N, G = h->G, W = h->W, H = h->H;
-    StepArgs sa;
-    sa.hdrs = a.hdrs;
-    sa.blob = a.blob;
-    sa.ovl = a.ovl;
-    sa.ovl_dir = a.ovl_dir;
+    const int N = h->N, W = h->W, H = h->H;
     LanePuzzleT<const uint64_t*, 2> p;
     uint32_t OT[8];
-    lane_puzzle<8>(sa, pid, p, OT);
-    uint32_t P0[4] = {0u, 0u, 0u, 0u};
-    if (srow) {
-      if (a.npad >= 8) {
-        const uint4 v = *reinterpret_cast<const uint4*>(srow);
-        P0[0] = v.x, P0[1] = v.y, P0[2] = v.z, P0[3] = v.w;
-      } else {
-        const uint2 v = *reinterpret_cast<const uint2*>(srow);
-        P0[0] = v.x, P0[1] = v.y;
-      }
-    } else {
-#pragma unroll
-      for (int w = 0; w < 4; w++) P0[w] = reinterpret_cast<const uint32_t*>(h->init)[w];
-    }
+    pw_bs_puzzle(a.hdrs, a.blob, a.ovl, a.ovl_dir, pid, p, OT);
+    uint32_t P0[4];
+    if (srow) pw_bs_load_row(srow, a.npad, P0);
+    else pw_bs_load_init(h, P0);
 #pragma unroll
     for (int j = 0; j < 8; j++)  // only the first N movables count
       if (j >= N) P0[j >> 1] &= (j & 1) ? 0x0000ffffu : 0u;
@@ -225,14 +210,8 @@ __global__ __launch_bounds__(64) void pw_push_plan_batch_kernel(PpbArgs a) {
     const unsigned long long t0 = wall_clock64();
     const uint32_t tag = tag_base + static_cast<uint32_t>(item);
     const uint64_t keep = pw_sb_keep(N);
-    uint64_t gkey = 0, gmask = 0;
-#pragma unroll
-    for (int j = 1; j < 8; j++)
-      if (j <= G) {
-        const uint32_t g = reinterpret_cast<const uint16_t*>(h->goal)[j - 1];
-        gkey |= static_cast<uint64_t>((g & 0xfu) | ((g >> 4) & 0xf0u)) << (8 * j);
-        gmask |= 0xffull << (8 * j);
-      }
+    uint64_t gkey, gmask;
+    pw_bs_goal_word(h, gkey, gmask);
     // ---- begin: the start's canon and region (every lane floods the same state into its own boards), the empty queue -------
     for (uint32_t w = lane; w < a.n0; w += PW_WAVE) bits0[w] = 0ull;
     for (uint32_t w = lane; w < a.n1; w += PW_WAVE) bits1[w] = 0ull;

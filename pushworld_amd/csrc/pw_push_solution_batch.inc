@@ -1,6 +1,8 @@
 // pw_push_solution_batch.inc -- cost-to-go tables OVER PUSHES of MANY small puzzles in one launch (DESIGN.md K22).
-// Included from pw_kernels.hip after pw_push_table.inc and pw_solution_batch.inc (uses pw_search.inc's pw_bs_* state words,
-// pw_solution_batch.inc's pw_bs_insert_slot / pw_bs_find / pw_sb_keep / PW_SB_* and the table-only lane step).
+// Included from pw_kernels.hip after pw_push_table.inc and pw_solution_batch.inc (uses pw_batch_set.inc's state words and
+// pw_solution_batch.inc's PW_SB_* statuses and the table-only lane step).  The SEARCH kernel below keeps its own closed-set
+// code, the text PwBatchSet was written from: built on the shared helpers it measured about 1 % slower and the cause was not
+// found (profiles/batch_closed_set.txt).  The query kernel and the host half use pw_batch_set.inc and pw_bs_ladder.
 //
 // pw_push_search_solve (K18) gives ONE puzzle its table with a handle, a launch sequence per layer and a flood launch per
 // query: at the sizes of the Level-0 pool it is bound by launches.  pw_push_solve_batch is K18 in the frame of K13: persistent
@@ -659,23 +661,11 @@ __global__ __launch_bounds__(256) void pw_push_solve_batch_query_kernel(PushSolv
   uint16_t* const b = s_boards + threadIdx.x;
   const PwPuzzleHeader* h = a.hdrs + pid;
   const int N = h->N, W = h->W, H = h->H;  // (a stored table: N <= 8, W, H <= 16, overlap tables present)
-  StepArgs sa;
-  sa.hdrs = a.hdrs;
-  sa.blob = a.blob;
-  sa.ovl = a.ovl;
-  sa.ovl_dir = a.ovl_dir;
   LanePuzzleT<const uint64_t*, 2> p;
   uint32_t OT[8];
-  lane_puzzle<8>(sa, pid, p, OT);
-  uint32_t P[4] = {0u, 0u, 0u, 0u};
-  const int8_t* row = a.pos + i * a.npad * 2;
-  if (a.npad >= 8) {
-    const uint4 v = *reinterpret_cast<const uint4*>(row);
-    P[0] = v.x, P[1] = v.y, P[2] = v.z, P[3] = v.w;
-  } else {
-    const uint2 v = *reinterpret_cast<const uint2*>(row);
-    P[0] = v.x, P[1] = v.y;
-  }
+  pw_bs_puzzle(a.hdrs, a.blob, a.ovl, a.ovl_dir, pid, p, OT);
+  uint32_t P[4];
+  pw_bs_load_row(a.pos + i * a.npad * 2, a.npad, P);
   const bool want_walk = a.out_walk != nullptr || a.out_action != nullptr;
   // the first N movables only: a pos row may hold anything beyond them
   const bool inside = N <= a.npad && pw_psb_in_grid(P, OT, N, W, H);
@@ -685,18 +675,7 @@ __global__ __launch_bounds__(256) void pw_push_solve_batch_query_kernel(PushSolv
   if (inside) {
     const uint32_t canon = want_walk ? pw_psb_region_layers<true>(p, h, OT, P, x0, y0, b) : pw_psb_region_layers<false>(p, h, OT, P, x0, y0, b);
     const uint64_t key = ((pw_bs_pack(P) & pw_sb_keep(N)) & ~0xffull) | canon;
-    const uint32_t* slots = a.pool_slots + a.slot_off[item];
-    const uint32_t smask = (1u << a.slot_log2[item]) - 1u;
-    uint32_t sl = pw_bs_hash(key) & smask;
-    for (uint32_t walked = 0; walked <= smask; walked++) {
-      const uint32_t r = slots[sl];
-      if (r == PW_SB_NOROW) break;
-      if (a.pool_key[sbase + r] == key) {  // a hit is confirmed against the stored key
-        idx = r;
-        break;
-      }
-      sl = (sl + 1u) & smask;
-    }
+    idx = pw_sb_probe(a.pool_slots + a.slot_off[item], (1u << a.slot_log2[item]) - 1u, a.pool_key + sbase, key);
   }
   int32_t cost = -2, walk = -1, act = -1;
   uint32_t fxy = 0, pact = 0xFFu;
@@ -941,22 +920,8 @@ int pw_push_solve_batch_run(PwPushSolveBatch* b, const int32_t* puzzles, const i
   off += pw_pad256(mr * 8);
   a.rmeta_off = off;
   off += pw_pad256(mr * 4);
-  const uint32_t ladder[6] = {1u << 16, 1u << 20, 1u << 22, 1u << 24, 1u << 26, 1u << 29};
-  int lv = 0;
-  for (int k = 0; k < 6; k++) {
-    a.level_slots[k] = 0u;
-    a.level_off[k] = 0;
-  }
-  uint64_t have = PW_PSB_LDS_SLOTS;
-  // (the inserts in flight when the store fills: at most one per lane beyond max_states)
-  for (int k = 0; k < 6 && have < 2ull * ms + 512ull; k++) {
-    a.level_slots[lv] = ladder[k];
-    a.level_off[lv] = off;
-    off += static_cast<uint64_t>(ladder[k]) * 12;
-    have = ladder[k];
-    lv++;
-  }
-  a.slab_bytes = pw_pad256(off);
+  // (+ 256: the inserts in flight when the store fills, at most one per lane beyond max_states)
+  a.slab_bytes = pw_pad256(pw_bs_ladder(ms + 256ull, PW_PSB_LDS_SLOTS, 12, off, a.level_slots, a.level_off));
   // persistent workgroups by pw_search_batch's rule; the slabs are the engine's, shared with pw_search_batch
   int64_t groups = 0;
   if (int rc = engine_search_slab(e, n, a.slab_bytes, st, "pw_push_solve_batch_run", &groups, &a.slab, &a.next)) return rc;

@@ -1302,7 +1302,6 @@ int pw_search_plan(PwSearch* s, int64_t index, uint8_t* actions, int32_t cap, vo
 // exhausted), 2 unknown (more than max_states states), 3 not searched (puzzle beyond 16 x 16 / 8 movables, or without
 // overlap tables).  Same answers as the layer-synchronous pw_search_* with novelty width 0 (tests/test_gpu_search.py).
 // ------------------------------------------------------------------------------------
-#define PW_BS_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define PW_BS_LDS_SLOTS 4096u
 
 struct BatchSearchArgs {
@@ -1327,41 +1326,6 @@ struct BatchSearchArgs {
   uint64_t link_off;       // with plans: byte offset of the (parent << 2 | action) word of every stored state in the slab
 };
 
-__device__ __forceinline__ uint64_t pw_bs_pack(const uint32_t (&P)[4]) {
-  uint64_t k = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    const uint32_t v = P[w];
-    const uint32_t r = (v & 0xfu) | ((v >> 4) & 0xf0u) | ((v >> 8) & 0xf00u) | ((v >> 12) & 0xf000u);
-    k |= static_cast<uint64_t>(r) << (16 * w);
-  }
-  return k;
-}
-__device__ __forceinline__ void pw_bs_unpack(uint64_t k, uint32_t (&P)[4]) {
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    const uint32_t r = static_cast<uint32_t>(k >> (16 * w)) & 0xffffu;
-    P[w] = (r & 0xfu) | ((r & 0xf0u) << 4) | ((r & 0xf00u) << 8) | ((r & 0xf000u) << 12);
-  }
-}
-__device__ __forceinline__ uint32_t pw_bs_hash(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  return static_cast<uint32_t>(k ^ (k >> 33));
-}
-// true when `key` was not in the table (it is now); the table never fills beyond half (see the growth rule)
-__device__ __forceinline__ bool pw_bs_insert(unsigned long long* tab, uint32_t mask, uint64_t key) {
-  uint32_t slot = pw_bs_hash(key) & mask;
-  for (;;) {
-    const unsigned long long old = atomicCAS(tab + slot, PW_BS_EMPTY, static_cast<unsigned long long>(key));
-    if (old == PW_BS_EMPTY) return true;
-    if (old == key) return false;
-    slot = (slot + 1u) & mask;
-  }
-}
-
 __global__ __launch_bounds__(256) void pw_search_batch_kernel(BatchSearchArgs a) {
   __shared__ unsigned long long s_tab[PW_BS_LDS_SLOTS];
   __shared__ uint32_t s_total, s_found, s_overflow, s_goal_idx;
@@ -1370,16 +1334,12 @@ __global__ __launch_bounds__(256) void pw_search_batch_kernel(BatchSearchArgs a)
   unsigned long long* store = reinterpret_cast<unsigned long long*>(a.slab + static_cast<uint64_t>(blockIdx.x) * a.slab_bytes);
   uint32_t* link = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(store) + a.link_off);  // (only with a.plans)
   for (;;) {
-    __syncthreads();  // (the previous puzzle's shared state is no longer read)
-    if (tid == 0) s_item = static_cast<int32_t>(atomicAdd(a.next, 1u));
-    __syncthreads();
-    const int item = s_item;
+    const int item = pw_bs_next_item(a.next, &s_item);
     if (item >= a.n) return;
     const int pid = pw_clamp_pid(a.puzzles ? a.puzzles[item] : item, a.num_puzzles);
     const PwPuzzleHeader* h = a.hdrs + pid;
-    const int N = h->N, G = h->G;
-    const uint4 dirw = *reinterpret_cast<const uint4*>(a.ovl_dir + pid);
-    if (N < 1 || N > 8 || h->W > 16 || h->H > 16 || dirw.x == 0u) {  // not this kernel's puzzle: the caller searches it alone
+    const int G = h->G;
+    if (!pw_bs_fits(h, a.ovl_dir, pid)) {  // not this kernel's puzzle: the caller searches it alone
       if (tid == 0) {
         a.verdict[item] = 3;
         a.plan_len[item] = -1;
@@ -1387,20 +1347,14 @@ __global__ __launch_bounds__(256) void pw_search_batch_kernel(BatchSearchArgs a)
       }
       continue;
     }
-    // the puzzle as the table-only lane step sees it
-    StepArgs sa;
-    sa.hdrs = a.hdrs;
-    sa.blob = a.blob;
-    sa.ovl = a.ovl;
-    sa.ovl_dir = a.ovl_dir;
     LanePuzzleT<const uint64_t*, 2> p;
     uint32_t OT[8];
-    lane_puzzle<8>(sa, pid, p, OT);
+    pw_bs_puzzle(a.hdrs, a.blob, a.ovl, a.ovl_dir, pid, p, OT);
 
-    for (uint32_t i = tid; i < PW_BS_LDS_SLOTS; i += 256u) s_tab[i] = PW_BS_EMPTY;
+    PwBatchSet<false> set;
+    set.start(s_tab, nullptr, PW_BS_LDS_SLOTS);
     uint32_t P0[4];
-#pragma unroll
-    for (int w = 0; w < 4; w++) P0[w] = reinterpret_cast<const uint32_t*>(h->init)[w];
+    pw_bs_load_init(h, P0);
     const uint64_t k0 = pw_bs_pack(P0);
     int at_goal = 0;
 #pragma unroll
@@ -1414,69 +1368,38 @@ __global__ __launch_bounds__(256) void pw_search_batch_kernel(BatchSearchArgs a)
       store[0] = k0;
     }
     __syncthreads();
-    if (tid == 0) (void)pw_bs_insert(s_tab, PW_BS_LDS_SLOTS - 1u, k0);
+    if (tid == 0) set.put(k0, 0u);
     int verdict = -1, plan_len = -1;
     if (at_goal == G) {  // the start state is a goal state (vacuously without goals): the empty plan
       verdict = 1;
       plan_len = 0;
     }
-    unsigned long long* tab = s_tab;
-    uint32_t cap = PW_BS_LDS_SLOTS, begin = 0u, end = 1u, depth = 0u;
-    int level = 0;
+    uint32_t begin = 0u, end = 1u, depth = 0u;
     while (verdict < 0) {
       __syncthreads();
       // (workgroup-uniform: `end` was read from s_total between two barriers; re-reading s_total here would race with the
       //  atomicAdd of a wavefront that is already expanding)
       const uint32_t total = end, L = end - begin;
-      // growth: everything this layer can add must fit at half load
-      const uint64_t need = min(static_cast<uint64_t>(total) + 4ull * L, static_cast<uint64_t>(a.max_states));
-      bool grown = false;
-      while (static_cast<uint64_t>(cap) < 2ull * need) {
-        if (level >= 6 || a.level_slots[level] == 0u) break;  // (the top level holds 2 * max_states by construction)
-        cap = a.level_slots[level];
-        tab = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(store) + a.level_off[level]);
-        level++;
-        grown = true;
-      }
-      if (grown) {
-        for (uint32_t i = tid; i < cap; i += 256u) tab[i] = PW_BS_EMPTY;
-        __threadfence();
-        __syncthreads();
-        for (uint32_t i = tid; i < total; i += 256u) (void)pw_bs_insert(tab, cap - 1u, store[i]);
-        __syncthreads();
-      }
-      const uint32_t mask = cap - 1u;
+      // everything this layer can add must fit at half load
+      if (set.grow(min(static_cast<uint64_t>(total) + 4ull * L, static_cast<uint64_t>(a.max_states)), a.level_slots, a.level_off,
+                   reinterpret_cast<uint8_t*>(store), store, total))
+        __syncthreads();  // (uniform) the rehash is complete
       for (uint32_t i = begin + tid; i < end; i += 256u) {
-        const uint64_t key = store[i];
         uint32_t PP[4];
-        pw_bs_unpack(key, PP);
+        pw_bs_unpack(store[i], PP);
 #pragma unroll 1
         for (int act = 0; act < 4; act++) {
           LaneEnv<8> s;
-#pragma unroll
-          for (int w = 0; w < 4; w++) s.P[w] = PP[w];
-          s.steps = 0;
-          s.term = 0;
-          s.trunc = 0;
-          s.reward = 0.0;
-          s.dgoals = 0;
+          pw_bs_fresh_env(PP, s);
           if (!lane_step<8>(p, h, OT, s, act, 0u, -1)) continue;  // nothing moved: the parent itself
-          const uint64_t k2 = pw_bs_pack(s.P);
           // a goal state decides the search whether or not the store still has room for it (one seen in an earlier layer would
           // have ended the search there, so this is a new one)
           if (s.term == 1) atomicMin(&s_found, depth + 1u);
-          // (once the store is full nothing more goes into the table: it has room for max_states + the inserts in flight)
-          if (*reinterpret_cast<volatile uint32_t*>(&s_overflow)) continue;
-          if (!pw_bs_insert(tab, mask, k2)) continue;
-          const uint32_t idx = atomicAdd(&s_total, 1u);
-          if (idx < a.max_states) {
-            store[idx] = k2;
-            if (a.plans) {
-              link[idx] = (i << 2) | static_cast<uint32_t>(act);
-              if (s.term == 1) atomicMin(&s_goal_idx, idx);
-            }
-          } else {
-            s_overflow = 1u;
+          uint32_t idx;
+          if (!set.claim(pw_bs_pack(s.P), store, a.max_states, &s_total, &s_overflow, idx)) continue;
+          if (a.plans) {
+            link[idx] = (i << 2) | static_cast<uint32_t>(act);
+            if (s.term == 1) atomicMin(&s_goal_idx, idx);
           }
         }
       }
@@ -1540,21 +1463,7 @@ extern "C" int pw_search_batch(PwEngine* e, const int32_t* puzzles, int32_t n, i
   a.plan_cap = plan_cap;
   a.link_off = off;
   if (plans) off += pw_pad256(static_cast<uint64_t>(max_states_each) * 4);
-  const uint32_t ladder[6] = {1u << 16, 1u << 20, 1u << 22, 1u << 24, 1u << 26, 1u << 29};
-  int lv = 0;
-  for (int k = 0; k < 6; k++) {
-    a.level_slots[k] = 0u;
-    a.level_off[k] = 0;
-  }
-  uint64_t have = PW_BS_LDS_SLOTS;
-  for (int k = 0; k < 6 && have < 2ull * static_cast<uint64_t>(max_states_each); k++) {
-    a.level_slots[lv] = ladder[k];
-    a.level_off[lv] = off;
-    off += static_cast<uint64_t>(ladder[k]) * 8;
-    have = ladder[k];
-    lv++;
-  }
-  a.slab_bytes = off;
+  a.slab_bytes = pw_bs_ladder(static_cast<uint64_t>(max_states_each), PW_BS_LDS_SLOTS, 8, off, a.level_slots, a.level_off);
   int64_t groups = 0;
   if (int rc = engine_search_slab(e, n, a.slab_bytes, st, "pw_search_batch", &groups, &a.slab, &a.next)) return rc;
   a.verdict = verdict;

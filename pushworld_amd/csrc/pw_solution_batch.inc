@@ -1,12 +1,13 @@
 // pw_solution_batch.inc -- exact cost-to-go tables of MANY small puzzles in one launch (DESIGN.md K13).
-// Included from pw_kernels.hip after pw_solution.inc (uses pw_search.inc's pw_bs_* state words and the table-only lane step).
+// Included from pw_kernels.hip after pw_solution.inc (uses pw_batch_set.inc's state words, closed set, slot table
+// and lookup, and the table-only lane step).
 //
 // pw_search_solve (K12) gives ONE puzzle its table with a launch per pass and per sweep: at the sizes of the Level-0 pool it
 // is launch bound.  pw_solve_batch is the backward half in the form of pw_search_batch (K5b): persistent workgroups of 256
 // take puzzles off a device counter and do everything for a puzzle inside the kernel --
-//   1. the exhaustive breadth-first search of pw_search_batch_kernel (one 64-bit word per state, closed set in LDS that
-//      moves up the 2^16 / 2^20 / ... ladder of the workgroup's slab, "grow before the layer"), which does NOT stop at a
-//      goal state; every slot of the closed set also holds the store index of its state (a uint32 next to the table);
+//   1. an exhaustive breadth-first search over PwBatchSet<true> (one 64-bit word per state, closed set in LDS that moves up
+//      the 2^16 / 2^20 / ... ladder of the workgroup's slab, "grow before the layer"), which does NOT stop at a goal state;
+//      every slot of the closed set also holds the store index of its state (a uint32 next to the table);
 //   2. the successor pass: the lane step again for every state and action, looked up (read only) in the closed set;
 //   3. backward sweeps over succ and a uint16 cost array: sweep k settles every unsettled state with a successor of cost
 //      k - 1; a barrier between sweeps instead of K12's launch, a workgroup flag in LDS ends them;
@@ -16,7 +17,6 @@
 // numbering of the states inside a breadth-first layer.  No result depends on either: rows are found by state.
 // pw_solve_batch_query maps live states of a mixed batch to rows in one capturable launch.
 
-#define PW_SB_NOROW 0xFFFFFFFFu
 #define PW_SB_BUILT 0
 #define PW_SB_TOO_MANY 2
 #define PW_SB_NOT_SEARCHED 3
@@ -55,32 +55,6 @@ struct SolveBatchArgs {
   uint32_t* pool_slots;
 };
 
-// the bits of a state word that belong to the first n movables (8 per movable)
-__host__ __device__ __forceinline__ uint64_t pw_sb_keep(int n) { return n >= 8 ? ~0ull : ((1ull << (8 * n)) - 1ull); }
-
-// pw_bs_insert that also says where: true when `key` was not in the table (it is now, in `slot`); else `slot` holds it
-__device__ __forceinline__ bool pw_bs_insert_slot(unsigned long long* tab, uint32_t mask, uint64_t key, uint32_t& slot) {
-  slot = pw_bs_hash(key) & mask;
-  for (;;) {
-    const unsigned long long old = atomicCAS(tab + slot, PW_BS_EMPTY, static_cast<unsigned long long>(key));
-    if (old == PW_BS_EMPTY) return true;
-    if (old == key) return false;
-    slot = (slot + 1u) & mask;
-  }
-}
-
-// read only: the store index of `key`, PW_SB_NOROW when the table does not hold it (the table is at most half full)
-__device__ __forceinline__ uint32_t pw_bs_find(const unsigned long long* tab, const uint32_t* tidx, uint32_t mask, uint64_t key) {
-  uint32_t slot = pw_bs_hash(key) & mask;
-  for (uint32_t walked = 0; walked <= mask; walked++) {
-    const unsigned long long v = tab[slot];
-    if (v == key) return tidx[slot];
-    if (v == PW_BS_EMPTY) return PW_SB_NOROW;
-    slot = (slot + 1u) & mask;
-  }
-  return PW_SB_NOROW;
-}
-
 __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
   __shared__ unsigned long long s_tab[PW_BS_LDS_SLOTS];
   __shared__ uint32_t s_idx[PW_BS_LDS_SLOTS];
@@ -93,46 +67,29 @@ __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
   int32_t* succ = reinterpret_cast<int32_t*>(slab + a.succ_off);
   uint16_t* cost = reinterpret_cast<uint16_t*>(slab + a.cost_off);
   for (;;) {
-    __syncthreads();  // (the previous puzzle's shared state is no longer read)
-    if (tid == 0) s_item = static_cast<int32_t>(atomicAdd(a.next, 1u));
-    __syncthreads();
-    const int item = s_item;
+    const int item = pw_bs_next_item(a.next, &s_item);
     if (item >= a.n) return;
     const int pid = pw_clamp_pid(a.puzzles ? a.puzzles[item] : item, a.num_puzzles);
     const PwPuzzleHeader* h = a.hdrs + pid;
-    const int N = h->N, G = h->G;
-    const uint4 dirw = *reinterpret_cast<const uint4*>(a.ovl_dir + pid);
+    const int N = h->N;
     int status = -1;
-    if (N < 1 || N > 8 || h->W > 16 || h->H > 16 || dirw.x == 0u) status = PW_SB_NOT_SEARCHED;  // the caller's pw_search_solve
+    if (!pw_bs_fits(h, a.ovl_dir, pid)) status = PW_SB_NOT_SEARCHED;  // the caller's pw_search_solve
     uint32_t total = 0, max_cost = 0;
     if (status < 0) {
-      // the puzzle as the table-only lane step sees it
-      StepArgs sa;
-      sa.hdrs = a.hdrs;
-      sa.blob = a.blob;
-      sa.ovl = a.ovl;
-      sa.ovl_dir = a.ovl_dir;
       LanePuzzleT<const uint64_t*, 2> p;
       uint32_t OT[8];
-      lane_puzzle<8>(sa, pid, p, OT);
+      pw_bs_puzzle(a.hdrs, a.blob, a.ovl, a.ovl_dir, pid, p, OT);
 
-      for (uint32_t i = tid; i < PW_BS_LDS_SLOTS; i += 256u) s_tab[i] = PW_BS_EMPTY;
+      PwBatchSet<true> set;
+      set.start(s_tab, s_idx, PW_BS_LDS_SLOTS);
       // A state word holds the first N movables and zeros beyond: whatever the 16-byte init row holds there stays out of the
       // key (the lane step never touches a movable beyond N, so the zeros stay; pw_solve_batch_query packs the same way).
       const uint64_t keep = pw_sb_keep(N);
       uint32_t P0[4];
-#pragma unroll
-      for (int w = 0; w < 4; w++) P0[w] = reinterpret_cast<const uint32_t*>(h->init)[w];
+      pw_bs_load_init(h, P0);
       const uint64_t k0 = pw_bs_pack(P0) & keep;
-      // goal test on the word: movable j = 1 .. G on goal j - 1 (every state without goals)
-      uint64_t gkey = 0, gmask = 0;
-#pragma unroll
-      for (int j = 1; j < 8; j++)
-        if (j <= G) {
-          const uint32_t g = reinterpret_cast<const uint16_t*>(h->goal)[j - 1];
-          gkey |= static_cast<uint64_t>((g & 0xfu) | ((g >> 4) & 0xf0u)) << (8 * j);
-          gmask |= 0xffull << (8 * j);
-        }
+      uint64_t gkey, gmask;
+      pw_bs_goal_word(h, gkey, gmask);
       if (tid == 0) {
         s_total = 1u;
         s_overflow = 0u;
@@ -143,68 +100,27 @@ __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
         store[0] = k0;
       }
       __syncthreads();
-      if (tid == 0) {
-        uint32_t sl;
-        (void)pw_bs_insert_slot(s_tab, PW_BS_LDS_SLOTS - 1u, k0, sl);
-        s_idx[sl] = 0u;
-      }
-      unsigned long long* tab = s_tab;
-      uint32_t* tidx = s_idx;
-      uint32_t cap = PW_BS_LDS_SLOTS, begin = 0u, end = 1u;
-      int level = 0;
-      // ---- 1. the whole reachable space (pw_search_batch_kernel's loop; goal states are expanded like any other)
+      if (tid == 0) set.put(k0, 0u);
+      uint32_t begin = 0u, end = 1u;
+      // ---- 1. the whole reachable space (goal states are expanded like any other)
       for (;;) {
         __syncthreads();
-        const uint32_t cur = end, L = end - begin;  // (workgroup-uniform: see pw_search_batch_kernel)
-        // growth: everything this layer can add must fit at half load
-        const uint64_t need = min(static_cast<uint64_t>(cur) + 4ull * L, static_cast<uint64_t>(a.max_states));
-        bool grown = false;
-        while (static_cast<uint64_t>(cap) < 2ull * need) {
-          if (level >= 6 || a.level_slots[level] == 0u) break;  // (the top level holds 2 * max_states by construction)
-          cap = a.level_slots[level];
-          tab = reinterpret_cast<unsigned long long*>(slab + a.level_off[level]);
-          tidx = reinterpret_cast<uint32_t*>(tab + cap);
-          level++;
-          grown = true;
-        }
-        if (grown) {
-          for (uint32_t i = tid; i < cap; i += 256u) tab[i] = PW_BS_EMPTY;
-          __threadfence();
-          __syncthreads();
-          for (uint32_t i = tid; i < cur; i += 256u) {
-            uint32_t sl;
-            (void)pw_bs_insert_slot(tab, cap - 1u, store[i], sl);
-            tidx[sl] = i;
-          }
-          __syncthreads();
-        }
-        const uint32_t mask = cap - 1u;
+        // (workgroup-uniform: `end` was read from s_total between two barriers, as in pw_search_batch_kernel)
+        const uint32_t cur = end, L = end - begin;
+        // everything this layer can add must fit at half load
+        if (set.grow(min(static_cast<uint64_t>(cur) + 4ull * L, static_cast<uint64_t>(a.max_states)), a.level_slots, a.level_off,
+                     slab, store, cur))
+          __syncthreads();  // (uniform) the rehash is complete
         for (uint32_t i = begin + tid; i < end; i += 256u) {
           uint32_t PP[4];
           pw_bs_unpack(store[i], PP);
 #pragma unroll 1
           for (int act = 0; act < 4; act++) {
             LaneEnv<8> s;
-#pragma unroll
-            for (int w = 0; w < 4; w++) s.P[w] = PP[w];
-            s.steps = 0;
-            s.term = 0;
-            s.trunc = 0;
-            s.reward = 0.0;
-            s.dgoals = 0;
+            pw_bs_fresh_env(PP, s);
             if (!lane_step<8>(p, h, OT, s, act, 0u, -1)) continue;  // nothing moved: the parent itself
-            const uint64_t k2 = pw_bs_pack(s.P) & keep;
-            // (once the store is full nothing more goes into the table: it has room for max_states + the inserts in flight)
-            if (*reinterpret_cast<volatile uint32_t*>(&s_overflow)) continue;
-            uint32_t sl;
-            if (!pw_bs_insert_slot(tab, mask, k2, sl)) continue;
-            const uint32_t idx = atomicAdd(&s_total, 1u);
-            if (idx < a.max_states) {
-              store[idx] = k2;
-              tidx[sl] = idx;  // (read only after the barrier below)
-            } else {
-              s_overflow = 1u;
-            }
+            uint32_t idx;
+            (void)set.claim(pw_bs_pack(s.P) & keep, store, a.max_states, &s_total, &s_overflow, idx);
           }
         }
         __threadfence();
@@ -220,7 +136,6 @@ __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
       total = min(status == PW_SB_TOO_MANY ? s_total : end, a.max_states);
       if (status < 0) {
         // ---- 2. successors (local indices) and the costs' starting values
-        const uint32_t mask = cap - 1u;
         for (uint32_t i0 = 0; i0 < total; i0 += 256u) {  // (whole rounds: the ballot below needs every lane)
           const uint32_t i = i0 + tid;
           bool goal = false;
@@ -232,15 +147,9 @@ __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
 #pragma unroll 1
             for (int act = 0; act < 4; act++) {
               LaneEnv<8> s;
-#pragma unroll
-              for (int w = 0; w < 4; w++) s.P[w] = PP[w];
-              s.steps = 0;
-              s.term = 0;
-              s.trunc = 0;
-              s.reward = 0.0;
-              s.dgoals = 0;
+              pw_bs_fresh_env(PP, s);
               if (!lane_step<8>(p, h, OT, s, act, 0u, -1)) continue;
-              uint32_t r = pw_bs_find(tab, tidx, mask, pw_bs_pack(s.P) & keep);
+              uint32_t r = pw_bs_find(set.tab, set.tidx, set.cap - 1u, pw_bs_pack(s.P) & keep);
               if (r >= total) {  // not in an exhausted closed set: counted, the item's status says so
                 atomicAdd(&s_missing, 1u);
                 r = i;
@@ -313,8 +222,7 @@ __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
     if (built) {
       uint32_t* slots = stored ? a.pool_slots + s_slot : nullptr;
       const uint32_t smask = (1u << s_log2) - 1u;
-      if (stored)
-        for (uint32_t i = tid; i <= smask; i += 256u) slots[i] = PW_SB_NOROW;
+      if (stored) pw_sb_slots_clear(slots, smask);
       for (uint32_t i0 = 0; i0 < total; i0 += 256u) {
         const uint32_t i = i0 + tid;
         bool dead = false;
@@ -341,14 +249,7 @@ __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
         const unsigned long long m = __ballot(dead);
         if ((tid & (PW_WAVE - 1)) == 0 && m) atomicAdd(&s_dead, static_cast<uint32_t>(__popcll(m)));
       }
-      if (stored) {
-        __threadfence();
-        __syncthreads();  // the slots are empty: every row takes the first free one on its probe path (the keys are distinct)
-        for (uint32_t i = tid; i < total; i += 256u) {
-          uint32_t sl = pw_bs_hash(store[i]) & smask;
-          while (atomicCAS(slots + sl, PW_SB_NOROW, i) != PW_SB_NOROW) sl = (sl + 1u) & smask;
-        }
-      }
+      if (stored) pw_sb_slots_fill(slots, smask, store, total);  // (uniform: s_row)
     }
     __syncthreads();
     if (tid == 0) {
@@ -370,16 +271,7 @@ __global__ __launch_bounds__(256) void pw_solve_batch_kernel(SolveBatchArgs a) {
 
 // ---- query: live states of a mixed batch -> rows -------------------------------------------------------------------------------
 struct SolveBatchQueryArgs {
-  const PwPuzzleHeader* hdrs;
-  int32_t num_puzzles;
-  const int32_t* item_of_puzzle;
-  const int64_t* row_off;
-  const int64_t* slot_off;
-  const uint8_t* slot_log2;
-  const unsigned long long* pool_key;
-  const uint16_t* pool_cost;
-  const uint8_t* pool_acts;
-  const uint32_t* pool_slots;
+  SolveBatchTables t;
   const int32_t* puzzle_id;  // [n]
   const int8_t* pos;         // [n][npad][2]
   const uint8_t* item_mask;  // or NULL
@@ -389,57 +281,27 @@ struct SolveBatchQueryArgs {
   uint8_t* out_acts;
 };
 
+// what row `idx` of the table at `base` answers (pw_sb_lookup's pair): the cost to go, -1 a dead end, -2 not in the table
+// (pw_sb_lookup's two negative answers, -1 and PW_SB_NOTABLE, both read -2 / no action bits)
+__device__ __forceinline__ int32_t pw_sb_row_cost(const SolveBatchTables& t, int64_t base, int64_t idx) {
+  if (idx < 0) return -2;
+  const uint32_t c = t.pool_cost[base + idx];
+  return c == PW_SOLVE_INF ? -1 : static_cast<int32_t>(c);
+}
+__device__ __forceinline__ uint32_t pw_sb_row_acts(const SolveBatchTables& t, int64_t base, int64_t idx) {
+  return idx >= 0 ? t.pool_acts[base + idx] : 0u;
+}
+
 __global__ __launch_bounds__(256) void pw_solve_batch_query_kernel(SolveBatchQueryArgs a) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= a.n) return;
   if (a.item_mask && a.item_mask[i] == 0) return;
-  const int32_t pid = a.puzzle_id[i];
-  if (pid < 0 || pid >= a.num_puzzles) return;
-  const int32_t item = a.item_of_puzzle[pid];
-  if (item < 0) return;  // no stored table for this puzzle: another table's item, untouched
-  const PwPuzzleHeader* h = a.hdrs + pid;
-  const int N = h->N, W = h->W, H = h->H;
-  uint32_t P[4] = {0u, 0u, 0u, 0u};
-  const int8_t* row = a.pos + i * a.npad * 2;
-  if (a.npad >= 8) {
-    const uint4 v = *reinterpret_cast<const uint4*>(row);
-    P[0] = v.x, P[1] = v.y, P[2] = v.z, P[3] = v.w;
-  } else {
-    const uint2 v = *reinterpret_cast<const uint2*>(row);
-    P[0] = v.x, P[1] = v.y;
-  }
-  // the first N movables only: a pos row may hold anything beyond them.  Every coordinate in 0 .. 15 and inside W x H.
-  bool inside = N <= a.npad;
-#pragma unroll
-  for (int j = 0; j < 8; j++)
-    if (j < N) {
-      const uint32_t xy = (P[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-      const int x = static_cast<int8_t>(xy & 0xffu), y = static_cast<int8_t>(xy >> 8);
-      inside = inside && x >= 0 && x < W && x < 16 && y >= 0 && y < H && y < 16;
-    }
-  int64_t idx = -1;
-  const int64_t base = a.row_off[item];
-  if (inside) {
-    const uint64_t key = pw_bs_pack(P) & pw_sb_keep(N);
-    const uint32_t* slots = a.pool_slots + a.slot_off[item];
-    const uint32_t smask = (1u << a.slot_log2[item]) - 1u;
-    uint32_t sl = pw_bs_hash(key) & smask;
-    for (uint32_t walked = 0; walked <= smask; walked++) {
-      const uint32_t r = slots[sl];
-      if (r == PW_SB_NOROW) break;
-      if (a.pool_key[base + r] == key) {  // a hit is confirmed against the stored key
-        idx = r;
-        break;
-      }
-      sl = (sl + 1u) & smask;
-    }
-  }
+  int64_t base;
+  const int64_t idx = pw_sb_lookup(a.t, a.puzzle_id[i], a.pos + i * a.npad * 2, a.npad, base);
+  if (idx == PW_SB_NOTABLE) return;  // no stored table for this puzzle: another table's item, untouched
   if (a.out_index) a.out_index[i] = static_cast<int32_t>(idx);
-  if (a.out_cost) {
-    const uint32_t c = idx >= 0 ? a.pool_cost[base + idx] : 0u;
-    a.out_cost[i] = idx < 0 ? -2 : (c == PW_SOLVE_INF ? -1 : static_cast<int32_t>(c));
-  }
-  if (a.out_acts) a.out_acts[i] = idx >= 0 ? a.pool_acts[base + idx] : static_cast<uint8_t>(0);
+  if (a.out_cost) a.out_cost[i] = pw_sb_row_cost(a.t, base, idx);
+  if (a.out_acts) a.out_acts[i] = static_cast<uint8_t>(pw_sb_row_acts(a.t, base, idx));
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -473,6 +335,22 @@ struct PwSolveBatch {
   int64_t* d_cs_off;         // [n] where an item's cost_start begins, -1: none
   std::vector<int64_t> h_cs_off;
 };
+
+// the stored tables as a query sees them (pw_solve_batch_query, pw_guide_step)
+static SolveBatchTables solve_batch_tables(const PwSolveBatch* b) {
+  SolveBatchTables t;
+  t.hdrs = b->eng->set->d_headers;
+  t.num_puzzles = b->eng->set->count;
+  t.item_of_puzzle = b->d_item_of_puzzle;
+  t.row_off = b->d_row_off;
+  t.slot_off = b->d_slot_off;
+  t.slot_log2 = b->d_slot_log2;
+  t.pool_key = b->d_key;
+  t.pool_cost = b->d_cost;
+  t.pool_acts = b->d_acts;
+  t.pool_slots = b->d_slots;
+  return t;
+}
 
 static void solve_batch_free_index(PwSolveBatch* b) {
   void* bufs[] = {b->d_rows_by_cost, b->d_cost_start, b->d_cs_off};
@@ -603,21 +481,7 @@ int pw_solve_batch_run(PwSolveBatch* b, const int32_t* puzzles, int32_t n, int64
   off += pw_pad256(static_cast<uint64_t>(max_states_each) * 16);
   a.cost_off = off;
   off += pw_pad256(static_cast<uint64_t>(max_states_each) * 2);
-  const uint32_t ladder[6] = {1u << 16, 1u << 20, 1u << 22, 1u << 24, 1u << 26, 1u << 29};
-  int lv = 0;
-  for (int k = 0; k < 6; k++) {
-    a.level_slots[k] = 0u;
-    a.level_off[k] = 0;
-  }
-  uint64_t have = PW_BS_LDS_SLOTS;
-  for (int k = 0; k < 6 && have < 2ull * static_cast<uint64_t>(max_states_each); k++) {
-    a.level_slots[lv] = ladder[k];
-    a.level_off[lv] = off;
-    off += static_cast<uint64_t>(ladder[k]) * 12;
-    have = ladder[k];
-    lv++;
-  }
-  a.slab_bytes = off;
+  a.slab_bytes = pw_bs_ladder(static_cast<uint64_t>(max_states_each), PW_BS_LDS_SLOTS, 12, off, a.level_slots, a.level_off);
   // persistent workgroups by pw_search_batch's rule; the slabs are the engine's, shared with pw_search_batch
   int64_t groups = 0;
   if (int rc = engine_search_slab(e, n, a.slab_bytes, st, "pw_solve_batch_run", &groups, &a.slab, &a.next)) return rc;
@@ -726,16 +590,7 @@ int pw_solve_batch_query(PwSolveBatch* b, const int32_t* puzzle_id, const int8_t
   if (b->n < 1) return pw_fail(PW_EINVAL, "pw_solve_batch_query: no run yet (call pw_solve_batch_run)");
   PwDeviceGuard guard(b->eng->set->device);
   SolveBatchQueryArgs a;
-  a.hdrs = b->eng->set->d_headers;
-  a.num_puzzles = b->eng->set->count;
-  a.item_of_puzzle = b->d_item_of_puzzle;
-  a.row_off = b->d_row_off;
-  a.slot_off = b->d_slot_off;
-  a.slot_log2 = b->d_slot_log2;
-  a.pool_key = b->d_key;
-  a.pool_cost = b->d_cost;
-  a.pool_acts = b->d_acts;
-  a.pool_slots = b->d_slots;
+  a.t = solve_batch_tables(b);
   a.puzzle_id = puzzle_id;
   a.pos = pos;
   a.item_mask = mask;

@@ -15,8 +15,49 @@ static int failures = 0;
     }                                                       \
   } while (0)
 
+// pw_bs_ladder: the top level (the LDS table without slab levels) holds 2 * max_states, the levels grow strictly, the offsets
+// advance by slots * bytes_per_slot from `off`, unused entries are 0, and the return value is the end of the last table
+static void check_ladder(uint64_t max_states, uint32_t lds_slots, uint32_t bytes_per_slot) {
+  const uint64_t off0 = 768;
+  uint32_t slots[6] = {1, 2, 3, 4, 5, 6};
+  uint64_t offs[6] = {1, 2, 3, 4, 5, 6};
+  const uint64_t end = pw_bs_ladder(max_states, lds_slots, bytes_per_slot, off0, slots, offs);
+  uint64_t top = lds_slots, at = off0;
+  int k = 0;
+  for (; k < 6 && slots[k] != 0u; k++) {
+    CHECK(slots[k] > top);
+    CHECK((slots[k] & (slots[k] - 1u)) == 0u);
+    CHECK(offs[k] == at);
+    CHECK(top < 2 * max_states);  // (a level is only added while the one below is too small)
+    at += static_cast<uint64_t>(slots[k]) * bytes_per_slot;
+    top = slots[k];
+  }
+  CHECK(top >= 2 * max_states);
+  CHECK(end == at);
+  for (; k < 6; k++) CHECK(slots[k] == 0u && offs[k] == 0u);
+}
+
 int main() {
   const unsigned long long never = ~0ull;
+  // pw_bs_ladder around the LDS tables' half load (4 096 and 2 048 slots), the first slab level (2^16) and the largest cap
+  const uint64_t caps4096[] = {1, 2047, 2048, 2049, 1ull << 15, (1ull << 15) + 1, 1ull << 28};
+  for (uint64_t m : caps4096) {
+    check_ladder(m, 4096u, 8);
+    check_ladder(m, 4096u, 12);
+  }
+  const uint64_t caps2048[] = {1024, 1025, 1ull << 15, (1ull << 15) + 1, 1ull << 28};
+  for (uint64_t m : caps2048) check_ladder(m, 2048u, 12);
+  {
+    uint32_t slots[6];
+    uint64_t offs[6];
+    CHECK(pw_bs_ladder(2048, 4096u, 8, 512, slots, offs) == 512 && slots[0] == 0u);  // stays in LDS: no slab table
+    CHECK(pw_bs_ladder(2049, 4096u, 8, 512, slots, offs) == 512 + (8ull << 16) && slots[0] == 1u << 16 && slots[1] == 0u);
+    CHECK(pw_bs_ladder(1024, 2048u, 12, 0, slots, offs) == 0 && slots[0] == 0u);
+    CHECK(pw_bs_ladder(1025, 2048u, 12, 0, slots, offs) == (12ull << 16) && slots[0] == 1u << 16 && slots[1] == 0u);
+    CHECK(pw_bs_ladder((1ull << 15) + 1, 4096u, 8, 0, slots, offs) == (8ull << 16) + (8ull << 20) && slots[1] == 1u << 20 && slots[2] == 0u);
+    CHECK(pw_bs_ladder(1ull << 28, 4096u, 8, 0, slots, offs) > (8ull << 29) && slots[5] == 1u << 29);
+  }
+
   // pw_deadline_ticks: 0 = no limit, at least one tick otherwise, saturated from 1.8e19 ticks upwards
   CHECK(pw_deadline_ticks(0.0, 100000u) == 0ull);
   CHECK(pw_deadline_ticks(-1.0, 100000u) == 0ull);

@@ -487,3 +487,108 @@ def test_deep_and_large_tables_in_one_launch(golden, per_cu):
             b.close()
     finally:
         eng.set_option("search_batch_groups_per_cu", 0)
+
+
+def _host_layers(oz, limit):
+    """One layer-synchronous breadth-first search that goes on past goal states: the number of states the start reaches
+    (None beyond ``limit``) and, per depth 1, 2 ..., (states seen so far, whether the layer holds the first goal state), up
+    to the first layer that ends beyond ``limit``."""
+    is_goal = oz.py.is_goal_state
+    s0 = oz.initial_state
+    seen, layer, layers, solved = {s0}, [s0], [], is_goal(s0)
+    while layer:
+        nxt, found = [], False
+        for s in layer:
+            for a in range(4):
+                n = oz.get_next_state(s, a)
+                if n not in seen:
+                    seen.add(n)
+                    nxt.append(n)
+                    found = found or is_goal(n)
+        layers.append((len(seen), found and not solved))
+        solved = solved or found
+        if len(seen) > limit:
+            return None, is_goal(s0), layers
+        layer = nxt
+    return len(seen), is_goal(s0), layers
+
+
+def _host_verdict(start_is_goal, layers, cap):
+    """pw_search_batch's (verdict, plan_len) from _host_layers: a goal state found in a layer decides, even when the store
+    fills up inside it; otherwise more than ``cap`` states = unknown (tests/test_gpu_search.py's _host_bfs_verdict)."""
+    if start_is_goal:
+        return 1, 0
+    for depth, (count, goal) in enumerate(layers, 1):
+        if goal:
+            return 1, depth
+        if count > cap:
+            return 2, -1
+    return 0, -1
+
+
+def test_the_three_batched_searches_agree_where_they_meet(golden):
+    """pw_search_batch (K5b), pw_solve_batch (K13) and pw_push_solve_batch (K22) share one closed set (csrc/pw_batch_set.inc):
+    one set through all three on one engine, at caps of 300 and 5 000 states.  Who exhausts, who solves and who passes the cap
+    is worked out on the host first (breadth-first searches over the oracle, and the recorded summaries where there are any),
+    so every branch below is known to be taken before anything is launched."""
+    from oracle import c_oracle
+    from pushworld_amd import _capi
+    from pushworld_amd.search import PushSolutionTableBatch, SolutionTableBatch, search_batch
+
+    keys = [k for k in golden.keys if k.startswith(("pytest:", "cpptest:"))] + [k for k in golden.keys if k.startswith("l0:")][::20]
+    texts = [golden.text(k) for k in keys]
+    oracles = [c_oracle.COraclePuzzle(t) for t in texts]
+    fits = [golden.meta[k]["num_movables"] <= 8 and golden.meta[k]["width"] <= 16 and golden.meta[k]["height"] <= 16 for k in keys]
+    searched = [_host_layers(oz, 5000) if f else (None, False, []) for oz, f in zip(oracles, fits)]
+    totals = [t for t, _, _ in searched]
+    for i, k in enumerate(keys):  # the recorded summaries: number of states and cost of the start
+        if k in EXPECT and EXPECT[k][0] <= 5000:
+            assert totals[i] == EXPECT[k][0], k
+    host = {}
+    for cap in (300, 5000):
+        verdicts = [_host_verdict(g, layers, cap) if f else (3, -1) for (_, g, layers), f in zip(searched, fits)]
+        builds = [f and t is not None and t <= cap for f, t in zip(fits, totals)]
+        exhausted = [i for i, v in enumerate(verdicts) if v[0] == 0]
+        solved = [i for i, v in enumerate(verdicts) if v[0] == 1 and builds[i]]
+        assert all(builds[i] for i in exhausted)
+        past_cap = [i for i, f in enumerate(fits) if f and not builds[i]]
+        assert exhausted and solved and past_cap, cap
+        assert any(totals[i] <= 1024 for i in exhausted + solved), cap  # inside the LDS set of all three
+        host[cap] = verdicts, builds, exhausted, solved
+    for i in host[5000][3]:
+        if keys[i] in EXPECT:
+            assert host[5000][0][i][1] == EXPECT[keys[i]][4], keys[i]
+    # past the LDS set (2 048 states at half load): the closed set climbs to 2^16 slots, with and without reaching the cap
+    assert any(b and totals[i] > 2048 for i, b in enumerate(host[5000][1]))
+    assert any(f and t is None for f, t in zip(fits, totals))
+
+    pset = _capi.PuzzleSet([_capi.ParsedPuzzle(t) for t in texts], 0)
+    eng = _capi.Engine(pset, None, 3, 1, _capi.OBS_U8)
+    both_dead = both_live = k22_past_lds = 0
+    for cap in (300, 5000):
+        verdicts, builds, exhausted, solved = host[cap]
+        v5, len5, n5 = search_batch(eng, None, max_states=cap)
+        k13 = SolutionTableBatch(eng, max_states_each=cap)
+        k22 = PushSolutionTableBatch(eng, max_states_each=cap)
+        try:
+            s13, sum13 = k13.status.cpu().numpy(), k13.summary.cpu().numpy()
+            s22, sum22 = k22.status.cpu().numpy(), k22.summary.cpu().numpy()
+        finally:
+            k13.close()
+            k22.close()
+        assert [(int(v), int(p)) for v, p in zip(v5, len5)] == verdicts, cap
+        assert [s in (BUILT, SUMMARY_ONLY) for s in s13] == builds, cap
+        assert [s == NOT_SEARCHED for s in s13] == [not f for f in fits] == [s == NOT_SEARCHED for s in s22], cap
+        for i in exhausted:  # K5b exhausts, K13 builds: the same closed set, and no way to a goal state
+            assert v5[i] == 0 and sum13[i, 0] == n5[i] == totals[i] and sum13[i, 4] == -1, (keys[i], cap)
+        for i in solved:  # K5b's shortest plan is K13's cost of the start
+            assert v5[i] == 1 and sum13[i, 4] == len5[i] >= 0 and sum13[i, 0] == totals[i], (keys[i], cap)
+        for i in range(len(keys)):
+            if builds[i] and s22[i] in (BUILT, SUMMARY_ONLY):  # solvable by steps = solvable by pushes
+                assert (sum13[i, 4] == -1) == (sum22[i, 5] == -1) and sum13[i, 4] >= -1 and sum22[i, 5] >= -1, (keys[i], cap)
+                assert sum22[i, 0] <= sum13[i, 0], (keys[i], cap)  # (a canonical state stands for states the steps reach)
+                both_dead += sum22[i, 5] == -1
+                both_live += sum22[i, 5] >= 0
+        k22_past_lds += int(((s22 == TOO_MANY) | (sum22[:, 0] > 1024)).sum())
+        assert (s22 == TOO_MANY).any() and ((s22 == BUILT) & (sum22[:, 0] <= 1024)).any(), cap
+    assert both_dead > 0 and both_live > 0 and k22_past_lds > 0
