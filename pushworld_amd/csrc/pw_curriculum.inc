@@ -1,7 +1,7 @@
 // pw_curriculum.inc -- K25: the level above the single puzzle, on the device.  Statistics per puzzle from the flags a step
 // left (pw_episode_stats), sampling weights and their prefix sums from the statistics (pw_curriculum_update), and the weighted
 // draw of the next puzzle of a finished environment (pw_resample_weighted).  Part of the single translation unit
-// pw_kernels.hip (included there after pw_engine.inc: uses mix64, rebind_async and check_launch).
+// pw_kernels.hip (included there after pw_engine_step.inc: uses mix64, rebind_async and check_launch).
 //
 // Everything is integer arithmetic: the results are exact and independent of launch geometry and atomic order.  Every launch
 // runs on the caller's stream, allocates nothing, never waits and can be captured.  No atomic returns a value (DESIGN K1f:

@@ -48,4 +48,22 @@ inline unsigned long long pw_deadline_ticks(double time_limit, uint32_t clock_kh
 // the padded movable counts of the position layouts
 inline bool pw_npad_ok(int npad) { return !(npad != 4 && npad != 8 && npad != 16 && npad != 32); }
 
+// Which values an integer setting accepts (a row of the engine option table, pw_engine_options.inc): an inclusive range
+// a .. b, one of the listed values a, b, c (a set of two repeats one), any value >= 0, or any value at all.  The remaining
+// kinds accept nothing here: a read-only setting, and one whose test is code next to the table.
+enum PwValueKind : uint8_t { PW_VALUE_RANGE, PW_VALUE_SET, PW_VALUE_NONNEG, PW_VALUE_ANY, PW_VALUE_CUSTOM, PW_VALUE_READ_ONLY };
+struct PwValueRule {
+  PwValueKind kind;
+  int64_t a, b, c;
+};
+inline bool pw_value_ok(const PwValueRule& r, int64_t value) {
+  switch (r.kind) {
+    case PW_VALUE_RANGE: return value >= r.a && value <= r.b;
+    case PW_VALUE_SET: return value == r.a || value == r.b || value == r.c;
+    case PW_VALUE_NONNEG: return value >= 0;
+    case PW_VALUE_ANY: return true;
+    default: return false;
+  }
+}
+
 #endif  // PW_HOSTLIB_PURE_H

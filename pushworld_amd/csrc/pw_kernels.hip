@@ -448,9 +448,17 @@ struct PageRec {
 #include "pw_expand_kernels.inc"
 #include "pw_render_kernels.inc"
 #include "pw_cells_kernels.inc"
+// the engine half of the C ABI, by family (each file's header says what it needs from the ones before it)
 #include "pw_engine.inc"
+#include "pw_engine_render.inc"
+#include "pw_engine_step.inc"
+#include "pw_engine_step_render.inc"
+#include "pw_engine_expand.inc"
+#include "pw_engine_obs.inc"
+#include "pw_engine_plan.inc"
 #include "pw_cells.inc"
 #include "pw_mailbox.inc"
+#include "pw_engine_options.inc"
 #include "pw_batch_set.inc"
 #include "pw_search.inc"
 #include "pw_solution.inc"

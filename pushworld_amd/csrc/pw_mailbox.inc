@@ -1,5 +1,6 @@
 // pw_mailbox_*: host side of the resident step kernel (pw_mailbox_kernel, K1f in pw_mailbox_kernels.inc).
-// Included by pw_kernels.hip after pw_engine.inc.
+// Included by pw_kernels.hip after the engine files it uses: pw_engine_step.inc (fill_step_args, attach_binding, bound_all) and
+// pw_engine_plan.inc (pw_cpu_relax); before pw_engine_options.inc, which asks mailbox_form_of.
 
 struct PwMailbox {
   PwEngine* e;

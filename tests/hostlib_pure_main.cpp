@@ -93,6 +93,37 @@ int main() {
   // pw_npad_ok: 4, 8, 16, 32 and nothing else
   for (int npad = -64; npad <= 128; npad++) CHECK(pw_npad_ok(npad) == (npad == 4 || npad == 8 || npad == 16 || npad == 32));
 
+  // pw_value_ok: each kind of rule at its two edges and one step beyond
+  {
+    const int64_t lo = std::numeric_limits<int64_t>::min(), hi = std::numeric_limits<int64_t>::max();
+    const PwValueRule r02{PW_VALUE_RANGE, 0, 2, 0};
+    CHECK(!pw_value_ok(r02, -1) && pw_value_ok(r02, 0) && pw_value_ok(r02, 1) && pw_value_ok(r02, 2) && !pw_value_ok(r02, 3));
+    CHECK(!pw_value_ok(r02, lo) && !pw_value_ok(r02, hi));
+    const PwValueRule r20{PW_VALUE_RANGE, 0, 1 << 20, 0};
+    CHECK(!pw_value_ok(r20, -1) && pw_value_ok(r20, 0) && pw_value_ok(r20, 1 << 20) && !pw_value_ok(r20, (1 << 20) + 1));
+    CHECK(!pw_value_ok(r20, int64_t(1) << 32));  // (no truncation to 32 bits: 2^32 is not 0)
+    const PwValueRule s02{PW_VALUE_SET, 0, 2, 2};  // {0, 2}: a set of two repeats a member
+    CHECK(!pw_value_ok(s02, -1) && pw_value_ok(s02, 0) && !pw_value_ok(s02, 1) && pw_value_ok(s02, 2) && !pw_value_ok(s02, 3));
+    const PwValueRule s048{PW_VALUE_SET, 0, 4, 8};
+    CHECK(!pw_value_ok(s048, -1) && pw_value_ok(s048, 0) && !pw_value_ok(s048, 1) && !pw_value_ok(s048, 3) && pw_value_ok(s048, 4) &&
+          !pw_value_ok(s048, 5) && !pw_value_ok(s048, 7) && pw_value_ok(s048, 8) && !pw_value_ok(s048, 9));
+    const PwValueRule sm{PW_VALUE_SET, -1, 0, 2};  // {-1, 0, 2}: the negative member
+    CHECK(!pw_value_ok(sm, -2) && pw_value_ok(sm, -1) && pw_value_ok(sm, 0) && !pw_value_ok(sm, 1) && pw_value_ok(sm, 2) && !pw_value_ok(sm, 3));
+    const PwValueRule s023{PW_VALUE_SET, 0, 2, 3};
+    CHECK(!pw_value_ok(s023, -1) && pw_value_ok(s023, 0) && !pw_value_ok(s023, 1) && pw_value_ok(s023, 2) && pw_value_ok(s023, 3) &&
+          !pw_value_ok(s023, 4));
+    const PwValueRule nn{PW_VALUE_NONNEG, 0, 0, 0};
+    CHECK(!pw_value_ok(nn, lo) && !pw_value_ok(nn, -1) && pw_value_ok(nn, 0) && pw_value_ok(nn, 1) && pw_value_ok(nn, hi));
+    const PwValueRule any{PW_VALUE_ANY, 0, 0, 0};
+    CHECK(pw_value_ok(any, lo) && pw_value_ok(any, -1) && pw_value_ok(any, 0) && pw_value_ok(any, hi));
+    // a read-only setting accepts nothing, and neither does the pure test of a rule that is code
+    const PwValueKind closed[] = {PW_VALUE_READ_ONLY, PW_VALUE_CUSTOM};
+    for (PwValueKind k : closed) {
+      const PwValueRule none{k, 0, 2, 0};
+      CHECK(!pw_value_ok(none, lo) && !pw_value_ok(none, -1) && !pw_value_ok(none, 0) && !pw_value_ok(none, 1) && !pw_value_ok(none, hi));
+    }
+  }
+
   if (failures) return 1;
   std::printf("ok\n");
   return 0;

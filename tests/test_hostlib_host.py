@@ -1,7 +1,8 @@
 """The shared host plumbing (csrc/pw_hostlib.inc, csrc/pw_hostlib_pure.h): the idioms it replaced occur nowhere else,
 ``build.HEADERS`` is the directory listing, the argument checks it serves still answer in each entry point's words (through the
 loaded library and stand-in pointers: every check returns before anything is read through them, no device memory), and the pure
-arithmetic passes a stand-alone host program under the address and undefined-behaviour sanitizers."""
+arithmetic passes a stand-alone host program under the address and undefined-behaviour sanitizers.  And the engine's family files
+(csrc/pw_engine*.inc): their include order, and the option table of pw_engine_options.inc against the header and ``_capi.OPTIONS``."""
 import ctypes
 import os
 import re
@@ -75,6 +76,11 @@ def test_no_local_copies_of_the_helpers():
     unit = _code("pw_kernels.hip")
     mine = unit.index('#include "pw_hostlib.inc"')
     assert unit.index("struct PwEngine {") < mine < unit.index('#include "pw_step_kernels.inc"') < unit.index('#include "pw_engine.inc"')
+    # the engine's family files follow pw_engine.inc in the order their headers name; the option table comes behind pw_mailbox.inc
+    engine = [unit.index('#include "%s"' % f) for f in ("pw_engine.inc", "pw_engine_render.inc", "pw_engine_step.inc",
+                                                         "pw_engine_step_render.inc", "pw_engine_expand.inc", "pw_engine_obs.inc",
+                                                         "pw_engine_plan.inc", "pw_mailbox.inc", "pw_engine_options.inc")]
+    assert engine == sorted(engine)
     for name in HOSTLIB:
         code = _code(name)
         assert "__global__" not in code and "__device__" not in code, name
@@ -102,6 +108,41 @@ def test_build_headers_is_the_directory():
     assert {"pw_hostlib.inc", "pw_hostlib_pure.h"} <= want
     for h in build.HEADERS:
         assert os.path.isfile(os.path.join(CSRC, h)), h
+
+
+# ---- the engine option table (csrc/pw_engine_options.inc): one row per PW_OPT_*, written nowhere else -------------------------------
+OPTIONS_FILE = "pw_engine_options.inc"
+
+
+def _header_options():
+    with open(os.path.join(ROOT, "include", "pushworld_amd.h")) as f:
+        return {name: int(num) for name, num in re.findall(r"^#define (PW_OPT_\w+) (\d+)\b", f.read(), flags=re.M)}
+
+
+def test_header_options_are_the_python_options():
+    header = _header_options()
+    assert len(header) == 58 and len(set(header.values())) == 58
+    assert {name[len("PW_OPT_"):].lower(): num for name, num in header.items()} == _capi.OPTIONS
+
+
+def test_every_option_has_one_table_row():
+    code = _code(OPTIONS_FILE)
+    table = code[code.index("kOptionRows[] = {"):]
+    table = table[:table.index("\n};")]
+    rows = re.findall(r"^\s*\{(PW_OPT_\w+),", table, flags=re.M)
+    assert sorted(rows) == sorted(_header_options()) and len(rows) == len(set(rows)) == 58
+    assert len(re.findall(r"^\s*\{", table, flags=re.M)) == 58  # (and nothing else is a row)
+
+
+@pytest.mark.parametrize("idiom", ["case PW_OPT_", 'return pw_fail(PW_EINVAL, "read-only option")', '"unknown engine option"'])
+def test_option_idioms_live_in_the_option_file(idiom):
+    where = [name for name in _sources() if idiom in _code(name)]
+    assert where == [OPTIONS_FILE], (idiom, where)
+
+
+def test_engine_files_need_no_forward_declaration():
+    for name in _sources():
+        assert not re.search(r"^static [\w ]+\b(rebind_async|live_build|mailbox_form_of)\([^)]*\);", _code(name), flags=re.M), name
 
 
 # ---- the argument checks, through the library ---------------------------------------------------------------------------------------
