@@ -402,6 +402,19 @@ int64_t pw_engine_obs_stride(const PwEngine* e);       /* recommended env stride
                                       environments */
 int pw_engine_set_option(PwEngine* e, int32_t option, int64_t value);
 int64_t pw_engine_get_option(const PwEngine* e, int32_t option);
+/* Only the changed pixel ROWS of a retained buffer are written: a switch on top of PW_OPT_OBS_CHANGED_PAGES (no option number; off by
+ * default).  While it is on, a call that would take the changed-page launch rewrites, per environment, the 16-byte chunks that hold
+ * the pixel rows of the grid rows that differ from what the buffer shows -- one wavefront per environment instead of one per page,
+ * about 0.4 of the bytes.  It has no effect unless PW_OPT_OBS_CHANGED_PAGES is on and the changed form applies, and it may be set
+ * between any two calls: for every legal state both forms leave the buffer equal to the positions the engine remembers.
+ *   - The one state in which they differ is illegal: a movable whose y is negative (written into `pos` by a caller) but whose
+ *     cells reach into the grid.  The page records skip such a movable, so pw_render and the changed-page form draw none of it;
+ *     the row form rewrites every row of that environment and draws the cells that lie inside the grid.
+ *   - A step no longer repairs foreign bytes elsewhere in a changed page: a byte a caller writes into a retained buffer stays until
+ *     the pixel row it lies in changes.  pw_render remains the repair path.
+ * pw_engine_get_obs_changed_rows returns 0 / 1, or a negative error code. */
+int pw_engine_set_obs_changed_rows(PwEngine* e, int32_t on);
+int32_t pw_engine_get_obs_changed_rows(const PwEngine* e);
 /* Durations (milliseconds) of the render launches recorded since the last call, in launch order
  * (PW_OPT_PROFILE_RENDER).  Waits for them to finish, writes at most `cap` values, returns how many
  * were recorded and starts over. */

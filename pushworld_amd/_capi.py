@@ -177,6 +177,8 @@ SIGNATURES = {
     "pw_engine_set_option": (c_int, [c_void_p, c_int32, c_int64]),
     "pw_engine_get_option": (c_int64, [c_void_p, c_int32]),
     "pw_engine_profile_read": (c_int, [c_void_p, POINTER(ctypes.c_float), c_int32]),
+    "pw_engine_set_obs_changed_rows": (c_int, [c_void_p, c_int32]),
+    "pw_engine_get_obs_changed_rows": (c_int32, [c_void_p]),
     "pw_engine_tune_render": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "pw_engine_bad_actions": (c_int64, [c_void_p, c_void_p]),
     "pw_validate_state": (c_int64, [c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_int32), c_void_p]),
@@ -961,6 +963,16 @@ class Engine:
     def get_option(self, key) -> int:
         k = OPTIONS[key] if isinstance(key, str) else int(key)
         return check(lib.pw_engine_get_option(self.handle, k))
+
+    @property
+    def obs_changed_rows(self) -> bool:
+        """``pw_engine_set_obs_changed_rows``: with ``obs_changed_pages`` on, a step rewrites only the changed pixel rows of
+        every environment (one wavefront per environment) instead of the changed pages.  No option number; off by default."""
+        return bool(check(lib.pw_engine_get_obs_changed_rows(self.handle)))
+
+    @obs_changed_rows.setter
+    def obs_changed_rows(self, on) -> None:
+        check(lib.pw_engine_set_obs_changed_rows(self.handle, 1 if on else 0))
 
     def profile_render(self, launches: int) -> None:
         """Time the next ``launches`` render launches with HIP events on their own stream."""

@@ -186,6 +186,10 @@ static bool retained_tracks(const PwEngine* e, const RenderArgs& ra, int32_t bat
   return r.chg_option && r.d_changed && r.shown_cap >= batch && (live_form != 0 || retained_establishes(e, ra, batch));
 }
 
+// the launch of a call whose record writer compared the new state with a valid `shown`: the changed pages (3), or with
+// pw_engine_set_obs_changed_rows the changed pixel rows (4)
+static int retained_changed_form(const PwEngine* e) { return e->ret.rows_option ? 4 : 3; }
+
 static void launch_rowpage(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st) {
   const uint32_t cpe = static_cast<uint32_t>(ra.env_stride / 16);
   int32_t max_envs = static_cast<int32_t>(std::max<uint64_t>(1, ((1ull << 31) - 512) / cpe));
@@ -233,7 +237,8 @@ static void launch_rowpage(PwEngine* e, const RenderArgs& ra, int32_t batch, hip
 
 // rec_ready: the group step kernel of this call already left the page records of (puzzle_id, pos) in e->d_rec
 // live_form: the caller checked (retained_live_form) that only the live pages need rendering: 1 the list, 2 the early exits, 3 the
-// list and of it the pages whose rows changed (PwRetained::d_changed, filled by the record writer of this call)
+// list and of it the pages whose rows changed (PwRetained::d_changed, filled by the record writer of this call), 4 the changed
+// pixel rows of every environment (pw_render_rows_kernel; retained_changed_form)
 // track: the records of this call are compared with PwRetained::d_shown (retained_tracks); a pre-pass here does it then
 static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipStream_t st, bool rec_ready, int live_form, bool track) {
   const bool paged = page_path(e, ra.env_stride) && !ra.do_step && !ra.skip_movables && ensure_rec(e, batch);
@@ -286,7 +291,23 @@ static void launch_render(PwEngine* e, const RenderArgs& ra, int32_t batch, hipS
       ca.live = nullptr;
       ca.live_n = nullptr;
       ca.n_live = 0;
+      // (the live forms run only where one launch covers the batch (live_applies), so `first` is 0 for them: form 3 passes
+      // `changed` as it is; form 4 indexes it by the environment inside the slice, like `rec`, and keeps the offset written out)
       ca.changed = live_form == 3 ? rt.d_changed : nullptr;
+      if (live_form == 4) {
+        // the changed rows, environment by environment: a fixed grid, no page order, no list, no LDS padding (an occupancy cap
+        // only costs here, profiles/obs_changed.txt section 4)
+        ca.changed = rt.d_changed + first;
+        const dim3 rows_grid(static_cast<unsigned>((nb + PW_ROWS_WAVES - 1) / PW_ROWS_WAVES)), rows_block(64 * PW_ROWS_WAVES);
+        if (e->page_f32) {
+          rp.estat = e->d_estat_page;
+          rp.estat_off = e->d_estat_page_off;
+          hipLaunchKernelGGL((pw_render_rows_kernel<float, PW_ROWS_STORE_NT != 0>), rows_grid, rows_block, 0, st, rp, ca);
+        } else {
+          hipLaunchKernelGGL((pw_render_rows_kernel<uint8_t, PW_ROWS_STORE_NT != 0>), rows_grid, rows_block, 0, st, rp, ca);
+        }
+        continue;
+      }
       unsigned grid = page_grid(ca.n_pages, ca.order, ca.run_log2);
       if (live_form == 1 || live_form == 3) {
         ca.live = rt.d_live;
@@ -360,13 +381,30 @@ int pw_render_retained(PwEngine* e, const int32_t* puzzle_id, const int8_t* pos,
   if (rc != PW_OK) return rc;
   const int live_form = retained_live_form(e, ra, batch);
   const bool track = retained_tracks(e, ra, batch, live_form);
-  launch_render(e, ra, batch, static_cast<hipStream_t>(stream), false, (live_form && track && e->ret.shown_valid) ? 3 : live_form,
+  launch_render(e, ra, batch, static_cast<hipStream_t>(stream), false, (live_form && track && e->ret.shown_valid) ? retained_changed_form(e) : live_form,
                 track);
   if (!live_form) retained_after_full_render(e, ra, batch);
   if (track) e->ret.shown_valid = true;  // (whichever form: the pre-pass left the new positions in `shown`)
   return check_launch("pw_render_retained");
 } catch (...) {
   return pw_current_exception();  // nothing C++ leaves the C ABI
+}
+
+// The changed-row switch: no engine option (the option table is closed), one setter and one getter.  Both forms leave the
+// retained buffer equal to `shown`, so the switch may change between any two calls.
+int pw_engine_set_obs_changed_rows(PwEngine* e, int32_t on) try {
+  if (!e) return pw_fail(PW_EINVAL, "pw_engine_set_obs_changed_rows: null engine");
+  e->ret.rows_option = on != 0 ? 1 : 0;
+  return PW_OK;
+} catch (...) {
+  return pw_current_exception();
+}
+
+int32_t pw_engine_get_obs_changed_rows(const PwEngine* e) try {
+  if (!e) return pw_fail(PW_EINVAL, "pw_engine_get_obs_changed_rows: null engine");
+  return e->ret.rows_option;
+} catch (...) {
+  return pw_current_exception();
 }
 
 }  // extern "C"

@@ -41,7 +41,7 @@ int pw_step_render(PwEngine* e, const int32_t* puzzle_id, const uint8_t* actions
       s1.changed = e->ret.d_changed;
     }
     const bool rec_ready = launch_one_step(e, s1, batch, st);
-    launch_render(e, ra, batch, st, rec_ready, (live_form && track && e->ret.shown_valid) ? 3 : live_form, track);
+    launch_render(e, ra, batch, st, rec_ready, (live_form && track && e->ret.shown_valid) ? retained_changed_form(e) : live_form, track);
     if (!live_form) retained_after_full_render(e, ra, batch);
     if (track) e->ret.shown_valid = true;  // (whichever form: the record writer left the new positions in `shown`)
     return check_launch("pw_step_render");

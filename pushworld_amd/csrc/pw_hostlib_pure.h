@@ -66,4 +66,36 @@ inline bool pw_value_ok(const PwValueRule& r, int64_t value) {
   }
 }
 
+// function qualifiers of the helpers a kernel calls too: the kernels' translation unit defines them before it includes this
+// header, a host program leaves them empty
+#ifndef PW_PURE_HD
+#define PW_PURE_HD
+#endif
+
+// The 16-byte chunks [lo, hi) of one environment's ppc-3 image that hold the pixels of the cell rows [r0, r1) of its puzzle
+// (pw_render_rows_kernel; 0 <= r0 < r1 <= H).  The frame is pad_h x pad_w cells, the puzzle H x W cells, es bytes per channel
+// value; the geometry is the page kernel's (PageGeom, page_rows_hit in csrc/pw_render_kernels.inc): cell row r covers the
+// channels [27 pad_w r + shift, 27 pad_w (r + 1) + shift + 9) of the image, where `shift` is the channel of zone entry 0
+// (the top-left frame padding, up to 6 channels early: entries are 9 channels wide and start on multiples of 3 pixels).
+// Clamped to the n_chunks chunks of the image.
+struct PwChunkRange {
+  int32_t lo, hi;
+};
+PW_PURE_HD inline int32_t pw_rows_entry_shift(int32_t pad_h, int32_t pad_w, int32_t H, int32_t W) {
+  const int32_t pady = (pad_h - H) * 3 / 2, padx = (pad_w - W) * 3 / 2;
+  const int32_t c0 = (padx + 2) / 3;
+  return 3 * (pady * pad_w * 3 + padx - 3 * c0);
+}
+PW_PURE_HD inline PwChunkRange pw_rows_chunk_range(int32_t pad_h, int32_t pad_w, int32_t H, int32_t W, int32_t es, int32_t r0,
+                                                   int32_t r1, int32_t n_chunks) {
+  const int32_t shift = pw_rows_entry_shift(pad_h, pad_w, H, W);
+  const int32_t ch_lo = 27 * pad_w * r0 + shift, ch_hi = 27 * pad_w * r1 + shift + 9;  // channels
+  PwChunkRange c;
+  c.lo = ch_lo > 0 ? (ch_lo * es) >> 4 : 0;
+  c.hi = (ch_hi * es + 15) >> 4;
+  if (c.hi > n_chunks) c.hi = n_chunks;
+  if (c.lo > c.hi) c.lo = c.hi;
+  return c;
+}
+
 #endif  // PW_HOSTLIB_PURE_H

@@ -151,6 +151,8 @@ struct PwRetained {
                              // of a call that renders into `obs`, read by that call's render)
   int64_t shown_cap;         // environments the two arrays hold
   bool shown_valid;          // d_shown holds exactly the positions whose picture `obs` holds (implies valid)
+  int rows_option;           // pw_engine_set_obs_changed_rows: the changed launch rewrites the changed pixel rows of every environment
+                             // (pw_render_rows_kernel) instead of the changed pages
 };
 
 struct PwEngine {
@@ -442,6 +444,7 @@ struct PageRec {
   uint64_t rows;  // bit y: some movable's bounding box covers grid row y
 };
 
+#define PW_PURE_HD __host__ __device__  // pw_hostlib_pure.h: pw_rows_chunk_range is called by pw_render_rows_kernel
 #include "pw_hostlib.inc"
 #include "pw_step_kernels.inc"
 #include "pw_mailbox_kernels.inc"

@@ -1242,6 +1242,117 @@ __global__ __launch_bounds__(64) void pw_render_delta_kernel(RenderArgs a, CopyA
   }
 }
 
+// ------------------------------------------------------------------------------------
+// Changed-row render (ppc 3; uint8 and float32; launch_render's live_form 4, pw_engine_set_obs_changed_rows): the
+// environment-major form of the changed-page launch.  The retained buffer shows PwRetained::d_shown, the record writers of
+// this call left the grid rows in which the new state differs from it in CopyArgs::changed -- so per environment only the pixel
+// rows of those cell rows are rewritten: every run of set bits [r0, r1) is one chunk range (pw_rows_chunk_range), walked
+// 256 chunks per pass with the delta kernel's body.  The unit of work is the environment, not the page: ceil(batch / 4)
+// workgroups of four wavefronts, wavefront w of workgroup b owns environment 4 b + w, with an LDS entry window of its own.
+// On the Level-1 mix 18 % of the wavefronts return after three loads, 82 % walk one run, 89 % of the runs are one pass.
+//
+// The wavefronts of a workgroup differ in their pass counts and return early, so behind the one barrier that every thread
+// reaches (the shared palette) each orders its own LDS traffic at wavefront scope: the LDS executes the operations of one
+// wavefront in order, the fences only keep the compiler from moving them.
+//   kNT: non-temporal stores (the page kernel's policy) instead of plain ones (the delta kernel's); fixed at compile time,
+//   see PAGE_STORE above.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ void rows_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// moves the 4 KiB window of a PageEnv to byte offset lo of the same environment's image (page_env's arithmetic)
+template <int ES>
+__device__ __forceinline__ void page_env_move(PageEnv& pe, int lo) {
+  pe.lo = lo;
+  const int t = (lo >= 0 ? lo / ES : -((-lo) / ES)) - pe.shift_bytes;
+  pe.q_lo = (t >= 0 ? t / 9 : -((-t + 8) / 9)) - 2;
+}
+
+#define PW_ROWS_WAVES 4  // environments (wavefronts) per workgroup
+// which store policy the changed-row launch runs with (kNT): 1 non-temporal, 0 plain; both measured, profiles/obs_rows.txt section 2
+#ifndef PW_ROWS_STORE_NT
+#define PW_ROWS_STORE_NT 1
+#endif
+
+template <typename T, bool kNT>
+__global__ __launch_bounds__(64 * PW_ROWS_WAVES) void pw_render_rows_kernel(RenderArgs a, CopyArgs ca) {
+  typedef pw_u32x4 u32x4;
+  constexpr int ES = static_cast<int>(sizeof(T));
+  __shared__ uint32_t pal[ES == 1 ? 16 : 64];
+  __shared__ uint32_t dirty_w[PW_ROWS_WAVES][8];
+  __shared__ __align__(16) uint32_t win_w[PW_ROWS_WAVES][PW_PAGE_ENTRIES];
+  const int tid = threadIdx.x;
+  const int lane = tid & (PW_WAVE - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t env_raw = blockIdx.x * static_cast<uint32_t>(PW_ROWS_WAVES) + static_cast<uint32_t>(wave);
+  // (the wavefronts behind the batch in the last workgroup load the last environment's words and return behind the barrier)
+  const uint32_t env = min(env_raw, static_cast<uint32_t>(a.batch) - 1u);
+  // first level of loads, all from the environment index alone: the changed rows, the record, the positions
+  const uint64_t ch = ca.changed[env];
+  const PageRec r = ca.rec[env];
+  const int xy = page_load_xy(a, env, lane);
+  if (ES == 1) {
+    if (tid < 16) pal[tid] = a.pal_rgb[tid];
+  } else {
+    if (tid < 64) pal[tid] = __float_as_uint(a.pal_f32[tid >> 2][tid & 3]);
+  }
+  __syncthreads();  // the only workgroup barrier: nothing has returned yet
+  if (env_raw >= static_cast<uint32_t>(a.batch)) return;
+  const int H = r.H, W = r.W;
+  uint64_t m = ch & (H >= 64 ? ~0ull : ((1ull << H) - 1ull));  // (a mask of all ones -- a y outside 0 .. 63 -- is rows [0, H))
+  if (m == 0ull) return;  // nothing this environment shows has changed: no other load, no store
+
+  uint32_t* win = win_w[wave];
+  uint32_t* dirty = dirty_w[wave];
+  const PageGeom g = page_geom_hw<ES>(a.pad_h, a.pad_w, H, W);
+  uint8_t* dst = a.obs + static_cast<int64_t>(env) * a.env_stride;
+  const uint8_t* src = ca.simg + static_cast<int64_t>(r.pid) * ca.simg_stride;
+  PageEnv pe = page_env<ES>(a, r.pid, env, 0);
+  while (m != 0ull) {
+    // the lowest run of set bits [r0, r1)
+    const int r0 = __builtin_ctzll(m);
+    const uint64_t t = ~(m >> r0);
+    const int r1 = t != 0ull ? r0 + __builtin_ctzll(t) : 64;
+    m = r1 >= 64 ? 0ull : (m & (~0ull << r1));
+    const PwChunkRange cr = pw_rows_chunk_range(a.pad_h, a.pad_w, H, W, ES, r0, r1, static_cast<int32_t>(ca.n_chunks));
+    for (int c0 = cr.lo; c0 < cr.hi; c0 += 256) {
+      page_env_move<ES>(pe, c0 * 16);
+      u32x4 v[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int c = c0 + lane + 64 * k;
+        v[k] = u32x4{0u, 0u, 0u, 0u};
+        if (c < cr.hi && c >= g.nz_lo && c < g.nz_hi) v[k] = *reinterpret_cast<const u32x4*>(src + static_cast<int64_t>(c) * 16);
+      }
+      rows_wave_sync();  // the previous pass's window is no longer read
+      if (page_prefilter<ES>(a, pe, lane, xy)) {
+        if (lane < 8) dirty[lane] = 0;
+        for (int i = lane; i < PW_PAGE_ENTRIES / 4; i += PW_WAVE) reinterpret_cast<uint4*>(win)[i] = make_uint4(0u, 0u, 0u, 0u);
+        rows_wave_sync();
+        page_mark<ES>(a, pe, lane, xy, win, dirty);
+        rows_wave_sync();
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int lc = lane + 64 * k;
+          if (c0 + lc < cr.hi && ((dirty[lc >> 5] >> (lc & 31)) & 1u)) v[k] = PAGE_CHUNK(pe, c0 + lc, win);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int c = c0 + lane + 64 * k;
+        if (c < cr.hi) {
+          u32x4* p = reinterpret_cast<u32x4*>(dst + static_cast<int64_t>(c) * 16);
+          if (kNT) __builtin_nontemporal_store(v[k], p);
+          else *p = v[k];
+        }
+      }
+    }
+  }
+}
+
 #undef PAGE_CHUNK
 
 // Generic path: any pixels_per_cell / border_width, uint8 or float32 elements.

@@ -96,6 +96,9 @@ class VecPushWorld:
             without touching this object), ``(lo, hi)`` ints (``hi`` None: up to each puzzle's largest level) or two int32
             device tensors [B], read by every draw.
         start_keep_initial: the share of new episodes that start from the puzzle's initial state all the same.
+        changed_rows: where the library turns ``obs_changed_pages`` on by itself (its own buffer, neither ``obs_padding_once`` nor
+            ``obs_changed_pages`` given), a step rewrites only the changed pixel rows of every environment
+            (``Engine.obs_changed_rows``) instead of the changed pages.  False: the changed pages.  Same observations.
     """
 
     # statistics per puzzle and the weighted draw (K25): off unless the constructor was asked for them
@@ -118,7 +121,8 @@ class VecPushWorld:
                  autoreset: bool = False, fused: bool = True, resample=False, seed: int = 0,
                  incremental: bool = False, engine_options: Optional[dict] = None, tune: Optional[bool] = None,
                  tune_allocations: Optional[int] = None, bind: Optional[bool] = None, episode_stats: bool = False,
-                 curriculum=None, start_pool=None, start_band="pool", start_keep_initial: float = 0.0):
+                 curriculum=None, start_pool=None, start_band="pool", start_keep_initial: float = 0.0,
+                 changed_rows: bool = True):
         # (the new options' refusals come first: nothing has been parsed or allocated yet)
         from .start_pool import check_start_options
 
@@ -227,11 +231,15 @@ class VecPushWorld:
             padding_once = self._bind and not resample and "obs_padding_once" not in (engine_options or {})
             # ... and of those only the pages whose pixel rows a step changed (with neither key given: the library's choice too)
             changed_pages = padding_once and "obs_changed_pages" not in (engine_options or {})
+            # ... written as the changed pixel rows of every environment (``Engine.obs_changed_rows``) unless ``changed_rows`` is off
+            rows = changed_pages and bool(changed_rows)
             if tune and tune_allocations:
                 if padding_once:
                     self.engine.set_option("obs_padding_once", 1)  # (before the tuner: it measures the live launch too)
                 if changed_pages:
                     self.engine.set_option("obs_changed_pages", 1)
+                if rows:
+                    self.engine.obs_changed_rows = True
                 # library-owned buffer: candidates are tuned on the initial states (reset() draws them again)
                 self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, None)
                 try:
@@ -250,6 +258,7 @@ class VecPushWorld:
                     self.engine.set_option("obs_padding_once", 0)
                 if changed_pages:
                     self.engine.set_option("obs_changed_pages", 0)
+                self.engine.obs_changed_rows = False
                 self._obs_storage, self.obs = self.engine.alloc_obs(self.num_envs)
                 if tune:
                     self.engine.reset(self.puzzle_id, self.pos, self.steps, self.terminated, self.truncated, None)

@@ -14,6 +14,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROWS_KERNEL = "pw_render_rows_kernel"
 KERNEL_SOURCE = os.path.join(ROOT, "pushworld_amd", "csrc", "pw_render_kernels.inc")
 
 
@@ -45,6 +46,13 @@ def mean_counter(db, kernel, counter, load_all):
     def form(name):  # (kLoadAll, kLive) of an instance's symbol
         m = re.search(r"<[^<>]*,\s*(true|false),\s*(\d)>", name)
         return (m.group(1) == "true", int(m.group(2))) if m and kernel in name else None
+
+    # the changed-row launch (pw_render_rows_kernel<T, kNT>, pw_engine_set_obs_changed_rows) stands in the changed-page form's place
+    # where it ran: one symbol per dtype, no kLoadAll instances -- the same record under both keys
+    rows_form = [r for r in rows if ROWS_KERNEL in r[0]]
+    if rows_form:
+        total = sum(n for _, _, n in rows_form)
+        return max(rows_form, key=lambda r: r[2])[0], sum(val * n for _, val, n in rows_form) / total, total
 
     # (the form is chosen over both kLoadAll instances: a variant that only the tuner's trials of another form ran gets no record)
     ran = {form(r[0])[1] for r in rows if form(r[0]) is not None}
@@ -81,7 +89,7 @@ def main():
         "note": "rocprofv3 --pmc WRITE_SIZE / --pmc FETCH_SIZE (separate passes, --kernel-trace only), mean over all "
                 "dispatches of the kernel's instances (production <T, 0, L, V> and the tuner's <T, 1, L, V>: same code; V = 3, the "
                 "launches of the changed pages of a retained buffer, where there are any, else V = 1, those of its live pages, "
-                "else V = 0, the full render) on the "
+                "else V = 0, the full render; where the changed-row launch pw_render_rows_kernel ran, its dispatches instead) on the "
                 "C3 workload; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies 128-B requests as 64 B)",
     }
     print(json.dumps(rec, indent=1))
